@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """bench.py — farm-steps/s of the HIP wind-farm step (BASELINE.json metric) + roofline + CPU baseline.
 
-  python bench.py [--gpus N --steps K --warmup W]            (N > 1: spawns one rank per GPU itself)
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   (N > 1: spawns one rank per GPU itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps of the headline and prints its line.  --full adds everything else: the
+host-synchronised steps, the other scaling leg (N > 1), the fused env step and env-level legs, the float32-only / float64
+re-solve timings, the per-farm-wind leg, the accuracy sample against the float64 oracle and the CPU baselines.
+--dump-outputs DIR writes what the last timed step returned (rank 0's farms) as DIR/<output>.npy, float32: every farm, or
+a fixed sample of at most DUMP_FARMS of them (rows numpy.random.default_rng(0).choice(B, DUMP_FARMS, replace=False), sorted).
 
 Workload (config.workload): BASELINE.json configs[3] — HornsRev1_Floris (80 turbines in the reference code,
 data_cases.py:269-334), env_batch 65536 IN TOTAL, ws 8 m/s, wd 270 deg, random-walk yaw (dyaw ~ U(-5,5) clipped to
 +-40).  It fits one GPU, so N = 1 runs the whole config on one device.  For N > 1 the default is
 STRONG scaling — the config's total batch sharded into contiguous blocks of independent farms, 65536 / N per GPU, as
-BASELINE configs[3-4] state it ("sharded across 8 MI355X") — and the same run also times the WEAK variant (the full
-config batch on every GPU) and reports it beside the headline (`weak_scaling`); `--scaling weak` swaps the two.  No
+BASELINE configs[3-4] state it ("sharded across 8 MI355X") — and with --full the same run also times the WEAK variant (the
+full config batch on every GPU) and reports it beside the headline (`weak_scaling`); `--scaling weak` swaps the two.  No
 data-path collective either way.  A "step" = one pass of the hot path (wf_step) over the batch, yaw already resident
 in HBM, outputs left in HBM.
 """
@@ -29,6 +35,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_COPY_GBS = 6290.0          # same guide: measured device copy rate
 VALU_PEAK_LANEOPS = 7.864e13   # 256 CU x 4 SIMD x 32 lanes x 2.4 GHz (157.3 TFLOP/s / 2)
+DUMP_FARMS = 8192              # --dump-outputs: 7 floats per turbine and farm, 18 MB at 80 turbines, under 64 MB up to 292
 
 CONFIGS = {
     # name: (layout, TOTAL env batch of the BASELINE config)
@@ -138,6 +145,21 @@ def counter_profile(config: str, B: int, info: dict):
         return None
 
 
+def dump_outputs(out, dirname):
+    """What the timed path's last step returned -> dirname/<name>.npy (float32, the sample of farms of the module docstring)."""
+    import torch
+
+    B = out["power"].shape[0]
+    rows = None
+    if B > DUMP_FARMS:
+        pick = np.sort(np.random.default_rng(0).choice(B, DUMP_FARMS, replace=False))
+        rows = torch.from_numpy(pick).to(out["power"].device)
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in out.items():
+        a = (t if rows is None else t.index_select(0, rows)).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32, copy=False))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -154,6 +176,10 @@ def main():
                     help="a wind per farm: cfg5 wd_b(t) = wd(t) + U(-10,10) (per-farm rotation + sort on the device every step); "
                          "other configs a fixed ws ~ U(6,12), wd ~ 270 + U(-10,10) per farm (the on-the-fly path)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: host-synced steps, the other scaling leg, env / re-solve / per-farm-wind legs, "
+                         "accuracy sample and CPU baselines (--no-env-leg / --no-cpu-baseline drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -202,10 +228,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run_leg(mode):
+    def run_leg(mode, dump_to=None):
         """One timed leg.  strong: this rank owns the contiguous block shard_bounds(B_total, rank, world) of the
         config's farms; weak: it owns B_total farms of a world x B_total batch.  Returns the leg's figures and the
-        live objects (handle, yaw ring, outputs) of rank-local use."""
+        live objects (handle, yaw ring, outputs) of rank-local use.  dump_to: rank 0 writes the last timed step's outputs there."""
         if mode == "strong":
             lo, hi = shard_bounds(B_total, rank, world)
             total = B_total
@@ -261,14 +287,18 @@ def main():
         kern_ms = w.timing_end() / args.steps  # HIP events on the stream the kernel is launched on
         barrier()
         elapsed = time.perf_counter() - t0
-        # host-synchronised per step (what a Python RL loop that reads every observation sees)
-        t1 = time.perf_counter()
-        nsync = min(args.steps, 20)
-        for i in range(nsync):
-            set_wind_at(args.warmup + i)
-            w.step(ring[i % len(ring)], out)
-            w.sync()
-        sync_ms = (time.perf_counter() - t1) / nsync * 1e3
+        if dump_to and rank == 0:
+            dump_outputs(out, dump_to)
+        sync_ms = None
+        if args.full:
+            # host-synchronised per step (what a Python RL loop that reads every observation sees)
+            t1 = time.perf_counter()
+            nsync = min(args.steps, 20)
+            for i in range(nsync):
+                set_wind_at(args.warmup + i)
+                w.step(ring[i % len(ring)], out)
+                w.sync()
+            sync_ms = (time.perf_counter() - t1) / nsync * 1e3
         shards = [[rank, local_rank, lo, hi]]
         ki = w.kernel_info()
         # every rank's kernel, beside its shard (each handle times its kernel families itself, so two ranks may
@@ -291,15 +321,16 @@ def main():
         return dict(mode=mode, B=B, total=total, elapsed=elapsed, kern_ms=kern_ms, sync_ms=sync_ms, w=w, ring=ring, out=out,
                     shards=shards, shard_kernels=kern)
 
-    main_leg = run_leg(args.scaling)
+    main_leg = run_leg(args.scaling, dump_to=args.dump_outputs)
     other_leg = None
     if world > 1:
         main_leg["w"].sync()
         keep = main_leg if rank == 0 else None
         if keep is None:
             main_leg["w"].close()
-        other_leg = run_leg("weak" if args.scaling == "strong" else "strong")
-        other_leg["w"].close()
+        if args.full:
+            other_leg = run_leg("weak" if args.scaling == "strong" else "strong")
+            other_leg["w"].close()
         # the collective part of the job is over: every rank leaves the group now, so that rank 0's remaining legs
         # (fused env step, env-level loop) run with no peer waiting on it
         dist.barrier()
@@ -316,7 +347,7 @@ def main():
     # only reward + local wind observations written): reported beside the headline, not as `value`
     venv_ms = None
     env_level = None
-    if not args.no_env_leg:
+    if args.full and not args.no_env_leg:
         try:
             w.env_config(load_coef=0.1)
             w.env_reset()
@@ -427,7 +458,7 @@ def main():
 
     strict = None
     per_farm = None
-    if not args.no_env_leg:
+    if args.full and not args.no_env_leg:
         try:
             def headline_step(i):
                 if sweep:
@@ -448,7 +479,7 @@ def main():
     # The reference gives every env its own wind at reset (mdp.py:237-258: 8 Weibull(8) clipped to [3, 28] m/s,
     # N(270, 20) mod 360).  The same farms under that distribution — the on-the-fly kernel, about 2 % of the farms
     # flagged — without and with the float64 re-solve: reported under `extra`, never as `value`.
-    if not args.per_env_wind and not args.no_env_leg:
+    if args.full and not args.per_env_wind and not args.no_env_leg:
         try:
             rngw = np.random.default_rng(1234 + cfg_id)
             ws_pf = np.clip(8 * rngw.weibull(8, B), 3, 28)
@@ -478,7 +509,6 @@ def main():
                if sweep else ("ws ~ U(6,12) m/s, wd ~ 270 + U(-10,10) per farm (fixed)" if args.per_env_wind else "ws 8 m/s, wd 270"))
     res = {"metric": "farm_steps_per_sec", "value": value, "unit": "farm-steps/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-           "ms_per_step_host_synced": main_leg["sync_ms"],
            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "config": {"workload": f"{layout_name}Floris x env_batch {main_leg['total']} in total (BASELINE configs[{cfg_id - 1}]), "
                                   + wl_wind + (", yaw ~ U(-40,40)" if cfg_id == 2 else ", random-walk yaw"),
@@ -529,6 +559,8 @@ def main():
            # VALU slots over the practical ceiling)
            "binding_roof": (None if not (cp and vp) else
                             ("valu" if valu_achieved / vp["peak"] >= cp["hbm_bytes"] / (kern_ms * 1e-3) / 1e9 / HBM_COPY_GBS else "fabric"))}
+    if main_leg["sync_ms"] is not None:
+        res["ms_per_step_host_synced"] = main_leg["sync_ms"]
     if other_leg is not None:
         res[f"{other_leg['mode']}_scaling"] = {
             "value": other_leg["total"] * args.steps / other_leg["elapsed"], "unit": "farm-steps/s",
@@ -539,7 +571,7 @@ def main():
                                  "outputs": "reward[B], yaw/wind_speed/wind_direction[B,N]"}
     if env_level:
         res["env_level"] = env_level
-    if not args.no_cpu_baseline and world == 1:  # CPU baseline + accuracy sample: rank 0 of the single-GPU run only
+    if args.full and not args.no_cpu_baseline and world == 1:  # CPU baseline + accuracy sample: rank 0 of the single-GPU run only
         from oracle import c_oracle
 
         sys.path.insert(0, os.path.join(ROOT, "tests"))

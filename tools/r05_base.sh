@@ -7,6 +7,6 @@ for g in 16 8 4x2 2x2; do
   done
 done
 timeout 600 python tools/small_batch_sweep.py > $O/small_batch_sweep.txt 2>&1
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err
 cp wfcrl-env_amd/libwfstep.so /tmp/lib_keep.so
 timeout 600 bash tools/res_stamps.sh > $O/res_stamps.txt 2>&1

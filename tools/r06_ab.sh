@@ -16,7 +16,7 @@ O=gpurun_out/r06_one_launch_ab.txt; : > $O
 for v in four both; do
   for cfg in cfg2 cfg3b cfg4; do
     echo "## WF_RESOLVE_POLICY=$v bench.py --config $cfg" >> $O
-    WF_RESOLVE_POLICY=$v python bench.py --config $cfg --no-cpu-baseline 2>/dev/null | python -c "
+    WF_RESOLVE_POLICY=$v python bench.py --full --config $cfg --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); e=d['extra']['headline_wind']
 print('ms_per_step %.4f  kernel %.4f  float32-only %.4f -> strict %.4f (%d farms re-solved)' % (d['ms_per_step'], d['roofline']['kernel_ms'], e['float32_only']['ms_per_step'], e['with_float64_resolve']['ms_per_step'], e['n_resolved']))" >> $O

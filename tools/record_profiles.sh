@@ -7,8 +7,8 @@ tag=$1
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$tag
 mkdir -p $O
 cd $R
-python3 bench.py > $O/bench.json 2> $O/bench.err
-python3 bench.py --gpus 2 --steps 20 --no-env-leg 2> $O/bench_n2.err | grep "^{" > $O/bench_n2_one_gpu_gloo.json
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --gpus 2 --steps 20 --no-env-leg 2> $O/bench_n2.err | grep "^{" > $O/bench_n2_one_gpu_gloo.json
 python3 tools/all_configs.py 40 > $O/all_configs.txt 2>&1
 (BP=4096 TIME=0 python3 tests/tools/gpu_check.py) > $O/parity_stats.txt 2>&1
 python3 tools/gs_sweep.py 2>&1 | grep ms/step > $O/variant_sweep.txt
