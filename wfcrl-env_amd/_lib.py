@@ -127,13 +127,26 @@ ABI = {
     "wf_last_error": (C.c_char_p, [_P]),
 }
 
+# every symbol include/wfprobe.h declares (flow sampling at arbitrary points): a table of its own — `ABI` stays exactly the
+# surface of include/wfstep.h
+PROBE_ABI = {
+    "wf_probe_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "wf_probe_destroy": (C.c_int, [_P]),
+    "wf_probe_set_points": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int]),
+    "wf_probe_sample": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
+    "wf_probe_last_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "wf_probe_kernel_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "wf_probe_last_error": (C.c_char_p, [_P]),
+}
+
 _lib = None
 
 
 def build(force: bool = False) -> Path:
     """Compile csrc/ into libwfstep.so with hipcc for gfx950 (cross-compiles without a GPU)."""
     srcs = sorted((PKG_DIR / "csrc").glob("*.hip")) + sorted((PKG_DIR / "csrc").glob("*.h"))
-    srcs.append(PKG_DIR.parent / "include" / "wfstep.h")
+    srcs += sorted((PKG_DIR / "csrc" / "probe").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "probe").glob("*.h"))
+    srcs += [PKG_DIR.parent / "include" / "wfstep.h", PKG_DIR.parent / "include" / "wfprobe.h"]
     stale = (not LIB_PATH.exists()) or any(s.stat().st_mtime > LIB_PATH.stat().st_mtime for s in srcs)
     if force or stale:
         subprocess.run(["make", "-j4", "-C", str(PKG_DIR / "csrc")] + (["-B"] if force else []), check=True)
@@ -164,7 +177,7 @@ def load() -> C.CDLL:
             build()
         _share_hip_runtime_with_torch()
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in ABI.items():
+        for name, (res, args) in list(ABI.items()) + list(PROBE_ABI.items()):
             fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -173,6 +186,16 @@ def load() -> C.CDLL:
 
 class WfError(RuntimeError):
     pass
+
+
+def check_probe(rc: int, probe):
+    """`check` for the probe extension: the text comes from wf_probe_last_error."""
+    if rc != WF_OK:
+        msg = load().wf_probe_last_error(probe)
+        text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
+        if rc in (-1, -2):
+            raise ValueError(text)
+        raise WfError(text)
 
 
 def check(rc: int, handle=None):

@@ -163,6 +163,7 @@ class WfStep:
             raise ValueError("xcoords and ycoords layout coordinates must have the same length")
         check(self._lib.wf_set_layout(self._h, x.size, x.ctypes.data, y.ctypes.data), self._h)
         self.num_turbines = int(x.size)
+        self._layout_xy = (x.copy(), y.copy())
 
     def set_layouts(self, xcoords, ycoords, layout_of=None, counts=None):
         """Several layouts in one batch (include/wfstep.h: wf_set_layouts): xcoords / ycoords [n_layouts][n_turbines],
@@ -305,6 +306,83 @@ class WfStep:
         check(self._lib.wf_step(self._h, yaw.ctypes.data, out["power"].ctypes.data, out["wind_speed"].ctypes.data,
                                 out["wind_direction"].ctypes.data, out["load"].ctypes.data, 0), self._h)
         return out
+
+    # -- flow sampling at arbitrary points (include/wfprobe.h) ---------------------------------------
+    def _probe(self, plane: bool = False) -> "_Probe":
+        """The handle's probe object for the caller's points, or the separate one horizontal_plane uses (so that a plane
+        leaves set_probe_points' points alone); created on first use, destroyed in close() before the handle."""
+        name = "_probe_plane" if plane else "_probe_points"
+        pr = getattr(self, name, None)
+        if pr is None:
+            pr = _Probe(self)
+            setattr(self, name, pr)
+        return pr
+
+    def set_probe_points(self, points, per_farm: bool = False):
+        """The points `sample_flow` samples: (P, 3) [x, y, z] in the layout's coordinates, z the height above ground (> 0) —
+        one set for every farm — or, with per_farm=True, (B, P, 3): a set per farm.  NumPy (validated: finite, z > 0; the
+        call synchronises) or a torch float64 CUDA tensor (copied as it is, asynchronously)."""
+        self._probe().set_points(points, per_farm)
+
+    def sample_flow(self, yaw=None, farms=None, out=None):
+        """The flow (u, v, w) [m/s] at the probe points: (n_farms, P, 3) float32, u along the wind, v lateral, w vertical.
+          yaw    (B, N) absolute degrees — torch CUDA float32 tensor or NumPy — or None: the fused env's current yaw state
+          farms  farm indices to solve and sample (any order, repeats allowed), or None: every farm of the batch
+          out    a tensor / array to write into (a torch `out` selects the device path when yaw is None)
+        The listed farms are solved in float64 at `yaw` under the handle's current wind, then sampled.  A probe value is
+        what a rotor-grid point of one additional, wake-less turbine placed there would see in THIS project's sequential
+        solve (include/wfprobe.h); it is not pinned to FLORIS' own full-flow solver (PARITY UNPINNED, as everything beyond
+        the one known-answer vector)."""
+        return self._probe().sample(yaw, farms, out)
+
+    def probe_timing(self, plane: bool = False) -> dict:
+        """HIP-event milliseconds of the two kernels of the last sample_flow (plane=True: of the last horizontal_plane):
+        {"state_ms": the float64 farm solve, "sample_ms": the sampler}; synchronises."""
+        return self._probe(plane).timing()
+
+    def probe_kernel_info(self) -> dict:
+        """Registers, static LDS bytes and private-segment bytes of the two probe kernels as the runtime reports them
+        (hipFuncGetAttributes; tools/probe_timing.py records them next to the timings)."""
+        return self._probe().kernel_info()
+
+    def horizontal_plane(self, farm: int, height: float = None, x_bounds=None, y_bounds=None, resolution=(200, 100), yaw=None):
+        """A horizontal cut through the flow of ONE farm of the batch (FLORIS: calculate_horizontal_plane): dict(x, y, u, v,
+        w) with x (nx,), y (ny,) in the layout's coordinates and u / v / w (ny, nx) float32.  Python on top of sample_flow
+        (same definition of a point value, same PARITY UNPINNED note).  Defaults: hub height; the layout's bounding box
+        plus 2 rotor diameters on every side, stretched to 10 D on the side(s) the farm's wind blows towards.
+        yaw: (N,) for this farm, (B, N), or None = the fused env's yaw state.  Leaves set_probe_points' points alone."""
+        B, N = self.env_batch, self.num_turbines
+        farm = int(farm)
+        if not 0 <= farm < B:
+            raise ValueError("farm index out of range")
+        model = getattr(self, "_model", None) or default_model()
+        D = float(model["rotor_diameter"])
+        z = float(model["hub_height"] if height is None else height)
+        lx, ly = self._layout_xy
+        if x_bounds is None or y_bounds is None:
+            wd = float(self.get_wind()[1][farm]) % 360.0
+            dev = np.radians((wd - 270.0) % 360.0)
+            ex, ey = np.cos(dev), -np.sin(dev)  # downstream direction in the layout's frame
+            if x_bounds is None:
+                x_bounds = (lx.min() - D * (2.0 + 8.0 * max(0.0, -ex)), lx.max() + D * (2.0 + 8.0 * max(0.0, ex)))
+            if y_bounds is None:
+                y_bounds = (ly.min() - D * (2.0 + 8.0 * max(0.0, -ey)), ly.max() + D * (2.0 + 8.0 * max(0.0, ey)))
+        nx, ny = int(resolution[0]), int(resolution[1])
+        x = np.linspace(float(x_bounds[0]), float(x_bounds[1]), nx)
+        y = np.linspace(float(y_bounds[0]), float(y_bounds[1]), ny)
+        X, Y = np.meshgrid(x, y)
+        pr = self._probe(plane=True)
+        pr.set_points(np.stack([X.ravel(), Y.ravel(), np.full(X.size, z)], axis=1), False)
+        if yaw is not None:
+            if _is_torch(yaw):
+                yaw = yaw.detach().cpu().numpy()
+            yaw = np.asarray(yaw, dtype=np.float32)
+            if yaw.size == N:
+                full = np.zeros((B, N), np.float32)
+                full[farm] = yaw.reshape(N)
+                yaw = full
+        uvw = pr.sample(yaw, [farm], None)[0].reshape(ny, nx, 3)
+        return {"x": x, "y": y, "u": uvw[..., 0].copy(), "v": uvw[..., 1].copy(), "w": uvw[..., 2].copy()}
 
     # -- fused env step (SURVEY f1) ---------------------------------------------------------------
     def env_config(self, yaw_lo=-40.0, yaw_hi=40.0, yaw_step=5.0, actuator_rate=0.3, dt=60.0, budget=0.1,
@@ -519,6 +597,11 @@ class WfStep:
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
+            for name in ("_probe_points", "_probe_plane"):  # a probe goes before its handle (include/wfprobe.h)
+                pr = getattr(self, name, None)
+                if pr is not None:
+                    pr.close()
+                    setattr(self, name, None)
             self._lib.wf_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -527,3 +610,86 @@ class WfStep:
             self.close()
         except Exception:
             pass
+
+
+class _Probe:
+    """One `wf_probe` object of a WfStep handle (include/wfprobe.h): its points and the two calls on them."""
+
+    def __init__(self, owner: WfStep):
+        self._w, self._lib = owner, owner._lib
+        self._p = C.c_void_p()
+        check(self._lib.wf_probe_create(owner._h, C.byref(self._p)), owner._h)
+        self.n_points = 0
+        self._host_points = None  # the NumPy points this probe holds (a copy), or None: none yet, or a device tensor's
+
+    def holds(self, points, per_farm: bool) -> bool:
+        """True when `points` is a NumPy array equal to the one this probe was last given: setting it again would change nothing."""
+        last = self._host_points
+        return (last is not None and not _is_torch(points) and last.ndim == (3 if per_farm else 2)
+                and last.shape == np.shape(points) and np.array_equal(last, points))
+
+    def set_points(self, points, per_farm: bool):
+        B = self._w.env_batch
+        on_device = _is_torch(points)
+        self._host_points = None
+        if on_device:
+            pts = points.contiguous()
+            assert pts.is_cuda and str(pts.dtype) == "torch.float64"
+        else:
+            pts = np.ascontiguousarray(points, dtype=np.float64)
+        shape = tuple(pts.shape)
+        if len(shape) != (3 if per_farm else 2) or shape[-1] != 3 or (per_farm and shape[0] != B):
+            raise ValueError("probe points must be (P, 3), or (env_batch, P, 3) with per_farm=True")
+        if on_device:
+            self._w._follow_torch_stream()
+        ptr = pts.data_ptr() if on_device else pts.ctypes.data
+        _lib.check_probe(self._lib.wf_probe_set_points(self._p, shape[-2], ptr, B if per_farm else 1, int(on_device)), self._p)
+        self.n_points = int(shape[-2])
+        self._host_points = None if on_device else pts.copy()
+
+    def sample(self, yaw, farms, out):
+        w = self._w
+        B, N, P = w.env_batch, w.num_turbines, self.n_points
+        fa = None if farms is None else np.ascontiguousarray(farms, dtype=np.int32).reshape(-1)
+        n_farms = B if fa is None else int(fa.size)
+        fptr = None if fa is None else fa.ctypes.data
+        shape = (n_farms, P, 3)
+        if _is_torch(yaw) or _is_torch(out):
+            import torch
+
+            w._follow_torch_stream()
+            yptr = None
+            if yaw is not None:
+                assert yaw.is_cuda and yaw.dtype == torch.float32 and yaw.numel() == B * N
+                yaw = yaw.contiguous()
+                yptr = yaw.data_ptr()
+            if out is None:
+                out = torch.empty(shape, device=yaw.device, dtype=torch.float32)
+            assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and (P == 0 or tuple(out.shape) == shape)
+            _lib.check_probe(self._lib.wf_probe_sample(self._p, yptr, n_farms, fptr, out.data_ptr(), 1), self._p)
+            return out
+        yptr = None
+        if yaw is not None:
+            yaw = np.ascontiguousarray(yaw, dtype=np.float32).reshape(B, N)
+            yptr = yaw.ctypes.data
+        if out is None:
+            out = np.empty(shape, np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and (P == 0 or out.shape == shape)
+        _lib.check_probe(self._lib.wf_probe_sample(self._p, yptr, n_farms, fptr, out.ctypes.data, 0), self._p)
+        return out
+
+    def timing(self) -> dict:
+        a, b = C.c_float(), C.c_float()
+        _lib.check_probe(self._lib.wf_probe_last_timing(self._p, C.byref(a), C.byref(b)), self._p)
+        return {"state_ms": float(a.value), "sample_ms": float(b.value)}
+
+    def kernel_info(self) -> dict:
+        v = (C.c_int * 6)()
+        _lib.check_probe(self._lib.wf_probe_kernel_info(self._p, v), self._p)
+        keys = ("vgprs", "lds_bytes", "scratch_bytes")
+        return {"state": dict(zip(keys, v[0:3])), "sample": dict(zip(keys, v[3:6]))}
+
+    def close(self):
+        if self._p is not None:
+            self._lib.wf_probe_destroy(self._p)
+            self._p = None

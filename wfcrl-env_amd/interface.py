@@ -266,6 +266,20 @@ class HipFlorisInterface(BaseInterface):
                          f" Wind : {self.avg_wind()}\n")
         return self._num_iter == self.max_iter
 
+    def sample_flow_at_points(self, x, y, z):
+        """FLORIS 3.5 `fi.sample_flow_at_points(x, y, z)`: the streamwise velocity u [m/s] at the points (x[k], y[k], z[k])
+        under the current wind and yaw command — float64 array of len(x).  Served by backend.WfStep.sample_flow: the
+        project's turbine solve extended to points, NOT FLORIS' own full-flow solver (PARITY UNPINNED, include/wfprobe.h)."""
+        x, y, z = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y, z))
+        if not (x.shape == y.shape == z.shape):
+            raise ValueError("x, y and z must have the same length")
+        if self._wind_dirty:
+            self.fi.set_wind(self._ws, self._wd)
+            self._wind_dirty = False
+        self.fi.set_probe_points(np.stack([x, y, z], axis=1))
+        uvw = self.fi.sample_flow(self._current_yaw_command.reshape(1, -1).astype(np.float32))
+        return uvw[0, :, 0].astype(np.float64)
+
     # -- accessors (interface.py:615-655) -----------------------------------------------------------
     def get_yaw_command(self):
         return self._current_yaw_command.copy().flatten()

@@ -301,6 +301,25 @@ class VecWindFarmEnv:
         self._num_iter += 1
         return self._obs(out), self._shape(out["reward"]), self._num_iter == self.farm_case.max_iter
 
+    def sample_flow(self, points, farms=None):
+        """The flow (u, v, w) at `points` — (P, 3) for every farm or (num_envs, P, 3) per farm; x, y in the layout's
+        coordinates, z above ground — at the envs' CURRENT yaw state and wind: (n_farms, P, 3) float32, a torch CUDA tensor
+        when the env returns torch.  A virtual met mast or lidar for an agent; reads the env state, never changes it
+        (backend.WfStep.sample_flow with yaw=None; a point value is defined in include/wfprobe.h, PARITY UNPINNED)."""
+        nd = points.dim() if hasattr(points, "dim") else np.ndim(points)
+        # the same NumPy points as the probe holds (a met mast sampled every step): no new upload, which would validate and
+        # synchronise.  The probe itself remembers them, so a set_probe_points on self.fi in between is seen.
+        if not self.fi._probe().holds(points, nd == 3):
+            self.fi.set_probe_points(points, per_farm=nd == 3)
+        out = None
+        if self.return_torch:
+            import torch
+
+            n = self.num_envs if farms is None else int(np.size(farms))
+            P = points.shape[-2] if hasattr(points, "shape") else np.shape(points)[-2]
+            out = torch.empty((n, int(P), 3), dtype=torch.float32, device=f"cuda:{self.fi.device_id}")
+        return self.fi.sample_flow(None, farms=farms, out=out)
+
     # -- checkpoint / resume (SURVEY §5: the env state is tiny; FLORIS itself is stateless between steps) ------
     def get_state(self) -> dict:
         """Everything needed to resume the batch: device env state, the per-farm wind, the step counter."""
