@@ -1,0 +1,112 @@
+"""CPU: the yaw-optimiser extension (include/wfyawopt.h) — header, binding table, kernel metadata — and the properties of
+the reference the GPU tests use (tests/yawopt_ref.py: the coordinate search restated in NumPy over the float64 oracle)."""
+import os
+import re
+import subprocess
+
+import numpy as np
+
+from conftest import ROOT
+
+D = 126.0
+ROW3 = (np.array([0.0, 5 * D, 10 * D]), np.zeros(3))  # three turbines in a row, 5 D apart
+
+
+def _declared(header):
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted(set(re.findall(r"\b(wf_[a-z0-9_]+)\s*\(", text)))
+
+
+def test_yawopt_header_is_bound_and_the_other_tables_are_untouched():
+    from wfcrl_env_amd import _lib
+
+    lib = _lib.load()
+    syms = _declared("wfyawopt.h")
+    assert {"wf_yawopt_create", "wf_yawopt_destroy", "wf_yawopt_config", "wf_yawopt_run", "wf_yawopt_last_timing",
+            "wf_yawopt_last_error"} <= set(syms)
+    assert all(s.startswith("wf_yawopt_") for s in syms), syms
+    for s in syms:
+        assert hasattr(lib, s), f"libwfstep.so does not export {s}"
+        assert s in _lib.YAWOPT_ABI, f"YAWOPT_ABI lacks {s}"
+        assert getattr(lib, s).argtypes == _lib.YAWOPT_ABI[s][1]  # bound by load()
+    assert set(_lib.YAWOPT_ABI) == set(syms)
+    assert lib.wf_version() == 7
+    assert set(_lib.ABI) == set(_declared("wfstep.h")) and set(_lib.PROBE_ABI) == set(_declared("wfprobe.h"))
+    assert not (set(_lib.ABI) | set(_lib.PROBE_ABI)) & set(_lib.YAWOPT_ABI)
+
+
+def test_yawopt_kernels_have_no_private_segment(tmp_path):
+    """The three glue kernels, compiled with the Makefile's flags: no private segment, no spilled register, no out-of-line
+    call (a kernel with a private segment pays ~20 us per launch on MI355X, and the advance kernel runs once per visit).
+    Metadata only."""
+    src = os.path.join(ROOT, "wfcrl-env_amd", "csrc")
+    mk = open(os.path.join(src, "Makefile")).read()
+    flags = re.search(r"^FLAGS \?= (.*)$", mk, flags=re.M).group(1).replace("$(ARCH)", "gfx950").split()
+    assert "YAWOPTOBJ = yawopt/wf_yawopt_kernels.o yawopt/wf_yawopt_abi.o" in mk and "$(YAWOPTOBJ): %.o: %.hip" in mk
+    out = tmp_path / "wf_yawopt_kernels.s"
+    subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-S", "--cuda-device-only", "-o", str(out),
+                                                      os.path.join(src, "yawopt", "wf_yawopt_kernels.hip")], check=True, capture_output=True)
+    text = out.read_text()
+    meta = text[text.index("amdhsa.kernels:"):]
+    seen = {}
+    for block in meta.split("  - .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block).group(1)
+        seen[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
+                      for k in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "group_segment_fixed_size")}
+    assert len(seen) == 3 and all(any(k in n for n in seen) for k in ("wf_yawopt_order_kernel", "wf_yawopt_wind_kernel", "wf_yawopt_advance_kernel")), seen
+    for name, m in seen.items():
+        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (name, m)
+    assert "s_swappc_b64" not in text
+
+
+def test_reference_on_a_row_of_three():
+    """270 deg, 8 m/s along the row: farm power never decreases over the visits, ends above the power at zero yaw, the
+    first turbine steers (a non-zero angle) and the most downstream one — nobody behind it to gain from its yaw — keeps
+    its incumbent 0.  The C restatement of the oracle (the default evaluator of the reference) and the NumPy oracle itself
+    lead to the same angles."""
+    import yawopt_ref
+
+    x, y = ROW3
+    r = yawopt_ref.optimize(x, y, [8.0], [270.0], step=yawopt_ref.numpy_step)
+    assert r["history"].shape == (2 * 3 + 1, 1)
+    assert (np.diff(r["history"][:, 0]) >= 0.0).all()
+    assert r["power"][0] > r["power_initial"][0] * 1.01
+    assert r["power_initial"][0] == yawopt_ref.farm_power(x, y, 8.0, 270.0, np.zeros((1, 3)), step=yawopt_ref.numpy_step)[0]
+    assert list(r["order"][0]) == [0, 1, 2]
+    assert r["yaw"][0, 2] == 0.0 and r["yaw"][0, 0] != 0.0
+    assert np.isfinite(r["margin"][0]) and r["margin"][0] > 0.0
+    c = yawopt_ref.optimize(x, y, [8.0], [270.0])
+    assert np.array_equal(c["yaw"], r["yaw"]) and abs(c["power"][0] / r["power"][0] - 1.0) < 1e-12
+    # the wind from the other end: the visit order turns round, and so does the roles of the turbines
+    e = yawopt_ref.optimize(x, y, [8.0], [90.0])
+    assert list(e["order"][0]) == [2, 1, 0] and e["yaw"][0, 0] == 0.0 and e["yaw"][0, 2] != 0.0
+
+
+def test_reference_keeps_an_incumbent_outside_the_bounds():
+    """One turbine, bounds (5, 25), start 0: every candidate lies in [5, 25] and yields less than zero yaw does, so the
+    incumbent 0 — outside the bounds, never clipped — survives every visit."""
+    import yawopt_ref
+
+    r = yawopt_ref.optimize(np.array([0.0]), np.array([0.0]), [8.0], [270.0], bounds=(5.0, 25.0))
+    assert r["yaw"][0, 0] == 0.0 and r["power"][0] == r["power_initial"][0]
+    assert (r["history"] == r["power_initial"][0]).all()
+
+
+def test_reference_candidate_grids():
+    import yawopt_ref
+
+    assert np.array_equal(yawopt_ref.pass0_candidates(-25.0, 25.0, 5), np.float32([-25.0, -12.5, 0.0, 12.5, 25.0]))
+    assert np.array_equal(yawopt_ref.pass0_candidates(0.0, 25.0, 3), np.float32([0.0, 12.5, 25.0]))
+    h = 12.5
+    c = yawopt_ref.refine_candidates(0.0, h, 4, -25.0, 25.0)
+    assert np.allclose(c, np.float32([-0.6 * h, -0.2 * h, 0.2 * h, 0.6 * h]), rtol=0, atol=1e-6)
+    assert yawopt_ref.pass_steps(-25.0, 25.0, (5, 4)) == [(5, None, 12.5), (4, 12.5, 5.0)]
+    assert yawopt_ref.pass_steps(-25.0, 25.0, (5, 4, 4))[2] == (4, 5.0, 2.0)
+    # clipping at the bounds: a bracket that reaches past hi is cut there (two candidates fall together), never beyond
+    c = yawopt_ref.refine_candidates(25.0, h, 4, -25.0, 25.0)
+    assert np.array_equal(c, np.float32([25.0 - 0.6 * h, 25.0 - 0.2 * h, 25.0, 25.0]))
+    c = yawopt_ref.refine_candidates(np.float32([-25.0, 3.0]), h, 4, -25.0, 25.0)
+    assert c.shape == (2, 4) and c.min() == -25.0 and (c[0, :2] == -25.0).all() and (np.abs(c[1] - 3.0) <= 0.6 * h + 1e-6).all()
+    # K = 1: the one candidate of a refining pass is the incumbent itself (the bracket's centre)
+    assert yawopt_ref.refine_candidates(7.5, h, 1, -25.0, 25.0)[0] == np.float32(7.5)

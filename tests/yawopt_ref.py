@@ -1,0 +1,118 @@
+"""TEST INFRASTRUCTURE — the reference for the batched yaw optimisation (include/wfyawopt.h): a plain NumPy restatement of the
+coordinate search, run over the float64 oracle, which it does not modify.
+
+The algorithm, as the header states it:
+  order    each farm visits its turbines in ascending wind-aligned x' (oracle rotate_layout / sort_order: ties by ascending
+           caller index)
+  pass 0   candidates c_k = lo + k h_0, h_0 = (hi - lo) / (K_0 - 1), k = 0 .. K_0 - 1, plus the incumbent
+  pass p   candidates inc - h + (j + 1) s, s = 2 h / (K_p + 1), h = h_{p-1}, j = 0 .. K_p - 1, plus the incumbent; h_p = s
+  every candidate is clipped to [lo, hi] in float64 and rounded once to float32; the incumbent is never clipped
+  decision strictly greater farm power replaces the incumbent; among equal maxima the lowest index wins
+  farm power = the oracle's float64 per-turbine powers added in caller order
+
+At every decision it records the relative MARGIN between the best and the second-best DISTINCT candidate (candidates whose
+float32 angle equals the winner's are the same configuration, not a rival): a device whose farm powers are good to a few
+1e-7 takes the same decisions wherever the smallest margin of a farm is well above that — which is what lets the GPU tests
+compare yaw angles honestly, and leave out the few farms where the reference's own decision hangs on less.
+"""
+import numpy as np
+
+from oracle.floris_gch_numpy import ModelParams, rotate_layout, sort_order
+
+
+def pass_steps(lo, hi, passes):
+    """[(K_p, h_{p-1} or None, s_p)]: the bracket half-width a pass starts from and the spacing it leaves."""
+    out, h = [], None
+    for p, K in enumerate(passes):
+        s = (hi - lo) / (K - 1) if p == 0 else 2.0 * h / (K + 1)
+        out.append((int(K), h, s))
+        h = s
+    return out
+
+
+def pass0_candidates(lo, hi, K):
+    c = lo + np.arange(K, dtype=np.float64) * ((hi - lo) / (K - 1))
+    return np.clip(c, lo, hi).astype(np.float32)
+
+
+def refine_candidates(inc, h, K, lo, hi):
+    """inc: float (or array, broadcast over the last axis): K candidates inside [inc - h, inc + h], clipped to the bounds."""
+    inc = np.asarray(inc, dtype=np.float64)[..., None]
+    c = (inc - h) + (np.arange(K, dtype=np.float64) + 1.0) * (2.0 * h / (K + 1))
+    return np.clip(c, lo, hi).astype(np.float32)
+
+
+def visit_order(x, y, wd):
+    xr, _ = rotate_layout(x, y, wd % 360.0)
+    return sort_order(xr)
+
+
+def _c_step(x, y, ws, wd, yaw, p):
+    from oracle import c_oracle
+
+    return c_oracle.farm_step_batch(x, y, ws, wd, yaw, p)["power"]
+
+
+def numpy_step(x, y, ws, wd, yaw, p):
+    from oracle.floris_gch_numpy import farm_step_batch
+
+    return farm_step_batch(x, y, ws, wd, yaw, p)["power"]
+
+
+def farm_power(x, y, ws, wd, yaw, p=None, step=None):
+    """(B,) float64: the oracle's per-turbine powers at yaw (B, N), added in caller order."""
+    yaw = np.atleast_2d(np.asarray(yaw, dtype=np.float64))
+    ws = np.broadcast_to(np.asarray(ws, np.float64), (yaw.shape[0],))
+    wd = np.broadcast_to(np.asarray(wd, np.float64), (yaw.shape[0],))
+    pw = (step or _c_step)(x, y, ws, wd, yaw, p or ModelParams())
+    s = np.zeros(yaw.shape[0])
+    for t in range(yaw.shape[1]):
+        s = s + pw[:, t]
+    return s
+
+
+def optimize(x, y, ws, wd, yaw0=None, bounds=(-25.0, 25.0), passes=(5, 4), p=None, step=None):
+    """ws, wd: (B,) one wind per farm.  Returns dict(yaw (B, N) float32, power (B,), power_initial (B,), margin (B,) the
+    smallest decision margin of each farm, history (visits + 1, B) farm power before the first and after every visit).
+    step: `numpy_step` for the NumPy oracle; default the C restatement of it (the same float64 arithmetic, batched)."""
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    ws, wd = np.atleast_1d(np.asarray(ws, np.float64)), np.atleast_1d(np.asarray(wd, np.float64))
+    B, N = ws.size, x.size
+    lo, hi = float(bounds[0]), float(bounds[1])
+    best = np.zeros((B, N), np.float32) if yaw0 is None else np.array(yaw0, dtype=np.float32).reshape(B, N)
+    order = np.stack([visit_order(x, y, wd[b]) for b in range(B)])
+    margin = np.full(B, np.inf)
+    history = []
+    rows = np.arange(B)
+    p_init = None
+    for pi, (K, h, _) in enumerate(pass_steps(lo, hi, passes)):
+        for s in range(N):
+            t = order[:, s]
+            inc = best[rows, t]
+            cand = np.broadcast_to(pass0_candidates(lo, hi, K), (B, K)) if pi == 0 else refine_candidates(inc, h, K, lo, hi)
+            vals = np.concatenate([inc[:, None], cand], axis=1)  # index 0: the incumbent
+            yaw = np.repeat(best[:, None, :], K + 1, axis=1).astype(np.float64)
+            yaw[rows, :, t] = vals
+            pw = farm_power(x, y, np.repeat(ws, K + 1), np.repeat(wd, K + 1), yaw.reshape(B * (K + 1), N), p, step).reshape(B, K + 1)
+            if p_init is None:
+                p_init = pw[:, 0].copy()
+                history.append(p_init)
+            w = np.argmax(pw, axis=1)  # first maximum: the incumbent, then the lowest index, keep a tie
+            pb = pw[rows, w]
+            rival = np.where(vals != vals[rows, w][:, None], pw, -np.inf).max(axis=1)
+            margin = np.minimum(margin, np.where(np.isfinite(rival), (pb - rival) / pb, np.inf))
+            best[rows, t] = vals[rows, w]
+            history.append(pb)
+    return {"yaw": best, "power": history[-1], "power_initial": p_init, "margin": margin, "history": np.array(history),
+            "order": order}
+
+
+# ---- the farms the GPU tests and tools/yawopt_timing.py share ------------------------------------------------------------
+GPU_CASE_SEED = 40  # checked on the CPU with the oracle: 3 of 32 farms below a margin of 1e-5 on either layout (default passes)
+
+
+def gpu_case(layouts, name, n_farms=32):
+    """(x, y, ws, wd): `n_farms` farms of layout `name` under winds drawn with GPU_CASE_SEED, 6-12 m/s, any direction."""
+    x, y = np.asarray(layouts[name]["xcoords"], np.float64), np.asarray(layouts[name]["ycoords"], np.float64)
+    rng = np.random.default_rng(GPU_CASE_SEED)
+    return x, y, rng.uniform(6.0, 12.0, n_farms), rng.uniform(0.0, 360.0, n_farms)

@@ -139,6 +139,18 @@ PROBE_ABI = {
     "wf_probe_last_error": (C.c_char_p, [_P]),
 }
 
+# every symbol include/wfyawopt.h declares (batched yaw optimisation on the device): again a table of its own
+YAWOPT_ABI = {
+    "wf_yawopt_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "wf_yawopt_destroy": (C.c_int, [_P]),
+    "wf_yawopt_config": (C.c_int, [_P, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int]),
+    "wf_yawopt_run": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int]),
+    "wf_yawopt_set_timing": (C.c_int, [_P, C.c_int]),
+    "wf_yawopt_last_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "wf_yawopt_evaluator": (_P, [_P]),
+    "wf_yawopt_last_error": (C.c_char_p, [_P]),
+}
+
 _lib = None
 
 
@@ -146,7 +158,8 @@ def build(force: bool = False) -> Path:
     """Compile csrc/ into libwfstep.so with hipcc for gfx950 (cross-compiles without a GPU)."""
     srcs = sorted((PKG_DIR / "csrc").glob("*.hip")) + sorted((PKG_DIR / "csrc").glob("*.h"))
     srcs += sorted((PKG_DIR / "csrc" / "probe").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "probe").glob("*.h"))
-    srcs += [PKG_DIR.parent / "include" / "wfstep.h", PKG_DIR.parent / "include" / "wfprobe.h"]
+    srcs += sorted((PKG_DIR / "csrc" / "yawopt").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "yawopt").glob("*.h"))
+    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfprobe.h", "wfyawopt.h")]
     stale = (not LIB_PATH.exists()) or any(s.stat().st_mtime > LIB_PATH.stat().st_mtime for s in srcs)
     if force or stale:
         subprocess.run(["make", "-j4", "-C", str(PKG_DIR / "csrc")] + (["-B"] if force else []), check=True)
@@ -177,7 +190,7 @@ def load() -> C.CDLL:
             build()
         _share_hip_runtime_with_torch()
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in list(ABI.items()) + list(PROBE_ABI.items()):
+        for name, (res, args) in list(ABI.items()) + list(PROBE_ABI.items()) + list(YAWOPT_ABI.items()):
             fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -192,6 +205,16 @@ def check_probe(rc: int, probe):
     """`check` for the probe extension: the text comes from wf_probe_last_error."""
     if rc != WF_OK:
         msg = load().wf_probe_last_error(probe)
+        text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
+        if rc in (-1, -2):
+            raise ValueError(text)
+        raise WfError(text)
+
+
+def check_yawopt(rc: int, opt):
+    """`check` for the yaw-optimiser extension: the text comes from wf_yawopt_last_error."""
+    if rc != WF_OK:
+        msg = load().wf_yawopt_last_error(opt)
         text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
         if rc in (-1, -2):
             raise ValueError(text)

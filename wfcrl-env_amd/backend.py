@@ -384,6 +384,36 @@ class WfStep:
         uvw = pr.sample(yaw, [farm], None)[0].reshape(ny, nx, 3)
         return {"x": x, "y": y, "u": uvw[..., 0].copy(), "v": uvw[..., 1].copy(), "w": uvw[..., 2].copy()}
 
+    # -- batched yaw optimisation on the device (include/wfyawopt.h) -----------------------------------
+    def _yawopt(self) -> "_YawOpt":
+        """The handle's optimiser object; created on first use, destroyed in close() before the handle."""
+        yo = getattr(self, "_yawopt_obj", None)
+        if yo is None:
+            yo = self._yawopt_obj = _YawOpt(self)
+        return yo
+
+    def optimize_yaw(self, yaw0=None, farms=None, bounds=(-25.0, 25.0), passes=(5, 4), strict=False, max_eval_farms=65536,
+                     out=None):
+        """The best static yaw for the handle's current wind, by the project's own coordinate search (include/wfyawopt.h;
+        in the spirit of "serial refine", not pinned to FLORIS' optimiser): turbines are visited upstream to downstream,
+        pass 0 tries `passes[0]` angles across `bounds` per turbine, each later pass `passes[p]` angles inside the bracket
+        the previous one left; the incumbent is always a candidate and only a strictly greater farm power replaces it.
+          yaw0    (n_farms, N) start (row i belongs to farms[i]) — torch CUDA float32 tensor or NumPy — or None: zeros
+          farms   farm indices to optimise (any order), or None: every farm of the batch
+          strict  every candidate is evaluated in float64 (validation); otherwise the handle's own resolve mode
+          max_eval_farms  farms the optimiser's evaluator handle may hold: longer lists run in chunks
+          out     dict of tensors / arrays to write into (a torch `out` selects the device path when yaw0 is None)
+        Returns dict(yaw (n_farms, N) degrees, power (n_farms,) W, power_initial (n_farms,) W at yaw0), float32.  With torch
+        tensors the call only enqueues work on torch's current stream (include/wfyawopt.h lists when it has to wait);
+        with NumPy it returns the results.  The handle itself — wind, env state, calibration — is not touched."""
+        return self._yawopt().run(yaw0, farms, bounds, passes, strict, max_eval_farms, out)
+
+    def yawopt_timing(self, detail=None) -> dict:
+        """detail=True / False: the following optimize_yaw calls record (do not record) an event around every launch, so
+        that step and glue time can be told apart — returns None.  detail=None: HIP-event milliseconds of the last
+        optimize_yaw {"total_ms", "step_ms", "glue_ms"} (the last two 0 without detail); synchronises."""
+        return self._yawopt().timing(detail)
+
     # -- fused env step (SURVEY f1) ---------------------------------------------------------------
     def env_config(self, yaw_lo=-40.0, yaw_hi=40.0, yaw_step=5.0, actuator_rate=0.3, dt=60.0, budget=0.1,
                    load_coef=0.1, discrete=False, power_mw=False):
@@ -602,6 +632,10 @@ class WfStep:
                 if pr is not None:
                     pr.close()
                     setattr(self, name, None)
+            yo = getattr(self, "_yawopt_obj", None)  # ... and so does the yaw optimiser (include/wfyawopt.h)
+            if yo is not None:
+                yo.close()
+                self._yawopt_obj = None
             self._lib.wf_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -693,3 +727,69 @@ class _Probe:
         if self._p is not None:
             self._lib.wf_probe_destroy(self._p)
             self._p = None
+
+
+class _YawOpt:
+    """The `wf_yawopt` object of a WfStep handle (include/wfyawopt.h)."""
+
+    def __init__(self, owner: WfStep):
+        self._w, self._lib = owner, owner._lib
+        self._o = C.c_void_p()
+        check(self._lib.wf_yawopt_create(owner._h, C.byref(self._o)), owner._h)
+
+    def run(self, yaw0, farms, bounds, passes, strict, max_eval_farms, out):
+        w = self._w
+        B, N = w.env_batch, w.num_turbines
+        K = (C.c_int * max(len(passes), 1))(*[int(k) for k in passes])
+        _lib.check_yawopt(self._lib.wf_yawopt_config(self._o, float(bounds[0]), float(bounds[1]), len(passes), K, int(bool(strict)),
+                                                     int(max_eval_farms)), self._o)
+        fa = None if farms is None else np.ascontiguousarray(farms, dtype=np.int32).reshape(-1)
+        n = B if fa is None else int(fa.size)
+        fptr = None if fa is None else fa.ctypes.data
+        shapes = {"yaw": (n, N), "power": (n,), "power_initial": (n,)}
+        on_device = _is_torch(yaw0) or (out is not None and _is_torch(out["yaw"]))
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            yptr = None
+            if yaw0 is not None:
+                assert yaw0.is_cuda and yaw0.dtype == torch.float32 and tuple(yaw0.shape) == (n, N)
+                yaw0 = yaw0.contiguous()
+                yptr = yaw0.data_ptr()
+            if out is None:
+                out = {k: torch.empty(s, device=yaw0.device, dtype=torch.float32) for k, s in shapes.items()}
+            for k, s in shapes.items():
+                assert out[k].is_cuda and out[k].dtype == torch.float32 and out[k].is_contiguous() and tuple(out[k].shape) == s, k
+            ptrs = [out[k].data_ptr() for k in shapes]
+        else:
+            yptr = None
+            if yaw0 is not None:
+                yaw0 = np.ascontiguousarray(yaw0, dtype=np.float32)
+                if yaw0.shape != (n, N):
+                    raise ValueError("yaw0 must be (n_farms, num_turbines): a row per optimised farm")
+                yptr = yaw0.ctypes.data
+            if out is None:
+                out = {k: np.empty(s, np.float32) for k, s in shapes.items()}
+            for k, s in shapes.items():
+                assert out[k].dtype == np.float32 and out[k].flags.c_contiguous and out[k].shape == s, k
+            ptrs = [out[k].ctypes.data for k in shapes]
+        _lib.check_yawopt(self._lib.wf_yawopt_run(self._o, yptr, n, fptr, ptrs[0], ptrs[1], ptrs[2], int(on_device)), self._o)
+        return out
+
+    def timing(self, detail=None):
+        if detail is not None:
+            _lib.check_yawopt(self._lib.wf_yawopt_set_timing(self._o, int(bool(detail))), self._o)
+            return None
+        t = [C.c_float(), C.c_float(), C.c_float()]
+        _lib.check_yawopt(self._lib.wf_yawopt_last_timing(self._o, *[C.byref(v) for v in t]), self._o)
+        return {"total_ms": float(t[0].value), "step_ms": float(t[1].value), "glue_ms": float(t[2].value)}
+
+    def evaluator(self):
+        """The evaluator's raw handle (None before the first run): tools/yawopt_timing.py times a plain wf_step loop on it."""
+        return self._lib.wf_yawopt_evaluator(self._o)
+
+    def close(self):
+        if self._o is not None:
+            self._lib.wf_yawopt_destroy(self._o)
+            self._o = None

@@ -1,0 +1,182 @@
+// wf_yawopt_kernels.hip — the loop around the step kernel that makes a coordinate search over yaw run on the device
+// (include/wfyawopt.h).  Candidate evaluation is the existing wf_step on the optimiser's evaluator handle; these kernels are
+// the glue, so that a whole optimisation is enqueued without a host round trip:
+//
+//   wf_yawopt_order_kernel    once per chunk: each slot's visit order — the float64 rotation and stable rank sort of
+//                             wf_geometry_kernel / wf_probe_state_kernel; one workgroup per slot, one thread per turbine.
+//   wf_yawopt_wind_kernel     once per chunk, only for a parent with a wind per farm: each farm's wind repeated over its
+//                             candidate rows (device to device), what wf_set_wind on the evaluator then takes.
+//   wf_yawopt_advance_kernel  once per visit, select and expand fused: per slot, sum the power of the previous visit's K + 1
+//                             candidates (caller's turbine order, float64), pick the winner (strictly greater than the
+//                             incumbent; lowest index among equals), update the slot's best yaw, and write the next visit's
+//                             [R][N] yaw block — the best yaw with one entry replaced per row.
+//
+// Lane layout of the advance kernel: ONE WAVE PER SLOT.  A slot's yaw block and power block are contiguous [R][N] floats
+// (wf_yawopt.h), so the wave walks them with lane = consecutive float: every global load and store of the only traffic that
+// scales as B K N is a full 256-byte line per wave instruction.  The power block is staged in LDS first, because the sums
+// must run in a FIXED order (turbine 0, 1, ... in float64): lane k then adds row k from LDS — a stride-N walk that would
+// touch a cache line per lane in global memory.  Trip counts are run-time values (no unrolled register arrays): no private
+// segment, no spill (tests/test_yawopt.py reads the metadata).
+#include <hip/hip_runtime.h>
+
+#include "../wf_f64_math.h"
+#include "wf_yawopt.h"
+
+namespace {
+
+__device__ __forceinline__ int yo_farm(const WfYawoptSlots& sl, int slot) {
+  const int s = sl.base + (slot < sl.n_slots ? slot : 0);
+  return sl.farms ? sl.farms[s] : s;
+}
+
+// candidate j of a visit's grid around `inc` (wf_yawopt.h: WfYawoptGrid).  The library is built with -ffp-contract=off: a
+// product and a sum stay two roundings, as in the NumPy restatement.
+__device__ __forceinline__ float yo_candidate(const WfYawoptGrid& g, double inc, int j, double lo, double hi) {
+  double c = g.mode == 0 ? g.a + (double)j * g.b : (inc - g.a) + (double)(j + 1) * g.b;
+  c = c < lo ? lo : c;
+  c = c > hi ? hi : c;
+  return (float)c;
+}
+
+}  // namespace
+
+#define YO_MAX_N 256
+
+__global__ __launch_bounds__(YO_MAX_N) void wf_yawopt_order_kernel(const WfYawoptOrderArgs a) {
+  __shared__ double sx[YO_MAX_N];
+  const int N = a.N, t = threadIdx.x, slot = blockIdx.x;
+  const int b = yo_farm(a.sl, slot);
+  // wd % 360, rotation about the bounding-box centre [A.1]: the arithmetic of wf_geometry_kernel
+  double wdm = fmod(a.wd[(size_t)b * a.wind_stride], 360.0);
+  if (wdm < 0.0) wdm += 360.0;
+  double dev = fmod(wdm - 270.0, 360.0);
+  if (dev < 0.0) dev += 360.0;
+  dev = fmod(dev + 360.0, 360.0);
+  double ca, sa;
+  sincos_any(dev * (M_PI / 180.0), sa, ca);
+  double xr = 0.0;
+  if (t < N) {
+    const double xo = a.lx[t] - a.xc, yo = a.ly[t] - a.yc;
+    xr = xo * ca - yo * sa + a.xc;
+    sx[t] = xr;
+  }
+  __syncthreads();
+  if (t < N) {
+    int rank = 0;
+    for (int u = 0; u < N; ++u) {
+      const double xu = sx[u];
+      rank += (xu < xr) || (xu == xr && u < t);
+    }
+    a.order[(size_t)slot * N + rank] = t;
+  }
+}
+
+__global__ __launch_bounds__(256) void wf_yawopt_wind_kernel(const WfYawoptWindArgs a) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= a.sl.C * a.R) return;
+  const int b = yo_farm(a.sl, e / a.R);
+  a.ews[e] = a.ws[b];
+  a.ewd[e] = a.wd[b];
+}
+
+// Dynamic LDS per wave: 32 doubles (the candidates' power sums), 32 floats (the next candidates), N floats (the slot's best
+// yaw), R N floats (the power block); the launcher sizes the region (a multiple of 16 bytes) and the waves per block.
+#define YO_HDR_BYTES (WF_YAWOPT_ROWS_MAX * 8 + WF_YAWOPT_ROWS_MAX * 4)
+
+__global__ __launch_bounds__(256) void wf_yawopt_advance_kernel(const WfYawoptAdvanceArgs a, int region_bytes) {
+  extern __shared__ double yo_dyn[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int slot = blockIdx.x * (blockDim.x >> 6) + wv;
+  const bool live = slot < a.sl.C;  // (wave-uniform; the barriers below are reached by every wave)
+  char* region = (char*)yo_dyn + (size_t)wv * region_bytes;
+  double* sums = (double*)region;
+  float* cnd = (float*)(region + WF_YAWOPT_ROWS_MAX * 8);
+  float* brow = (float*)(region + YO_HDR_BYTES);
+  const int N = a.N, RN = a.R * a.N;
+  float* pw = brow + N;
+  const bool has_prev = a.prev.s >= 0, has_next = a.next.s >= 0;
+  const bool writes = live && slot < a.sl.n_slots;
+  const size_t row0 = (size_t)slot * N, blk0 = (size_t)slot * RN;
+
+  // ---- the slot's best yaw and the previous visit's power block -> LDS (coalesced) ----
+  if (live) {
+    if (!has_prev) {
+      const size_t src = (size_t)(slot < a.sl.n_slots ? slot : 0) * N;
+      for (int t = lane; t < N; t += 64) {
+        const float v = a.yaw0 ? a.yaw0[src + t] : 0.0f;
+        brow[t] = v;
+        a.best[row0 + t] = v;
+      }
+    } else {
+      for (int t = lane; t < N; t += 64) brow[t] = a.best[row0 + t];
+      const int n_load = (a.prev.K + 1) * N;
+      for (int i = lane; i < n_load; i += 64) pw[i] = a.power[blk0 + i];
+    }
+  }
+  __syncthreads();
+  // ---- farm power of each candidate: lane k sums row k, caller's turbine order, float64 ----
+  if (live && has_prev && lane <= a.prev.K) {
+    const float* row = pw + lane * N;
+    double s = 0.0;
+    for (int t = 0; t < N; ++t) s += (double)row[t];
+    sums[lane] = s;
+  }
+  __syncthreads();
+  // ---- the winner (every lane finds it: K + 1 LDS broadcasts) ----
+  int tp = 0;
+  float newval = 0.0f;
+  if (live && has_prev) {
+    tp = a.order[row0 + a.prev.s];
+    const double p_inc = sums[0];
+    double p_best = p_inc;
+    int w = 0;
+    for (int k = 1; k <= a.prev.K; ++k) {
+      const double pk = sums[k];
+      if (pk > p_best) { p_best = pk; w = k; }  // strictly greater: the incumbent, then the lowest index, keep a tie
+    }
+    const float inc = brow[tp];
+    newval = w ? yo_candidate(a.prev, (double)inc, w - 1, a.lo, a.hi) : inc;
+    if (lane == 0) {
+      if (w) a.best[row0 + tp] = newval;
+      if (writes && a.first) a.out_init[slot] = (float)p_inc;
+      if (writes && !has_next) a.out_power[slot] = (float)p_best;
+    }
+  }
+  __syncthreads();  // (every lane has read brow[tp])
+  if (live && has_prev && lane == 0) brow[tp] = newval;
+  __syncthreads();
+  // ---- the next visit's candidates, then its yaw block: the best yaw, one entry replaced per candidate row ----
+  int tn = 0;
+  if (live && has_next) {
+    tn = a.order[row0 + a.next.s];
+    if (lane < a.next.K) cnd[lane] = yo_candidate(a.next, (double)brow[tn], lane, a.lo, a.hi);
+  }
+  __syncthreads();
+  if (live && has_next) {
+    for (int i = lane; i < RN; i += 64) {
+      const int k = i / N, t = i - k * N;
+      float v = brow[t];
+      if (t == tn && k >= 1 && k <= a.next.K) v = cnd[k - 1];
+      a.yaw[blk0 + i] = v;
+    }
+  } else if (writes) {
+    for (int t = lane; t < N; t += 64) a.out_yaw[row0 + t] = brow[t];
+  }
+}
+
+extern "C" hipError_t wfk_launch_yawopt_order(const WfYawoptOrderArgs* a, hipStream_t s) {
+  hipLaunchKernelGGL(wf_yawopt_order_kernel, dim3(a->sl.C), dim3(((a->N + 63) / 64) * 64), 0, s, *a);
+  return hipGetLastError();
+}
+extern "C" hipError_t wfk_launch_yawopt_wind(const WfYawoptWindArgs* a, hipStream_t s) {
+  const int n = a->sl.C * a->R;
+  hipLaunchKernelGGL(wf_yawopt_wind_kernel, dim3((n + 255) / 256), dim3(256), 0, s, *a);
+  return hipGetLastError();
+}
+extern "C" hipError_t wfk_launch_yawopt_advance(const WfYawoptAdvanceArgs* a, hipStream_t s) {
+  const int region = (YO_HDR_BYTES + 4 * a->N * (a->R + 1) + 15) & ~15;
+  int wpb = 49152 / region;  // waves (= slots) per block: what fits in 48 KiB of LDS, at most 4
+  wpb = wpb < 1 ? 1 : (wpb > 4 ? 4 : wpb);
+  hipLaunchKernelGGL(wf_yawopt_advance_kernel, dim3((a->sl.C + wpb - 1) / wpb), dim3(64 * wpb), (size_t)region * wpb, s, *a, region);
+  return hipGetLastError();
+}

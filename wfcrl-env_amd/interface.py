@@ -280,6 +280,17 @@ class HipFlorisInterface(BaseInterface):
         uvw = self.fi.sample_flow(self._current_yaw_command.reshape(1, -1).astype(np.float32))
         return uvw[0, :, 0].astype(np.float64)
 
+    def optimize_yaw(self, bounds=(-25.0, 25.0), passes=(5, 4), strict=False, yaw0=None):
+        """The best static yaw for the current wind: (yaw[N] degrees, farm power [W]).  The project's own coordinate
+        search (backend.WfStep.optimize_yaw, include/wfyawopt.h) — in the spirit of FLORIS' serial refine, not pinned to
+        FLORIS' optimiser.  The yaw command of the interface is not changed."""
+        if self._wind_dirty:
+            self.fi.set_wind(self._ws, self._wd)
+            self._wind_dirty = False
+        y0 = None if yaw0 is None else np.asarray(yaw0, dtype=np.float32).reshape(1, -1)
+        r = self.fi.optimize_yaw(y0, bounds=bounds, passes=passes, strict=strict)
+        return r["yaw"][0].astype(np.float64), float(r["power"][0])
+
     # -- accessors (interface.py:615-655) -----------------------------------------------------------
     def get_yaw_command(self):
         return self._current_yaw_command.copy().flatten()

@@ -320,6 +320,24 @@ class VecWindFarmEnv:
             out = torch.empty((n, int(P), 3), dtype=torch.float32, device=f"cuda:{self.fi.device_id}")
         return self.fi.sample_flow(None, farms=farms, out=out)
 
+    def optimal_yaw(self, passes=(5, 4), strict=False, farms=None):
+        """The best static yaw for the farms' CURRENT wind — the baseline a wake-steering agent is held to: dict(yaw
+        (n_farms, N), power (n_farms,) W, power_initial (n_farms,) W at zero yaw), torch CUDA tensors when the env returns
+        torch.  Bounds are the env's yaw limits, the start is zero yaw.  The project's own coordinate search
+        (backend.WfStep.optimize_yaw, include/wfyawopt.h; not pinned to FLORIS' optimiser), run on a handle of its own:
+        the env's yaw state, accumulators, wind and buffers are read, never changed."""
+        lo, hi = self.controls["yaw"][0], self.controls["yaw"][1]
+        out = None
+        if self.return_torch:
+            import torch
+
+            n = self.num_envs if farms is None else int(np.size(farms))
+            dev = f"cuda:{self.fi.device_id}"
+            out = {"yaw": torch.empty((n, self.num_turbines), dtype=torch.float32, device=dev),
+                   "power": torch.empty(n, dtype=torch.float32, device=dev),
+                   "power_initial": torch.empty(n, dtype=torch.float32, device=dev)}
+        return self.fi.optimize_yaw(None, farms=farms, bounds=(lo, hi), passes=passes, strict=strict, out=out)
+
     # -- checkpoint / resume (SURVEY §5: the env state is tiny; FLORIS itself is stateless between steps) ------
     def get_state(self) -> dict:
         """Everything needed to resume the batch: device env state, the per-farm wind, the step counter."""
