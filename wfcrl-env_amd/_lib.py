@@ -151,6 +151,20 @@ YAWOPT_ABI = {
     "wf_yawopt_last_error": (C.c_char_p, [_P]),
 }
 
+# every symbol include/wfrose.h declares (expected power over a wind rose, yaw look-up-table controller): a table of its own
+ROSE_ABI = {
+    "wf_rose_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "wf_rose_destroy": (C.c_int, [_P]),
+    "wf_rose_set_table": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int]),
+    "wf_rose_set_rose": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_double, C.c_double]),
+    "wf_rose_config": (C.c_int, [_P, C.c_int, C.c_int]),
+    "wf_rose_evaluate": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int]),
+    "wf_rose_policy": (C.c_int, [_P, C.c_int, _P, _P, C.c_int]),
+    "wf_rose_last_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "wf_rose_kernel_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "wf_rose_last_error": (C.c_char_p, [_P]),
+}
+
 _lib = None
 
 
@@ -159,7 +173,8 @@ def build(force: bool = False) -> Path:
     srcs = sorted((PKG_DIR / "csrc").glob("*.hip")) + sorted((PKG_DIR / "csrc").glob("*.h"))
     srcs += sorted((PKG_DIR / "csrc" / "probe").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "probe").glob("*.h"))
     srcs += sorted((PKG_DIR / "csrc" / "yawopt").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "yawopt").glob("*.h"))
-    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfprobe.h", "wfyawopt.h")]
+    srcs += sorted((PKG_DIR / "csrc" / "rose").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "rose").glob("*.h"))
+    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfprobe.h", "wfyawopt.h", "wfrose.h")]
     stale = (not LIB_PATH.exists()) or any(s.stat().st_mtime > LIB_PATH.stat().st_mtime for s in srcs)
     if force or stale:
         subprocess.run(["make", "-j4", "-C", str(PKG_DIR / "csrc")] + (["-B"] if force else []), check=True)
@@ -190,7 +205,7 @@ def load() -> C.CDLL:
             build()
         _share_hip_runtime_with_torch()
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in list(ABI.items()) + list(PROBE_ABI.items()) + list(YAWOPT_ABI.items()):
+        for name, (res, args) in list(ABI.items()) + list(PROBE_ABI.items()) + list(YAWOPT_ABI.items()) + list(ROSE_ABI.items()):
             fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -215,6 +230,16 @@ def check_yawopt(rc: int, opt):
     """`check` for the yaw-optimiser extension: the text comes from wf_yawopt_last_error."""
     if rc != WF_OK:
         msg = load().wf_yawopt_last_error(opt)
+        text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
+        if rc in (-1, -2):
+            raise ValueError(text)
+        raise WfError(text)
+
+
+def check_rose(rc: int, rose):
+    """`check` for the rose extension: the text comes from wf_rose_last_error."""
+    if rc != WF_OK:
+        msg = load().wf_rose_last_error(rose)
         text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
         if rc in (-1, -2):
             raise ValueError(text)

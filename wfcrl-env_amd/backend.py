@@ -414,6 +414,78 @@ class WfStep:
         optimize_yaw {"total_ms", "step_ms", "glue_ms"} (the last two 0 without detail); synchronises."""
         return self._yawopt().timing(detail)
 
+    # -- wind-rose expected power and the yaw look-up table (include/wfrose.h) -------------------------
+    def _rose(self) -> "_Rose":
+        """The handle's rose object; created on first use, destroyed in close() before the handle."""
+        ro = getattr(self, "_rose_obj", None)
+        if ro is None:
+            ro = self._rose_obj = _Rose(self)
+        return ro
+
+    def set_yaw_table(self, table, wd_axis, ws_axis, interp="linear", slot=0):
+        """Store a yaw look-up table in `slot` (0..3): table (Dt, St, N) degrees — NumPy, or a torch CUDA float32 tensor
+        with float64 CUDA axes, copied as it is — over wd_axis (Dt,) degrees, strictly ascending inside [0, 360), circular,
+        and ws_axis (St,) m/s, strictly ascending, clamped at both ends.  interp "linear" (bilinear) or "nearest"; the
+        look-up is the project's own definition (include/wfrose.h).  `expected_power` cases ("table", slot) and the
+        look-up-table controller (`lut_policy`, VecWindFarmEnv.lut_action) read it."""
+        self._rose().set_table(table, wd_axis, ws_axis, interp, slot)
+
+    def expected_power(self, wd, ws, freq, cases=("zero",), cut_in=0.001, cut_out=None, strict=False, max_eval_farms=65536,
+                       out=None):
+        """Expected power over a wind rose: directions wd (D,), speeds ws (S,), frequencies freq (D, S) >= 0 (any scale).
+          cases   each "zero", an (N,) yaw array held under every condition, or ("table", slot) — a table of set_yaw_table
+                  looked up at every condition
+          cut_in / cut_out   a condition with ws < cut_in or ws > cut_out counts as zero power (None: no cut-out)
+          strict  every condition is solved in float64 (validation); otherwise the handle's own resolve mode
+          max_eval_farms  rows (direction x case x speed) the rose's evaluator handle may hold: longer roses run in chunks
+          out     dict of torch CUDA tensors weighted_power (C,) float64, weighted_turbine_power (C, N) float64,
+                  condition_power (C, D, S) float32 to write into: the call then only enqueues work on torch's current
+                  stream (include/wfrose.h lists when it has to wait) and the results are torch tensors
+        Returns dict(expected_power (C,) W = sum(freq P) / sum(freq), aep_gwh (C,) = sum(freq P) x 8760 h / 1e9,
+        turbine_expected_power (C, N), condition_power (C, D, S) float32, freq_sum).  The project's own interpolation and
+        reduction (deterministic: fixed summation order, no atomics), not FLORIS' AEP routine; PARITY UNPINNED beyond the
+        oracle.  The handle itself — wind, env state, calibration — is not touched."""
+        return self._rose().evaluate(wd, ws, freq, cases, cut_in, cut_out, strict, max_eval_farms, out)
+
+    def build_yaw_table(self, wd_axis, ws_axis, bounds=(-25.0, 25.0), passes=(5, 4), strict=False):
+        """Fill a yaw table with `optimize_yaw`: a private helper handle with this handle's layout and model and one farm
+        per (direction, speed) node, a wind per farm, optimised in one call.  Returns dict(table (Dt, St, N) float32 —
+        what set_yaw_table takes —, power (Dt, St) and power_initial (Dt, St): the optimiser's farm power at the optimum
+        and at zero yaw)."""
+        wd_axis = np.ascontiguousarray(np.atleast_1d(wd_axis), dtype=np.float64)
+        ws_axis = np.ascontiguousarray(np.atleast_1d(ws_axis), dtype=np.float64)
+        if wd_axis.ndim != 1 or ws_axis.ndim != 1 or wd_axis.size < 1 or ws_axis.size < 1:
+            raise ValueError("wd_axis and ws_axis must be 1-D with at least one node each")
+        if self.turbine_types():
+            raise ValueError("WF_E_UNSUPPORTED: a yaw table is built for one turbine definition (and the layout of set_layout)")
+        Dt, St = wd_axis.size, ws_axis.size
+        x, y = self._layout_xy
+        helper = WfStep(x, y, env_batch=Dt * St, device_id=self.device_id, model=getattr(self, "_model", None))
+        try:
+            helper.set_risk_resolve(self.risk_resolve())
+            helper.set_wind(np.tile(ws_axis, Dt), np.repeat(wd_axis, St))
+            r = helper.optimize_yaw(None, bounds=bounds, passes=passes, strict=strict)
+        finally:
+            helper.close()
+        return {"table": r["yaw"].reshape(Dt, St, self.num_turbines), "power": r["power"].reshape(Dt, St),
+                "power_initial": r["power_initial"].reshape(Dt, St)}
+
+    def lut_policy(self, slot=0, want=("target_yaw", "action"), as_torch=False) -> dict:
+        """The look-up-table controller for every farm: the table of `slot` at the farm's CURRENT wind (read on the device),
+        clipped to the env's yaw bounds -> target_yaw (B, N); and the `action` (B, N) env_step takes to track it from the
+        env's current yaw state under env_config (continuous: the difference clipped to +-yaw_step; discrete: 0 / 1 / 2).
+        Reads the env state, never writes it (include/wfrose.h: wf_rose_policy)."""
+        return self._rose().policy(slot, want, as_torch)
+
+    def rose_timing(self) -> dict:
+        """HIP-event milliseconds of the last expected_power {"total_ms", "step_ms", "glue_ms"}: the evaluator's wind + step
+        calls, and the lay-out and reducing kernels; synchronises."""
+        return self._rose().timing()
+
+    def rose_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the rose kernels as the runtime reports them."""
+        return self._rose().kernel_info()
+
     # -- fused env step (SURVEY f1) ---------------------------------------------------------------
     def env_config(self, yaw_lo=-40.0, yaw_hi=40.0, yaw_step=5.0, actuator_rate=0.3, dt=60.0, budget=0.1,
                    load_coef=0.1, discrete=False, power_mw=False):
@@ -636,6 +708,10 @@ class WfStep:
             if yo is not None:
                 yo.close()
                 self._yawopt_obj = None
+            ro = getattr(self, "_rose_obj", None)  # ... and the rose object (include/wfrose.h)
+            if ro is not None:
+                ro.close()
+                self._rose_obj = None
             self._lib.wf_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -793,3 +869,124 @@ class _YawOpt:
         if self._o is not None:
             self._lib.wf_yawopt_destroy(self._o)
             self._o = None
+
+
+class _Rose:
+    """The `wf_rose` object of a WfStep handle (include/wfrose.h)."""
+
+    INTERP = {"linear": 0, "nearest": 1}
+
+    def __init__(self, owner: WfStep):
+        self._w, self._lib = owner, owner._lib
+        self._r = C.c_void_p()
+        check(self._lib.wf_rose_create(owner._h, C.byref(self._r)), owner._h)
+
+    def set_table(self, table, wd_axis, ws_axis, interp, slot):
+        if interp not in self.INTERP:
+            raise ValueError("interp must be 'linear' or 'nearest'")
+        N = self._w.num_turbines
+        if _is_torch(table):
+            tb, twd, tws = table.contiguous(), wd_axis.contiguous().reshape(-1), ws_axis.contiguous().reshape(-1)
+            assert tb.is_cuda and str(tb.dtype) == "torch.float32" and twd.is_cuda and tws.is_cuda
+            assert str(twd.dtype) == "torch.float64" and str(tws.dtype) == "torch.float64"
+            Dt, St = int(twd.numel()), int(tws.numel())
+            ptrs, on_device = (twd.data_ptr(), tws.data_ptr(), tb.data_ptr()), 1
+            self._w._follow_torch_stream()
+        else:
+            tb = np.ascontiguousarray(table, dtype=np.float32)
+            twd = np.ascontiguousarray(np.atleast_1d(wd_axis), dtype=np.float64).reshape(-1)
+            tws = np.ascontiguousarray(np.atleast_1d(ws_axis), dtype=np.float64).reshape(-1)
+            Dt, St = int(twd.size), int(tws.size)
+            ptrs, on_device = (twd.ctypes.data, tws.ctypes.data, tb.ctypes.data), 0
+        if tuple(tb.shape) != (Dt, St, N):
+            raise ValueError("a yaw table must be (len(wd_axis), len(ws_axis), num_turbines)")
+        _lib.check_rose(self._lib.wf_rose_set_table(self._r, int(slot), Dt, ptrs[0], St, ptrs[1], ptrs[2], self.INTERP[interp],
+                                                    on_device), self._r)
+
+    def _cases(self, cases):
+        N = self._w.num_turbines
+        kind, arg, fixed = [], [], []
+        for c in cases:
+            if isinstance(c, str):
+                if c != "zero":
+                    raise ValueError('a case is "zero", an (N,) yaw array or ("table", slot)')
+                kind.append(0); arg.append(0)
+            elif isinstance(c, tuple) and len(c) == 2 and c[0] == "table":
+                kind.append(2); arg.append(int(c[1]))
+            else:
+                row = np.asarray(c.detach().cpu() if _is_torch(c) else c, dtype=np.float32).reshape(-1)
+                if row.shape != (N,):
+                    raise ValueError('a case is "zero", an (N,) yaw array or ("table", slot)')
+                kind.append(1); arg.append(len(fixed)); fixed.append(row)
+        if not kind:
+            raise ValueError("expected_power needs at least one case")
+        fx = np.ascontiguousarray(np.stack(fixed)) if fixed else None
+        return np.asarray(kind, np.int32), np.asarray(arg, np.int32), fx
+
+    def evaluate(self, wd, ws, freq, cases, cut_in, cut_out, strict, max_eval_farms, out):
+        w = self._w
+        N = w.num_turbines
+        wd = np.ascontiguousarray(np.atleast_1d(wd), dtype=np.float64)
+        ws = np.ascontiguousarray(np.atleast_1d(ws), dtype=np.float64)
+        freq = np.ascontiguousarray(freq, dtype=np.float64)
+        if wd.ndim != 1 or ws.ndim != 1 or freq.shape != (wd.size, ws.size):
+            raise ValueError("freq must be (len(wd), len(ws))")
+        D, S = wd.size, ws.size
+        kind, arg, fixed = self._cases(cases)
+        Cn = kind.size
+        _lib.check_rose(self._lib.wf_rose_set_rose(self._r, D, wd.ctypes.data, S, ws.ctypes.data, freq.ctypes.data, float(cut_in),
+                                                   0.0 if cut_out is None else float(cut_out)), self._r)
+        _lib.check_rose(self._lib.wf_rose_config(self._r, int(bool(strict)), int(max_eval_farms)), self._r)
+        shapes = {"weighted_power": (Cn,), "weighted_turbine_power": (Cn, N), "condition_power": (Cn, D, S)}
+        fsum = float(np.sum(freq))
+        if out is not None:
+            import torch
+
+            w._follow_torch_stream()
+            for k, sh in shapes.items():
+                want = torch.float32 if k == "condition_power" else torch.float64
+                assert out[k].is_cuda and out[k].dtype == want and out[k].is_contiguous() and tuple(out[k].shape) == sh, k
+            fx = None if fixed is None else torch.as_tensor(fixed, device=out["condition_power"].device)
+            _lib.check_rose(self._lib.wf_rose_evaluate(self._r, Cn, kind.ctypes.data, arg.ctypes.data, None if fx is None else fx.data_ptr(),
+                                                       *[out[k].data_ptr() for k in shapes], 1), self._r)
+        else:
+            out = {k: np.empty(sh, np.float32 if k == "condition_power" else np.float64) for k, sh in shapes.items()}
+            _lib.check_rose(self._lib.wf_rose_evaluate(self._r, Cn, kind.ctypes.data, arg.ctypes.data, None if fixed is None else fixed.ctypes.data,
+                                                       *[out[k].ctypes.data for k in shapes], 0), self._r)
+        wp, wtp = out["weighted_power"], out["weighted_turbine_power"]
+        return {"expected_power": wp / fsum, "aep_gwh": wp * (8760.0 / 1.0e9), "turbine_expected_power": wtp / fsum,
+                "condition_power": out["condition_power"], "freq_sum": fsum, "weighted_power": wp, "weighted_turbine_power": wtp}
+
+    def policy(self, slot, want, as_torch):
+        w = self._w
+        B, N = w.env_batch, w.num_turbines
+        keys = [k for k in ("target_yaw", "action") if k in want]
+        if not keys:
+            raise ValueError("want must name target_yaw and / or action")
+        if as_torch:
+            import torch
+
+            w._follow_torch_stream()
+            out = {k: torch.empty((B, N), dtype=torch.float32, device=f"cuda:{w.device_id}") for k in keys}
+            ptr = {k: v.data_ptr() for k, v in out.items()}
+        else:
+            out = {k: np.empty((B, N), np.float32) for k in keys}
+            ptr = {k: v.ctypes.data for k, v in out.items()}
+        _lib.check_rose(self._lib.wf_rose_policy(self._r, int(slot), ptr.get("target_yaw"), ptr.get("action"), int(bool(as_torch))), self._r)
+        return out
+
+    def timing(self) -> dict:
+        t = [C.c_float(), C.c_float(), C.c_float()]
+        _lib.check_rose(self._lib.wf_rose_last_timing(self._r, *[C.byref(v) for v in t]), self._r)
+        return {"total_ms": float(t[0].value), "step_ms": float(t[1].value), "glue_ms": float(t[2].value)}
+
+    def kernel_info(self) -> dict:
+        v = (C.c_int * 12)()
+        _lib.check_rose(self._lib.wf_rose_kernel_info(self._r, v), self._r)
+        keys = ("vgprs", "lds_bytes", "scratch_bytes")
+        return {n: dict(zip(keys, v[3 * i:3 * i + 3])) for i, n in enumerate(("layout", "rowsum", "accumulate", "policy"))}
+
+    def close(self):
+        if self._r is not None:
+            self._lib.wf_rose_destroy(self._r)
+            self._r = None

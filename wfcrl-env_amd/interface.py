@@ -291,6 +291,34 @@ class HipFlorisInterface(BaseInterface):
         r = self.fi.optimize_yaw(y0, bounds=bounds, passes=passes, strict=strict)
         return r["yaw"][0].astype(np.float64), float(r["power"][0])
 
+    def get_farm_AEP(self, wind_directions, wind_speeds, freq, cut_in_wind_speed=0.001, cut_out_wind_speed=None,
+                     yaw_angles=None, no_wake=False, turbine_weights=None):
+        """Annual energy production [GWh] over a wind rose, with the argument names FLORIS users know:
+        sum(freq x farm power) x 8760 h / 1e9, freq (n_wd, n_ws) as given (not normalised here).  yaw_angles
+        (n_wd, n_ws, N): a yaw per condition — a table on the rose's own grid, read at its nodes ("nearest"); None: zero yaw.
+        The project's own reduction (backend.WfStep.expected_power, include/wfrose.h), not FLORIS' AEP routine; PARITY
+        UNPINNED beyond the oracle.  The wind and yaw command of the interface are not changed."""
+        if no_wake:
+            raise NotImplementedError("get_farm_AEP: no_wake=True is not supported (the step always solves the wakes)")
+        if turbine_weights is not None:
+            raise NotImplementedError("get_farm_AEP: turbine_weights is not supported (expected_power returns "
+                                      "turbine_expected_power: weight it yourself)")
+        wd = np.atleast_1d(np.asarray(wind_directions, dtype=np.float64))
+        ws = np.atleast_1d(np.asarray(wind_speeds, dtype=np.float64))
+        cases = ("zero",)
+        if yaw_angles is not None:
+            ya = np.asarray(yaw_angles, dtype=np.float32)
+            if ya.shape != (wd.size, ws.size, self.fi.num_turbines):
+                raise ValueError("yaw_angles must be (n_wind_directions, n_wind_speeds, num_turbines)")
+            # the table's axes: directions reduced to [0, 360) and both axes ascending, as set_yaw_table wants them
+            wdm = np.fmod(wd, 360.0)
+            wdm = np.where(wdm < 0.0, wdm + 360.0, wdm)
+            od, osp = np.argsort(wdm, kind="stable"), np.argsort(ws, kind="stable")
+            self.fi.set_yaw_table(ya[od][:, osp], wdm[od], ws[osp], interp="nearest", slot=3)
+            cases = (("table", 3),)
+        r = self.fi.expected_power(wd, ws, freq, cases=cases, cut_in=cut_in_wind_speed, cut_out=cut_out_wind_speed)
+        return float(r["aep_gwh"][0])
+
     # -- accessors (interface.py:615-655) -----------------------------------------------------------
     def get_yaw_command(self):
         return self._current_yaw_command.copy().flatten()

@@ -338,6 +338,19 @@ class VecWindFarmEnv:
                    "power_initial": torch.empty(n, dtype=torch.float32, device=dev)}
         return self.fi.optimize_yaw(None, farms=farms, bounds=(lo, hi), passes=passes, strict=strict, out=out)
 
+    def lut_target_yaw(self, table_slot: int = 0):
+        """The yaw (num_envs, N) the look-up table in `table_slot` (backend.WfStep.set_yaw_table on `self.fi`) holds for
+        every farm's CURRENT wind, clipped to the env's yaw bounds — a torch CUDA tensor when the env returns torch.  The
+        wind is read on the device; the env state is not changed.  The project's own interpolation (include/wfrose.h)."""
+        return self.fi.lut_policy(table_slot, want=("target_yaw",), as_torch=self.return_torch)["target_yaw"]
+
+    def lut_action(self, table_slot: int = 0) -> dict:
+        """The industry-baseline controller as a policy: {"yaw": action} ready for `step` — the action that moves every
+        turbine from the env's current yaw towards `lut_target_yaw` under the env's control (continuous: the difference
+        clipped to +-step; discrete: 0 / 1 / 2 = down / hold / up, hold inside half a step).  Reads the env state, never
+        changes it; a torch CUDA tensor when the env returns torch, computed without a host round trip."""
+        return {"yaw": self.fi.lut_policy(table_slot, want=("action",), as_torch=self.return_torch)["action"]}
+
     # -- checkpoint / resume (SURVEY §5: the env state is tiny; FLORIS itself is stateless between steps) ------
     def get_state(self) -> dict:
         """Everything needed to resume the batch: device env state, the per-farm wind, the step counter."""
