@@ -1,0 +1,137 @@
+"""The robust yaw search on the device (csrc/robust/, include/wfrobust.h): what a run costs next to the nominal search on
+the same farms, and how far the default mode's result lies from the strict (float64) one.  Writes profiles/robust_timing.json.
+
+Timing, default passes (5, 4), members (-6, -3, 0, 3, 6) deg with weights exp(-d^2 / 18), FIXED frame, one MI355X, HIP events
+on the handle's stream: HornsRev1 x 256 farms and Ablaincourt x 4096 farms, a wind per farm.  Per workload, after 2 warm-up
+runs (the first builds the evaluator and times its kernel families):
+    total_ms   median of `reps` runs of optimize_yaw(wd_uncertainty=...), two events per run (first to last launch)
+    step_ms / glue_ms   median of `reps` more runs with an event around every launch group (these runs are a little slower
+               themselves — `total_detail_ms`)
+    nominal_total_ms   optimize_yaw() without uncertainty on the same farms — the capability the search is built on; the
+               ratio of the two totals stands against M = 5 (M times the rows; the nominal evaluator may sit on another
+               kernel family)
+    plain_loop_ms   the same number of wf_step calls on the search's OWN evaluator handle, batch and wind with nothing between
+               them: the step-only time; runs of the three alternate
+    kernels    wf_robust_kernel_info: vgprs / static LDS bytes / private-segment bytes
+Default against strict: Ablaincourt x 32 (tests/yawopt_ref.gpu_case), both frames — the largest relative distance between the
+expected power the default mode reports and the strict run's; tests/test_robust_gpu.py asserts twice that, or 2e-4.
+Run from the repo root on an MI355X:  python tools/robust_timing.py [reps, default 10] [output file]"""
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import robust_ref  # noqa: E402
+import yawopt_ref  # noqa: E402
+from wfcrl_env_amd.backend import WfStep  # noqa: E402
+
+assert torch.cuda.is_available(), "this tool measures on the GPU: there is nothing to fall back to"
+LAYOUTS = json.load(open(os.path.join(ROOT, "wfcrl-env_amd", "environments", "layouts.json")))
+REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+OUT = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "robust_timing.json")
+PASSES = (5, 4)
+MEMBERS = dict(delta=robust_ref.MEMBERS5[0], weight=robust_ref.MEMBERS5[1], frame="fixed")
+M = len(MEMBERS["delta"])
+
+
+def plain_loop_ms(w, n_steps):
+    """n_steps wf_step calls on the search's evaluator (its batch, its wind), between two events on the shared stream."""
+    lib, ev = w._lib, C.c_void_p(w._robust().evaluator())
+    rows = (max(PASSES) + 1) * M
+    n_eval = min(w.env_batch, 65536 // rows) * rows
+    yaw = torch.zeros((n_eval, w.num_turbines), dtype=torch.float32, device="cuda")
+    power = torch.empty_like(yaw)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n_steps):
+        rc = lib.wf_step(ev, yaw.data_ptr(), power.data_ptr(), None, None, None, 1)
+        assert rc == 0, rc
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b), n_eval
+
+
+def workload(label, name, B):
+    lay = LAYOUTS[name]
+    x, y = np.asarray(lay["xcoords"], float), np.asarray(lay["ycoords"], float)
+    N = len(x)
+    rng = np.random.default_rng(7)
+    w = WfStep(x, y, env_batch=B)
+    w.set_wind(rng.uniform(6.0, 12.0, B), rng.uniform(0.0, 360.0, B))
+    out, nom = ({"yaw": torch.empty((B, N), dtype=torch.float32, device="cuda"), "power": torch.empty(B, dtype=torch.float32, device="cuda"),
+                 "power_initial": torch.empty(B, dtype=torch.float32, device="cuda")} for _ in range(2))
+    chunks = -(-B // (65536 // ((max(PASSES) + 1) * M)))  # (the evaluator holds 65 536 rows: longer farm lists run in chunks)
+    n_steps = len(PASSES) * N * chunks
+    for _ in range(2):
+        w.optimize_yaw(passes=PASSES, out=out, wd_uncertainty=MEMBERS)
+        w.robust_timing()
+        w.optimize_yaw(passes=PASSES, out=nom)
+        w.yawopt_timing()
+    plain_loop_ms(w, n_steps)
+    total, nominal, plain = [], [], []
+    for _ in range(REPS):  # alternating: the three share whatever else the machine is doing
+        w.optimize_yaw(passes=PASSES, out=out, wd_uncertainty=MEMBERS)
+        total.append(w.robust_timing()["total_ms"])
+        w.optimize_yaw(passes=PASSES, out=nom)
+        nominal.append(w.yawopt_timing()["total_ms"])
+        ms, n_eval = plain_loop_ms(w, n_steps)
+        plain.append(ms)
+    w.robust_timing(detail=True)
+    det = []
+    for _ in range(REPS):
+        w.optimize_yaw(passes=PASSES, out=out, wd_uncertainty=MEMBERS)
+        det.append(w.robust_timing())
+    w.robust_timing(detail=False)
+    e_rob = w.uncertain_power(out["yaw"], wd_uncertainty=MEMBERS)["expected_power"]
+    e_nom = w.uncertain_power(nom["yaw"], wd_uncertainty=MEMBERS)["expected_power"]
+    kernels = w.robust_kernel_info()
+    w.close()
+    t, q, p = float(np.median(total)), float(np.median(nominal)), float(np.median(plain))
+    step, glue = float(np.median([d["step_ms"] for d in det])), float(np.median([d["glue_ms"] for d in det]))
+    r = {"workload": label, "layout": name, "turbines": N, "farms": B, "wind": "per farm", "passes": list(PASSES), "members": M,
+         "visits": len(PASSES) * N, "chunks": chunks, "evaluator_steps": n_steps, "evaluator_farms": n_eval, "reps": REPS,
+         "total_ms": t, "total_ms_min": float(np.min(total)), "total_ms_max": float(np.max(total)),
+         "nominal_total_ms": q, "nominal_total_ms_min": float(np.min(nominal)), "ratio_robust_over_nominal": t / q,
+         "ratio_robust_over_nominal_per_member": t / q / M,
+         "plain_loop_ms": p, "plain_loop_ms_min": float(np.min(plain)), "ratio_total_over_plain_loop": t / p,
+         "total_detail_ms": float(np.median([d["total_ms"] for d in det])), "step_ms": step, "glue_ms": glue,
+         "glue_share_of_step": glue / step, "farms_per_s": B / (t * 1e-3), "farm_steps_per_s": n_eval * n_steps / (t * 1e-3),
+         "mean_expected_gain_of_robust_over_nominal_yaw": float((e_rob / e_nom).mean().item() - 1.0), "kernels": kernels}
+    print(json.dumps(r), flush=True)
+    return r
+
+
+def default_vs_strict():
+    rows, worst = [], 0.0
+    x, y, ws, wd = yawopt_ref.gpu_case(LAYOUTS, "Ablaincourt_")
+    for frame in ("fixed", "relative"):
+        spec = dict(MEMBERS, frame=frame)
+        w = WfStep(x, y, env_batch=len(ws))
+        w.set_wind(ws, wd)
+        s, d = w.optimize_yaw(strict=True, wd_uncertainty=spec), w.optimize_yaw(wd_uncertainty=spec)
+        w.close()
+        gap = np.abs(d["power"] / s["power"] - 1.0)
+        rows.append({"layout": "Ablaincourt_", "farms": len(ws), "seed": yawopt_ref.GPU_CASE_SEED, "frame": frame,
+                     "max_rel_gap": float(gap.max()), "farms_with_another_yaw": int((d["yaw"] != s["yaw"]).any(axis=1).sum())})
+        worst = max(worst, float(gap.max()))
+    return {"what": "largest relative distance between the expected power optimize_yaw(wd_uncertainty=...) reports in the default "
+                    "mode and in strict mode, same farms (tests/yawopt_ref.gpu_case), default passes, five members",
+            "max_rel_gap": worst, "cases": rows}
+
+
+if __name__ == "__main__":
+    gap = default_vs_strict()
+    print(json.dumps(gap), flush=True)
+    res = [workload("HornsRev1 x 256, a wind per farm", "HornsRev1_", 256),
+           workload("Ablaincourt x 4096, a wind per farm", "Ablaincourt_", 4096)]
+    os.makedirs(os.path.dirname(OUT), exist_ok=True)
+    with open(OUT, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(0), "method": "HIP events on the handle's stream; 2 warm-up runs, median of `reps`; "
+                   "robust search, nominal search and plain wf_step loop alternate", "default_vs_strict": gap, "workloads": res}, f, indent=1)
+        f.write("\n")

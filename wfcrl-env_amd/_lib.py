@@ -165,6 +165,21 @@ ROSE_ABI = {
     "wf_rose_last_error": (C.c_char_p, [_P]),
 }
 
+# every symbol include/wfrobust.h declares (expected power under wind-direction uncertainty, robust yaw search): its own table
+ROBUST_ABI = {
+    "wf_robust_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "wf_robust_destroy": (C.c_int, [_P]),
+    "wf_robust_set_members": (C.c_int, [_P, C.c_int, _P, _P, C.c_int]),
+    "wf_robust_config": (C.c_int, [_P, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int]),
+    "wf_robust_evaluate": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int]),
+    "wf_robust_optimize": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int]),
+    "wf_robust_set_timing": (C.c_int, [_P, C.c_int]),
+    "wf_robust_last_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "wf_robust_evaluator": (_P, [_P]),
+    "wf_robust_kernel_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "wf_robust_last_error": (C.c_char_p, [_P]),
+}
+
 _lib = None
 
 
@@ -174,7 +189,8 @@ def build(force: bool = False) -> Path:
     srcs += sorted((PKG_DIR / "csrc" / "probe").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "probe").glob("*.h"))
     srcs += sorted((PKG_DIR / "csrc" / "yawopt").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "yawopt").glob("*.h"))
     srcs += sorted((PKG_DIR / "csrc" / "rose").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "rose").glob("*.h"))
-    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfprobe.h", "wfyawopt.h", "wfrose.h")]
+    srcs += sorted((PKG_DIR / "csrc" / "robust").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "robust").glob("*.h"))
+    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfprobe.h", "wfyawopt.h", "wfrose.h", "wfrobust.h")]
     stale = (not LIB_PATH.exists()) or any(s.stat().st_mtime > LIB_PATH.stat().st_mtime for s in srcs)
     if force or stale:
         subprocess.run(["make", "-j4", "-C", str(PKG_DIR / "csrc")] + (["-B"] if force else []), check=True)
@@ -205,7 +221,7 @@ def load() -> C.CDLL:
             build()
         _share_hip_runtime_with_torch()
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in list(ABI.items()) + list(PROBE_ABI.items()) + list(YAWOPT_ABI.items()) + list(ROSE_ABI.items()):
+        for name, (res, args) in list(ABI.items()) + list(PROBE_ABI.items()) + list(YAWOPT_ABI.items()) + list(ROSE_ABI.items()) + list(ROBUST_ABI.items()):
             fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -240,6 +256,16 @@ def check_rose(rc: int, rose):
     """`check` for the rose extension: the text comes from wf_rose_last_error."""
     if rc != WF_OK:
         msg = load().wf_rose_last_error(rose)
+        text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
+        if rc in (-1, -2):
+            raise ValueError(text)
+        raise WfError(text)
+
+
+def check_robust(rc: int, rob):
+    """`check` for the robust extension: the text comes from wf_robust_last_error."""
+    if rc != WF_OK:
+        msg = load().wf_robust_last_error(rob)
         text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
         if rc in (-1, -2):
             raise ValueError(text)

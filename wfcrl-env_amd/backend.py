@@ -41,6 +41,40 @@ def turbine_table(name: str = "nrel_5MW_floris3") -> dict:
             "table_cp": [cp[i] for i in range(n.value)]}
 
 
+def wd_uncertainty_members(spec) -> tuple:
+    """(delta (M,) float64 degrees, weight (M,) float64 — not normalised —, frame "fixed" | "relative"): the member set of
+    a `wd_uncertainty` argument (include/wfrobust.h).  `spec` is one of two dicts:
+      dict(delta=..., weight=..., frame="fixed")  the offsets and weights as they are
+      dict(std=..., resolution=1.0, cutoff=0.995, frame="fixed")  a Gaussian table the way FLORIS users expect
+          (UncertaintyInterface: std_wd, pmf_res, pdf_cutoff): bound = ceil(inv_cdf(cutoff) std / resolution),
+          2 bound + 1 members at resolution x (-bound .. bound), weights exp(-delta^2 / (2 std^2))
+    The default frame is "fixed": the nacelle stays where the nominal direction put it."""
+    if not isinstance(spec, dict):
+        raise ValueError("wd_uncertainty must be a dict: (delta, weight[, frame]) or (std[, resolution, cutoff, frame])")
+    frame = spec.get("frame", "fixed")
+    if frame not in ("fixed", "relative"):
+        raise ValueError("wd_uncertainty: frame must be 'fixed' or 'relative'")
+    if "std" in spec:
+        if set(spec) - {"std", "resolution", "cutoff", "frame"}:
+            raise ValueError("wd_uncertainty: give either (delta, weight) or (std, resolution, cutoff)")
+        from statistics import NormalDist
+
+        std, res, cutoff = float(spec["std"]), float(spec.get("resolution", 1.0)), float(spec.get("cutoff", 0.995))
+        if not (std > 0.0 and res > 0.0 and 0.5 < cutoff < 1.0) or not np.isfinite(std + res):
+            raise ValueError("wd_uncertainty: std and resolution must be > 0 and cutoff inside (0.5, 1)")
+        bound = int(np.ceil(NormalDist().inv_cdf(cutoff) * std / res))
+        delta = res * np.arange(-bound, bound + 1, dtype=np.float64)
+        weight = np.exp(-(delta * delta) / (2.0 * std * std))
+    else:
+        if set(spec) - {"delta", "weight", "frame"} or "delta" not in spec or "weight" not in spec:
+            raise ValueError("wd_uncertainty: give either (delta, weight) or (std, resolution, cutoff)")
+        delta = np.ascontiguousarray(np.atleast_1d(spec["delta"]), dtype=np.float64)
+        weight = np.ascontiguousarray(np.atleast_1d(spec["weight"]), dtype=np.float64)
+        if delta.ndim != 1 or weight.shape != delta.shape:
+            raise ValueError("wd_uncertainty: delta and weight must be 1-D and of one length")
+    return delta, weight, frame
+
+
 class WfStep:
     def __init__(self, xcoords, ycoords, env_batch: int = 1, device_id: int = 0, model: dict | None = None,
                  kernel_choice: dict | None = None, layout_of=None):
@@ -393,7 +427,7 @@ class WfStep:
         return yo
 
     def optimize_yaw(self, yaw0=None, farms=None, bounds=(-25.0, 25.0), passes=(5, 4), strict=False, max_eval_farms=65536,
-                     out=None):
+                     out=None, wd_uncertainty=None):
         """The best static yaw for the handle's current wind, by the project's own coordinate search (include/wfyawopt.h;
         in the spirit of "serial refine", not pinned to FLORIS' optimiser): turbines are visited upstream to downstream,
         pass 0 tries `passes[0]` angles across `bounds` per turbine, each later pass `passes[p]` angles inside the bracket
@@ -405,7 +439,13 @@ class WfStep:
           out     dict of tensors / arrays to write into (a torch `out` selects the device path when yaw0 is None)
         Returns dict(yaw (n_farms, N) degrees, power (n_farms,) W, power_initial (n_farms,) W at yaw0), float32.  With torch
         tensors the call only enqueues work on torch's current stream (include/wfyawopt.h lists when it has to wait);
-        with NumPy it returns the results.  The handle itself — wind, env state, calibration — is not touched."""
+        with NumPy it returns the results.  The handle itself — wind, env state, calibration — is not touched.
+          wd_uncertainty  None: the wind direction is taken as exact.  A dict (`wd_uncertainty_members`): the ROBUST search
+                  of include/wfrobust.h — the same search with "farm power" replaced by the expected power over the
+                  direction offsets; power / power_initial are then expected powers, and max_eval_farms has to hold
+                  (max(passes) + 1) x members rows per farm."""
+        if wd_uncertainty is not None:
+            return self._robust().optimize(yaw0, farms, bounds, passes, strict, max_eval_farms, out, wd_uncertainty)
         return self._yawopt().run(yaw0, farms, bounds, passes, strict, max_eval_farms, out)
 
     def yawopt_timing(self, detail=None) -> dict:
@@ -413,6 +453,40 @@ class WfStep:
         that step and glue time can be told apart — returns None.  detail=None: HIP-event milliseconds of the last
         optimize_yaw {"total_ms", "step_ms", "glue_ms"} (the last two 0 without detail); synchronises."""
         return self._yawopt().timing(detail)
+
+    # -- wind-direction uncertainty: expected power and the robust yaw search (include/wfrobust.h) -----
+    def _robust(self) -> "_Robust":
+        """The handle's robust object; created on first use, destroyed in close() before the handle."""
+        ro = getattr(self, "_robust_obj", None)
+        if ro is None:
+            ro = self._robust_obj = _Robust(self)
+        return ro
+
+    def uncertain_power(self, yaw=None, farms=None, wd_uncertainty=None, strict=False, max_eval_farms=65536, out=None):
+        """Expected power under wind-direction uncertainty at a given yaw, for the handle's current wind: every farm is
+        stepped once per member at (ws, wd + delta[m]) and the powers are averaged with the normalised weights
+        (include/wfrobust.h; the project's own definition, PARITY UNPINNED beyond the oracle).
+          yaw     (n_farms, N) degrees (row i belongs to farms[i]) — torch CUDA float32 tensor or NumPy — or None: zeros
+          farms   farm indices (any order), or None: every farm of the batch
+          wd_uncertainty  the member set, a dict `wd_uncertainty_members` understands; frame "fixed" (default): the nacelle
+                  stays where the nominal direction put it, member m is stepped at yaw + delta[m]; "relative": at yaw
+          strict  every member is solved in float64 (validation); otherwise the handle's own resolve mode
+          max_eval_farms  rows (farm x member) the evaluator handle may hold: longer lists run in chunks
+          out     dict of torch CUDA tensors expected_power (n,) float64, turbine_expected_power (n, N) float64,
+                  member_power (n, M) float32 to write into (selects the device path when yaw is None)
+        Returns dict(expected_power (n,) W, turbine_expected_power (n, N), member_power (n, M) float32, delta (M,),
+        weight (M,) normalised).  Deterministic: fixed summation order, no atomics.  The handle is not touched."""
+        if wd_uncertainty is None:
+            raise ValueError("uncertain_power needs wd_uncertainty: dict(delta, weight[, frame]) or dict(std[, resolution, cutoff, frame])")
+        return self._robust().evaluate(yaw, farms, strict, max_eval_farms, out, wd_uncertainty)
+
+    def robust_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last robust optimize_yaw or uncertain_power {"total_ms", "step_ms", "glue_ms"}."""
+        return self._robust().timing(detail)
+
+    def robust_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the robust kernels as the runtime reports them."""
+        return self._robust().kernel_info()
 
     # -- wind-rose expected power and the yaw look-up table (include/wfrose.h) -------------------------
     def _rose(self) -> "_Rose":
@@ -447,11 +521,12 @@ class WfStep:
         oracle.  The handle itself — wind, env state, calibration — is not touched."""
         return self._rose().evaluate(wd, ws, freq, cases, cut_in, cut_out, strict, max_eval_farms, out)
 
-    def build_yaw_table(self, wd_axis, ws_axis, bounds=(-25.0, 25.0), passes=(5, 4), strict=False):
+    def build_yaw_table(self, wd_axis, ws_axis, bounds=(-25.0, 25.0), passes=(5, 4), strict=False, wd_uncertainty=None):
         """Fill a yaw table with `optimize_yaw`: a private helper handle with this handle's layout and model and one farm
         per (direction, speed) node, a wind per farm, optimised in one call.  Returns dict(table (Dt, St, N) float32 —
         what set_yaw_table takes —, power (Dt, St) and power_initial (Dt, St): the optimiser's farm power at the optimum
-        and at zero yaw)."""
+        and at zero yaw).  wd_uncertainty: as in optimize_yaw — every node is then optimised for the expected power
+        over the direction offsets, and the two powers are expected powers."""
         wd_axis = np.ascontiguousarray(np.atleast_1d(wd_axis), dtype=np.float64)
         ws_axis = np.ascontiguousarray(np.atleast_1d(ws_axis), dtype=np.float64)
         if wd_axis.ndim != 1 or ws_axis.ndim != 1 or wd_axis.size < 1 or ws_axis.size < 1:
@@ -464,7 +539,7 @@ class WfStep:
         try:
             helper.set_risk_resolve(self.risk_resolve())
             helper.set_wind(np.tile(ws_axis, Dt), np.repeat(wd_axis, St))
-            r = helper.optimize_yaw(None, bounds=bounds, passes=passes, strict=strict)
+            r = helper.optimize_yaw(None, bounds=bounds, passes=passes, strict=strict, wd_uncertainty=wd_uncertainty)
         finally:
             helper.close()
         return {"table": r["yaw"].reshape(Dt, St, self.num_turbines), "power": r["power"].reshape(Dt, St),
@@ -712,6 +787,10 @@ class WfStep:
             if ro is not None:
                 ro.close()
                 self._rose_obj = None
+            rb = getattr(self, "_robust_obj", None)  # ... and the robust object (include/wfrobust.h)
+            if rb is not None:
+                rb.close()
+                self._robust_obj = None
             self._lib.wf_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -989,4 +1068,130 @@ class _Rose:
     def close(self):
         if self._r is not None:
             self._lib.wf_rose_destroy(self._r)
+            self._r = None
+
+
+class _Robust:
+    """The `wf_robust` object of a WfStep handle (include/wfrobust.h)."""
+
+    FRAME = {"relative": 0, "fixed": 1}
+    KERNELS = ("order", "layout", "rowsum", "advance", "expect")
+
+    def __init__(self, owner: WfStep):
+        self._w, self._lib = owner, owner._lib
+        self._r = C.c_void_p()
+        check(self._lib.wf_robust_create(owner._h, C.byref(self._r)), owner._h)
+
+    def _set_members(self, spec):
+        delta, weight, frame = wd_uncertainty_members(spec)
+        _lib.check_robust(self._lib.wf_robust_set_members(self._r, int(delta.size), delta.ctypes.data, weight.ctypes.data,
+                                                          self.FRAME[frame]), self._r)
+        s = 0.0
+        for v in weight:  # (the library's normalisation: the sum in index order)
+            s = s + float(v)
+        return delta, weight / s
+
+    def _config(self, bounds, passes, strict, max_eval_farms):
+        K = (C.c_int * max(len(passes), 1))(*[int(k) for k in passes])
+        _lib.check_robust(self._lib.wf_robust_config(self._r, float(bounds[0]), float(bounds[1]), len(passes), K, int(bool(strict)),
+                                                     int(max_eval_farms)), self._r)
+
+    def _farms(self, farms):
+        fa = None if farms is None else np.ascontiguousarray(farms, dtype=np.int32).reshape(-1)
+        return fa, (self._w.env_batch if fa is None else int(fa.size)), (None if fa is None else fa.ctypes.data)
+
+    def _yaw_ptr(self, yaw, n, on_device):
+        N = self._w.num_turbines
+        if yaw is None:
+            return None, None
+        if on_device:
+            import torch
+
+            assert yaw.is_cuda and yaw.dtype == torch.float32 and tuple(yaw.shape) == (n, N)
+            yaw = yaw.contiguous()
+            return yaw, yaw.data_ptr()
+        yaw = np.ascontiguousarray(yaw, dtype=np.float32)
+        if yaw.shape != (n, N):
+            raise ValueError("yaw must be (n_farms, num_turbines): a row per listed farm")
+        return yaw, yaw.ctypes.data
+
+    def evaluate(self, yaw, farms, strict, max_eval_farms, out, spec):
+        w = self._w
+        N = w.num_turbines
+        delta, wn = self._set_members(spec)
+        self._config((-25.0, 25.0), (5, 4), strict, max_eval_farms)  # (bounds and passes play no part in an evaluation)
+        fa, n, fptr = self._farms(farms)
+        shapes = {"expected_power": (n,), "turbine_expected_power": (n, N), "member_power": (n, delta.size)}
+        on_device = _is_torch(yaw) or (out is not None and _is_torch(out["expected_power"]))
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            kinds = {k: (torch.float32 if k == "member_power" else torch.float64) for k in shapes}
+            yaw, yptr = self._yaw_ptr(yaw, n, True)
+            if out is None:
+                out = {k: torch.empty(s, device=yaw.device, dtype=kinds[k]) for k, s in shapes.items()}
+            for k, s in shapes.items():
+                assert out[k].is_cuda and out[k].dtype == kinds[k] and out[k].is_contiguous() and tuple(out[k].shape) == s, k
+            ptrs = [out[k].data_ptr() for k in shapes]
+        else:
+            yaw, yptr = self._yaw_ptr(yaw, n, False)
+            if out is None:
+                out = {k: np.empty(s, np.float32 if k == "member_power" else np.float64) for k, s in shapes.items()}
+            for k, s in shapes.items():
+                assert out[k].dtype == (np.float32 if k == "member_power" else np.float64) and out[k].flags.c_contiguous and out[k].shape == s, k
+            ptrs = [out[k].ctypes.data for k in shapes]
+        _lib.check_robust(self._lib.wf_robust_evaluate(self._r, yptr, n, fptr, ptrs[0], ptrs[1], ptrs[2], int(on_device)), self._r)
+        return {**{k: out[k] for k in shapes}, "delta": delta, "weight": wn}
+
+    def optimize(self, yaw0, farms, bounds, passes, strict, max_eval_farms, out, spec):
+        w = self._w
+        N = w.num_turbines
+        self._set_members(spec)
+        self._config(bounds, passes, strict, max_eval_farms)
+        fa, n, fptr = self._farms(farms)
+        shapes = {"yaw": (n, N), "power": (n,), "power_initial": (n,)}
+        on_device = _is_torch(yaw0) or (out is not None and _is_torch(out["yaw"]))
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            yaw0, yptr = self._yaw_ptr(yaw0, n, True)
+            if out is None:
+                out = {k: torch.empty(s, device=yaw0.device, dtype=torch.float32) for k, s in shapes.items()}
+            for k, s in shapes.items():
+                assert out[k].is_cuda and out[k].dtype == torch.float32 and out[k].is_contiguous() and tuple(out[k].shape) == s, k
+            ptrs = [out[k].data_ptr() for k in shapes]
+        else:
+            yaw0, yptr = self._yaw_ptr(yaw0, n, False)
+            if out is None:
+                out = {k: np.empty(s, np.float32) for k, s in shapes.items()}
+            for k, s in shapes.items():
+                assert out[k].dtype == np.float32 and out[k].flags.c_contiguous and out[k].shape == s, k
+            ptrs = [out[k].ctypes.data for k in shapes]
+        _lib.check_robust(self._lib.wf_robust_optimize(self._r, yptr, n, fptr, ptrs[0], ptrs[1], ptrs[2], int(on_device)), self._r)
+        return out
+
+    def timing(self, detail=None):
+        if detail is not None:
+            _lib.check_robust(self._lib.wf_robust_set_timing(self._r, int(bool(detail))), self._r)
+            return None
+        t = [C.c_float(), C.c_float(), C.c_float()]
+        _lib.check_robust(self._lib.wf_robust_last_timing(self._r, *[C.byref(v) for v in t]), self._r)
+        return {"total_ms": float(t[0].value), "step_ms": float(t[1].value), "glue_ms": float(t[2].value)}
+
+    def evaluator(self):
+        """The search's evaluator handle (None before the first robust optimize_yaw): tools/robust_timing.py times a plain
+        wf_step loop on it."""
+        return self._lib.wf_robust_evaluator(self._r)
+
+    def kernel_info(self) -> dict:
+        v = (C.c_int * (3 * len(self.KERNELS)))()
+        _lib.check_robust(self._lib.wf_robust_kernel_info(self._r, v), self._r)
+        keys = ("vgprs", "lds_bytes", "scratch_bytes")
+        return {n: dict(zip(keys, v[3 * i:3 * i + 3])) for i, n in enumerate(self.KERNELS)}
+
+    def close(self):
+        if self._r is not None:
+            self._lib.wf_robust_destroy(self._r)
             self._r = None

@@ -280,15 +280,18 @@ class HipFlorisInterface(BaseInterface):
         uvw = self.fi.sample_flow(self._current_yaw_command.reshape(1, -1).astype(np.float32))
         return uvw[0, :, 0].astype(np.float64)
 
-    def optimize_yaw(self, bounds=(-25.0, 25.0), passes=(5, 4), strict=False, yaw0=None):
+    def optimize_yaw(self, bounds=(-25.0, 25.0), passes=(5, 4), strict=False, yaw0=None, wd_uncertainty=None):
         """The best static yaw for the current wind: (yaw[N] degrees, farm power [W]).  The project's own coordinate
         search (backend.WfStep.optimize_yaw, include/wfyawopt.h) — in the spirit of FLORIS' serial refine, not pinned to
-        FLORIS' optimiser.  The yaw command of the interface is not changed."""
+        FLORIS' optimiser.  The yaw command of the interface is not changed.  wd_uncertainty (a dict, see
+        backend.wd_uncertainty_members): the yaw that maximises the expected power over direction offsets
+        (include/wfrobust.h; what FLORIS users reach through UncertaintyInterface — the project's own definition), and
+        that expected power."""
         if self._wind_dirty:
             self.fi.set_wind(self._ws, self._wd)
             self._wind_dirty = False
         y0 = None if yaw0 is None else np.asarray(yaw0, dtype=np.float32).reshape(1, -1)
-        r = self.fi.optimize_yaw(y0, bounds=bounds, passes=passes, strict=strict)
+        r = self.fi.optimize_yaw(y0, bounds=bounds, passes=passes, strict=strict, wd_uncertainty=wd_uncertainty)
         return r["yaw"][0].astype(np.float64), float(r["power"][0])
 
     def get_farm_AEP(self, wind_directions, wind_speeds, freq, cut_in_wind_speed=0.001, cut_out_wind_speed=None,

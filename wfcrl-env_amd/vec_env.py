@@ -320,12 +320,14 @@ class VecWindFarmEnv:
             out = torch.empty((n, int(P), 3), dtype=torch.float32, device=f"cuda:{self.fi.device_id}")
         return self.fi.sample_flow(None, farms=farms, out=out)
 
-    def optimal_yaw(self, passes=(5, 4), strict=False, farms=None):
+    def optimal_yaw(self, passes=(5, 4), strict=False, farms=None, wd_uncertainty=None):
         """The best static yaw for the farms' CURRENT wind — the baseline a wake-steering agent is held to: dict(yaw
         (n_farms, N), power (n_farms,) W, power_initial (n_farms,) W at zero yaw), torch CUDA tensors when the env returns
         torch.  Bounds are the env's yaw limits, the start is zero yaw.  The project's own coordinate search
         (backend.WfStep.optimize_yaw, include/wfyawopt.h; not pinned to FLORIS' optimiser), run on a handle of its own:
-        the env's yaw state, accumulators, wind and buffers are read, never changed."""
+        the env's yaw state, accumulators, wind and buffers are read, never changed.  wd_uncertainty (a dict, see
+        backend.wd_uncertainty_members): the robust baseline of include/wfrobust.h — the yaw that maximises the EXPECTED
+        power over the direction offsets; the two powers are then expected powers."""
         lo, hi = self.controls["yaw"][0], self.controls["yaw"][1]
         out = None
         if self.return_torch:
@@ -336,7 +338,8 @@ class VecWindFarmEnv:
             out = {"yaw": torch.empty((n, self.num_turbines), dtype=torch.float32, device=dev),
                    "power": torch.empty(n, dtype=torch.float32, device=dev),
                    "power_initial": torch.empty(n, dtype=torch.float32, device=dev)}
-        return self.fi.optimize_yaw(None, farms=farms, bounds=(lo, hi), passes=passes, strict=strict, out=out)
+        return self.fi.optimize_yaw(None, farms=farms, bounds=(lo, hi), passes=passes, strict=strict, out=out,
+                                    wd_uncertainty=wd_uncertainty)
 
     def lut_target_yaw(self, table_slot: int = 0):
         """The yaw (num_envs, N) the look-up table in `table_slot` (backend.WfStep.set_yaw_table on `self.fi`) holds for
