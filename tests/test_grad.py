@@ -1,0 +1,170 @@
+"""CPU: the gradient extension (include/wfgrad.h) — header, binding table, kernel metadata — and the properties of the
+reference the GPU tests use (tests/grad_ref.py: the difference quotients restated in NumPy over the float64 oracle)."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+D = 126.0
+ROW3 = (np.array([0.0, 5 * D, 10 * D]), np.zeros(3))  # three turbines in a row, 5 D apart
+KERNELS = ("wf_grad_layout_kernel", "wf_grad_reduce_kernel")
+YAW = np.float32([[5.0, -7.0, 3.0]])
+
+
+def _declared(header):
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted(set(re.findall(r"\b(wf_[a-z0-9_]+)\s*\(", text)))
+
+
+def _steps():
+    import yawopt_ref
+
+    return {"numpy": yawopt_ref.numpy_step, "c": yawopt_ref._c_step}
+
+
+def test_grad_header_is_bound_and_the_other_tables_are_untouched():
+    from wfcrl_env_amd import _lib
+
+    lib = _lib.load()
+    syms = _declared("wfgrad.h")
+    assert {"wf_grad_create", "wf_grad_destroy", "wf_grad_config", "wf_grad_run", "wf_grad_set_timing", "wf_grad_last_timing",
+            "wf_grad_evaluator", "wf_grad_kernel_info", "wf_grad_last_error"} <= set(syms)
+    assert all(s.startswith("wf_grad_") for s in syms), syms
+    for s in syms:
+        assert hasattr(lib, s), f"libwfstep.so does not export {s}"
+        assert s in _lib.GRAD_ABI, f"GRAD_ABI lacks {s}"
+        assert getattr(lib, s).argtypes == _lib.GRAD_ABI[s][1]  # bound by load()
+    assert set(_lib.GRAD_ABI) == set(syms)
+    assert lib.wf_version() == 7
+    others = {"wfstep.h": _lib.ABI, "wfprobe.h": _lib.PROBE_ABI, "wfyawopt.h": _lib.YAWOPT_ABI, "wfrose.h": _lib.ROSE_ABI,
+              "wfrobust.h": _lib.ROBUST_ABI}
+    for header, table in others.items():
+        assert set(table) == set(_declared(header)), header
+        assert not set(table) & set(_lib.GRAD_ABI), header
+    text = open(os.path.join(ROOT, "include", "wfgrad.h")).read()
+    assert "PARITY UNPINNED" in text and "DIFFERENCE QUOTIENT" in text and "ON-THE-FLY" in text
+
+
+def test_grad_kernels_have_no_private_segment(tmp_path):
+    """The two glue kernels, compiled with the Makefile's flags: no private segment, no spilled register, no out-of-line
+    call.  Metadata only."""
+    src = os.path.join(ROOT, "wfcrl-env_amd", "csrc")
+    mk = open(os.path.join(src, "Makefile")).read()
+    flags = re.search(r"^FLAGS \?= (.*)$", mk, flags=re.M).group(1).replace("$(ARCH)", "gfx950").split()
+    assert "GRADOBJ = grad/wf_grad_kernels.o grad/wf_grad_abi.o" in mk and "$(GRADOBJ): %.o: %.hip" in mk
+    assert re.search(r"^\$\(OUT\):.*\$\(GRADOBJ\)", mk, flags=re.M) and re.search(r"^\trm -f .*grad/\*\.o", mk, flags=re.M)
+    out = tmp_path / "wf_grad_kernels.s"
+    subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-S", "--cuda-device-only", "-o", str(out),
+                                                      os.path.join(src, "grad", "wf_grad_kernels.hip")], check=True, capture_output=True)
+    text = out.read_text()
+    meta = text[text.index("amdhsa.kernels:"):]
+    seen = {}
+    for block in meta.split("  - .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block).group(1)
+        seen[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
+                      for k in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "group_segment_fixed_size")}
+    assert len(seen) == len(KERNELS) and all(any(k in n for n in seen) for k in KERNELS), seen
+    for name, m in seen.items():
+        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (name, m)
+    assert "s_swappc_b64" not in text
+
+
+def test_perturbed_yaws_and_rows():
+    """Clipped in float64, rounded once; at y = hi the quotient is one-sided: d = float32(hi) - float32(hi - h); a yaw beyond
+    a bound by h or more has d <= 0."""
+    import grad_ref
+
+    yp, ym, d = grad_ref.perturbed(np.float32([0.0, 25.0, -25.0, 24.5, 0.1]), 1.0, (-25.0, 25.0))
+    assert yp.dtype == ym.dtype == np.float32 and d.dtype == np.float64
+    assert np.array_equal(yp, np.float32([1.0, 25.0, -24.0, 25.0, np.float32(np.float64(np.float32(0.1)) + 1.0)]))
+    assert np.array_equal(ym, np.float32([-1.0, 24.0, -25.0, 23.5, np.float32(np.float64(np.float32(0.1)) - 1.0)]))
+    assert np.array_equal(d[:4], [2.0, 1.0, 1.0, 1.5]) and d[4] == np.float64(yp[4]) - np.float64(ym[4])
+    hi, h = 20.3, 0.7  # neither is a float32 value
+    yp, ym, d = grad_ref.perturbed(np.float32([hi]), h, (-hi, hi))
+    y32 = np.float64(np.float32(hi))
+    assert yp[0] == np.float32(min(y32 + h, hi)) and d[0] == np.float64(np.float32(min(y32 + h, hi))) - np.float64(np.float32(y32 - h))
+    assert grad_ref.perturbed(np.float32([27.0]), 1.0, (-25.0, 25.0))[2][0] < 0.0
+    assert grad_ref.perturbed(np.float32([26.0]), 1.0, (-25.0, 25.0))[2][0] == 0.0
+    blk = grad_ref.rows(YAW, 1.0)
+    assert blk.shape == (1, 7, 3) and blk.dtype == np.float32
+    assert np.array_equal(blk[0, 0], YAW[0]) and np.array_equal(blk[0, 1], np.float32([6, -7, 3])) and np.array_equal(blk[0, 2], np.float32([4, -7, 3]))
+    assert np.array_equal(blk[0, 5], np.float32([5, -7, 4])) and np.array_equal(blk[0, 6], np.float32([5, -7, 2]))
+
+
+@pytest.mark.parametrize("step", ["numpy", "c"])
+def test_reference_jacobian_structure_on_a_row_of_three(step):
+    """8 m/s along the row.  At 270 deg turbine 0 is upstream: J[i][j] == 0.0 exactly for every j upstream of i (a turbine's
+    yaw does not reach upwind), so J is upper triangular and J[2][j] == 0 for j != 2; at 90 deg the pattern mirrors.  Every
+    diagonal entry and every downstream entry is non-zero at this yaw."""
+    import grad_ref
+
+    x, y = ROW3
+    fn = _steps()[step]
+    r = grad_ref.gradient(x, y, 8.0, 270.0, YAW, step=fn)
+    J = r["jacobian"][0]
+    assert J.shape == (3, 3) and (J[np.tril_indices(3, -1)] == 0.0).all() and (J[np.triu_indices(3)] != 0.0).all()
+    assert J[2, 0] == 0.0 and J[2, 1] == 0.0
+    assert J[0, 0] < 0.0 and J[0, 1] > 0.0  # steering costs the turbine itself and pays behind it
+    m = grad_ref.gradient(x, y, 8.0, 90.0, YAW, step=fn)["jacobian"][0]
+    assert (m[np.triu_indices(3, 1)] == 0.0).all() and (m[np.tril_indices(3)] != 0.0).all()
+    again = grad_ref.gradient(x, y, 8.0, 270.0, YAW, step=fn)
+    for k in ("d", "jacobian", "gradient", "power"):
+        assert np.array_equal(again[k], r[k]), k  # invariant under recomputation
+
+
+@pytest.mark.parametrize("step", ["numpy", "c"])
+def test_reference_gradient_is_the_central_difference_of_farm_power(step):
+    """c = 1: G[i] is the central difference of yawopt_ref.farm_power to 1e-12 relative (the same float64 powers, summed before
+    instead of after the subtraction); c = e_j: G is column j of J bit for bit (the other products are exact zeros)."""
+    import grad_ref
+    import yawopt_ref
+
+    x, y = ROW3
+    fn = _steps()[step]
+    ws, wd = np.array([8.0, 9.0]), np.array([270.0, 262.0])
+    yaw = np.float32([[5.0, -7.0, 3.0], [12.0, 0.0, -4.0]])
+    r = grad_ref.gradient(x, y, ws, wd, yaw, step=fn)
+    yp, ym, d = grad_ref.perturbed(yaw)
+    assert np.array_equal(d, r["d"]) and (d == 2.0).all()
+    for i in range(3):
+        a, b = yaw.copy(), yaw.copy()
+        a[:, i], b[:, i] = yp[:, i], ym[:, i]
+        cd = (yawopt_ref.farm_power(x, y, ws, wd, a, step=fn) - yawopt_ref.farm_power(x, y, ws, wd, b, step=fn)) / d[:, i]
+        assert np.abs(cd / r["gradient"][:, i] - 1.0).max() <= 1e-12, i
+    for j in range(3):
+        e = np.zeros((2, 3), np.float32)
+        e[:, j] = 1.0
+        g = grad_ref.gradient(x, y, ws, wd, yaw, cotangent=e, step=fn)["gradient"]
+        assert np.array_equal(g, r["jacobian"][:, :, j]), j
+    c = np.float32([[0.5, -2.0, 1.25], [3.0, 0.0, -1.0]])
+    g = grad_ref.gradient(x, y, ws, wd, yaw, cotangent=c, step=fn)["gradient"]
+    assert np.abs(g - np.einsum("bj,bij->bi", c.astype(np.float64), r["jacobian"])).max() <= 1e-12 * np.abs(r["jacobian"]).max() * 6
+
+
+@pytest.mark.parametrize("step", ["numpy", "c"])
+def test_reference_at_a_bound_and_on_a_lone_turbine(step):
+    """At y = hi the quotient is one-sided with d = float32(hi) - float32(hi - h) and equals the backward difference of the
+    oracle's powers; beyond the bound by h, d <= 0 and the sensitivities are exactly 0.  A lone turbine: G changes sign
+    with y (+-20 deg: turning further away from the wind loses power) and is 0 at y = 0 to rounding (P is even in y; the
+    bound is 1e-12 of P per degree, a few ulps of the two powers subtracted)."""
+    import grad_ref
+
+    x, y = ROW3
+    fn = _steps()[step]
+    p = __import__("yawopt_ref").ModelParams()
+    yaw = np.float32([[25.0, 25.0, 26.5]])
+    r = grad_ref.gradient(x, y, 8.0, 270.0, yaw, bounds=(-25.0, 25.0), step=fn)
+    assert np.array_equal(r["d"][0], [1.0, 1.0, -0.5])
+    assert (r["jacobian"][0, 2] == 0.0).all() and r["gradient"][0, 2] == 0.0
+    at = fn(x, y, np.full(2, 8.0), np.full(2, 270.0), np.float64([[25.0, 25.0, 26.5], [24.0, 25.0, 26.5]]), p)
+    assert np.array_equal(r["jacobian"][0, 0], (at[0] - at[1]) / 1.0)
+    assert np.array_equal(r["power"][0], at[0])
+    g = {v: grad_ref.gradient(x[:1], y[:1], 8.0, 270.0, np.float32([[v]]), step=fn) for v in (-20.0, 0.0, 20.0)}
+    assert g[-20.0]["gradient"][0, 0] > 0.0 > g[20.0]["gradient"][0, 0]
+    assert abs(g[-20.0]["gradient"][0, 0] / g[20.0]["gradient"][0, 0] + 1.0) <= 1e-12
+    assert abs(g[0.0]["gradient"][0, 0]) <= 1e-12 * g[0.0]["power"][0, 0]

@@ -180,6 +180,19 @@ ROBUST_ABI = {
     "wf_robust_last_error": (C.c_char_p, [_P]),
 }
 
+# every symbol include/wfgrad.h declares (yaw sensitivities: power Jacobian and vector-Jacobian product): its own table
+GRAD_ABI = {
+    "wf_grad_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "wf_grad_destroy": (C.c_int, [_P]),
+    "wf_grad_config": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int]),
+    "wf_grad_run": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int]),
+    "wf_grad_set_timing": (C.c_int, [_P, C.c_int]),
+    "wf_grad_last_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "wf_grad_evaluator": (_P, [_P]),
+    "wf_grad_kernel_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "wf_grad_last_error": (C.c_char_p, [_P]),
+}
+
 _lib = None
 
 
@@ -190,7 +203,8 @@ def build(force: bool = False) -> Path:
     srcs += sorted((PKG_DIR / "csrc" / "yawopt").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "yawopt").glob("*.h"))
     srcs += sorted((PKG_DIR / "csrc" / "rose").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "rose").glob("*.h"))
     srcs += sorted((PKG_DIR / "csrc" / "robust").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "robust").glob("*.h"))
-    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfprobe.h", "wfyawopt.h", "wfrose.h", "wfrobust.h")]
+    srcs += sorted((PKG_DIR / "csrc" / "grad").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "grad").glob("*.h"))
+    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfprobe.h", "wfyawopt.h", "wfrose.h", "wfrobust.h", "wfgrad.h")]
     stale = (not LIB_PATH.exists()) or any(s.stat().st_mtime > LIB_PATH.stat().st_mtime for s in srcs)
     if force or stale:
         subprocess.run(["make", "-j4", "-C", str(PKG_DIR / "csrc")] + (["-B"] if force else []), check=True)
@@ -221,7 +235,7 @@ def load() -> C.CDLL:
             build()
         _share_hip_runtime_with_torch()
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in list(ABI.items()) + list(PROBE_ABI.items()) + list(YAWOPT_ABI.items()) + list(ROSE_ABI.items()) + list(ROBUST_ABI.items()):
+        for name, (res, args) in list(ABI.items()) + list(PROBE_ABI.items()) + list(YAWOPT_ABI.items()) + list(ROSE_ABI.items()) + list(ROBUST_ABI.items()) + list(GRAD_ABI.items()):
             fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -266,6 +280,16 @@ def check_robust(rc: int, rob):
     """`check` for the robust extension: the text comes from wf_robust_last_error."""
     if rc != WF_OK:
         msg = load().wf_robust_last_error(rob)
+        text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
+        if rc in (-1, -2):
+            raise ValueError(text)
+        raise WfError(text)
+
+
+def check_grad(rc: int, grad):
+    """`check` for the gradient extension: the text comes from wf_grad_last_error."""
+    if rc != WF_OK:
+        msg = load().wf_grad_last_error(grad)
         text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
         if rc in (-1, -2):
             raise ValueError(text)

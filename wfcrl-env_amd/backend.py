@@ -488,6 +488,41 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the robust kernels as the runtime reports them."""
         return self._robust().kernel_info()
 
+    # -- yaw sensitivities: power Jacobian and vector-Jacobian product (include/wfgrad.h) --------------
+    def _grad(self) -> "_Grad":
+        """The handle's gradient object; created on first use, destroyed in close() before the handle."""
+        go = getattr(self, "_grad_obj", None)
+        if go is None:
+            go = self._grad_obj = _Grad(self)
+        return go
+
+    def yaw_gradient(self, yaw=None, cotangent=None, farms=None, step=1.0, bounds=(-45.0, 45.0), strict=False,
+                     max_eval_farms=65536, jacobian=False, out=None):
+        """How the power changes when a turbine turns, for the handle's current wind: the DIFFERENCE QUOTIENT of the step's
+        per-turbine power at a finite step (include/wfgrad.h; the project's own definition, PARITY UNPINNED beyond the
+        oracle) — not an analytic derivative of the kernels.  Turbine i is moved to y+ = float32(min(y + step, hi)) and
+        y- = float32(max(y - step, lo)); d = y+ - y- is the divisor (one-sided at a bound, 0 sensitivity where d <= 0).
+          yaw        (n_farms, N) degrees (row i belongs to farms[i]) — torch CUDA float32 tensor or NumPy — or None: zeros
+          cotangent  (n_farms, N) float32 weights c of the per-turbine powers, or None: ones (the farm power)
+          farms      farm indices (any order), or None: every farm of the batch
+          strict     every row is solved in float64 (validation); otherwise the handle's own resolve mode
+          max_eval_farms  rows the evaluator handle may hold, 2 N + 1 per farm: longer lists run in chunks
+          jacobian   also return J (n_farms, N, N) float64, J[i, j] = d P_j / d yaw_i [W/deg]
+          out        dict of tensors / arrays power (n, N) float32, gradient (n, N) float64[, jacobian (n, N, N) float64] to
+                     write into (a torch `out` selects the device path when yaw is None)
+        Returns dict(power — the forward value —, gradient G[i] = sum_j c_j J[i, j], summed over j in caller order in
+        float64[, jacobian]).  Deterministic: fixed summation order, no atomics.  With torch tensors the call only enqueues
+        work on torch's current stream; with NumPy it returns the results.  The handle is not touched."""
+        return self._grad().run(yaw, cotangent, farms, step, bounds, strict, max_eval_farms, jacobian, out)
+
+    def grad_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last yaw_gradient {"total_ms", "step_ms", "glue_ms"}."""
+        return self._grad().timing(detail)
+
+    def grad_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the gradient kernels as the runtime reports them."""
+        return self._grad().kernel_info()
+
     # -- wind-rose expected power and the yaw look-up table (include/wfrose.h) -------------------------
     def _rose(self) -> "_Rose":
         """The handle's rose object; created on first use, destroyed in close() before the handle."""
@@ -791,6 +826,10 @@ class WfStep:
             if rb is not None:
                 rb.close()
                 self._robust_obj = None
+            go = getattr(self, "_grad_obj", None)  # ... and the gradient object (include/wfgrad.h)
+            if go is not None:
+                go.close()
+                self._grad_obj = None
             self._lib.wf_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -1195,3 +1234,104 @@ class _Robust:
         if self._r is not None:
             self._lib.wf_robust_destroy(self._r)
             self._r = None
+
+
+class _Grad:
+    """The `wf_grad` object of a WfStep handle (include/wfgrad.h)."""
+
+    KERNELS = ("layout", "reduce")
+
+    def __init__(self, owner: WfStep):
+        self._w, self._lib = owner, owner._lib
+        self._g = C.c_void_p()
+        check(self._lib.wf_grad_create(owner._h, C.byref(self._g)), owner._h)
+
+    def _row_ptr(self, a, n, on_device, name):
+        """(the array kept alive, its pointer) of an (n, N) float32 input, or (None, None)."""
+        N = self._w.num_turbines
+        if a is None:
+            return None, None
+        if on_device:
+            import torch
+
+            assert a.is_cuda and a.dtype == torch.float32 and tuple(a.shape) == (n, N), name
+            a = a.contiguous()
+            return a, a.data_ptr()
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != (n, N):
+            raise ValueError(f"{name} must be (n_farms, num_turbines): a row per listed farm")
+        return a, a.ctypes.data
+
+    def run(self, yaw, cotangent, farms, step, bounds, strict, max_eval_farms, jacobian, out):
+        w = self._w
+        N = w.num_turbines
+        _lib.check_grad(self._lib.wf_grad_config(self._g, float(step), float(bounds[0]), float(bounds[1]), int(bool(strict)),
+                                                 int(max_eval_farms)), self._g)
+        fa = None if farms is None else np.ascontiguousarray(farms, dtype=np.int32).reshape(-1)
+        n = w.env_batch if fa is None else int(fa.size)
+        fptr = None if fa is None else fa.ctypes.data
+        shapes = {"power": (n, N), "gradient": (n, N)}
+        if jacobian:
+            shapes["jacobian"] = (n, N, N)
+        on_device = _is_torch(yaw) or _is_torch(cotangent) or (out is not None and _is_torch(out["gradient"]))
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            kinds = {k: (torch.float32 if k == "power" else torch.float64) for k in shapes}
+            yaw, yptr = self._row_ptr(yaw, n, True, "yaw")
+            cotangent, cptr = self._row_ptr(cotangent, n, True, "cotangent")
+            if out is None:
+                dev = (yaw if yaw is not None else cotangent).device
+                out = {k: torch.empty(s, device=dev, dtype=kinds[k]) for k, s in shapes.items()}
+            for k, s in shapes.items():
+                assert out[k].is_cuda and out[k].dtype == kinds[k] and out[k].is_contiguous() and tuple(out[k].shape) == s, k
+            ptrs = {k: out[k].data_ptr() for k in shapes}
+        else:
+            yaw, yptr = self._row_ptr(yaw, n, False, "yaw")
+            cotangent, cptr = self._row_ptr(cotangent, n, False, "cotangent")
+            if out is None:
+                out = {k: np.empty(s, np.float32 if k == "power" else np.float64) for k, s in shapes.items()}
+            for k, s in shapes.items():
+                assert out[k].dtype == (np.float32 if k == "power" else np.float64) and out[k].flags.c_contiguous and out[k].shape == s, k
+            ptrs = {k: out[k].ctypes.data for k in shapes}
+        _lib.check_grad(self._lib.wf_grad_run(self._g, yptr, cptr, n, fptr, ptrs["power"], ptrs["gradient"], ptrs.get("jacobian"),
+                                              int(on_device)), self._g)
+        return {k: out[k] for k in shapes}
+
+    def backward(self, yaw, cotangent, step, bounds, strict):
+        """The vector-Jacobian product alone, device pointers in and out (autograd.differentiable_power): (B, N) float64."""
+        import torch
+
+        w = self._w
+        B, N = w.env_batch, w.num_turbines
+        _lib.check_grad(self._lib.wf_grad_config(self._g, float(step), float(bounds[0]), float(bounds[1]), int(bool(strict)), 0), self._g)
+        w._follow_torch_stream()
+        yaw, yptr = self._row_ptr(yaw, B, True, "yaw")
+        cotangent, cptr = self._row_ptr(cotangent, B, True, "cotangent")
+        grad = torch.empty((B, N), device=yaw.device, dtype=torch.float64)
+        _lib.check_grad(self._lib.wf_grad_run(self._g, yptr, cptr, B, None, None, grad.data_ptr(), None, 1), self._g)
+        return grad
+
+    def timing(self, detail=None):
+        if detail is not None:
+            _lib.check_grad(self._lib.wf_grad_set_timing(self._g, int(bool(detail))), self._g)
+            return None
+        t = [C.c_float(), C.c_float(), C.c_float()]
+        _lib.check_grad(self._lib.wf_grad_last_timing(self._g, *[C.byref(v) for v in t]), self._g)
+        return {"total_ms": float(t[0].value), "step_ms": float(t[1].value), "glue_ms": float(t[2].value)}
+
+    def evaluator(self):
+        """The evaluator handle (None before the first yaw_gradient): tools/grad_timing.py times a plain wf_step loop on it."""
+        return self._lib.wf_grad_evaluator(self._g)
+
+    def kernel_info(self) -> dict:
+        v = (C.c_int * (3 * len(self.KERNELS)))()
+        _lib.check_grad(self._lib.wf_grad_kernel_info(self._g, v), self._g)
+        keys = ("vgprs", "lds_bytes", "scratch_bytes")
+        return {n: dict(zip(keys, v[3 * i:3 * i + 3])) for i, n in enumerate(self.KERNELS)}
+
+    def close(self):
+        if self._g is not None:
+            self._lib.wf_grad_destroy(self._g)
+            self._g = None

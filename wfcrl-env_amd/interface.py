@@ -294,6 +294,21 @@ class HipFlorisInterface(BaseInterface):
         r = self.fi.optimize_yaw(y0, bounds=bounds, passes=passes, strict=strict, wd_uncertainty=wd_uncertainty)
         return r["yaw"][0].astype(np.float64), float(r["power"][0])
 
+    def yaw_gradient(self, yaw=None, cotangent=None, step=1.0, bounds=(-45.0, 45.0), strict=False, jacobian=False):
+        """How the power changes when a turbine turns, for the current wind: dict(power [N] W, gradient [N] W/deg[, jacobian
+        [N][N] W/deg, jacobian[i, j] = d P_j / d yaw_i]), float64.  yaw None: the current yaw command; cotangent None: ones,
+        the gradient of the farm power.  The DIFFERENCE QUOTIENT of include/wfgrad.h at `step` degrees, one-sided at a bound
+        (backend.WfStep.yaw_gradient; the project's own definition) — what FLORIS' scipy yaw optimiser takes 2 N
+        sequential solves for.  The yaw command of the interface is not changed."""
+        if self._wind_dirty:
+            self.fi.set_wind(self._ws, self._wd)
+            self._wind_dirty = False
+        y = self._current_yaw_command if yaw is None else yaw
+        y = np.asarray(y, dtype=np.float64).reshape(1, -1).astype(np.float32)
+        c = None if cotangent is None else np.asarray(cotangent, dtype=np.float32).reshape(1, -1)
+        r = self.fi.yaw_gradient(y, c, step=step, bounds=bounds, strict=strict, jacobian=jacobian)
+        return {k: v[0].astype(np.float64) for k, v in r.items()}
+
     def get_farm_AEP(self, wind_directions, wind_speeds, freq, cut_in_wind_speed=0.001, cut_out_wind_speed=None,
                      yaw_angles=None, no_wake=False, turbine_weights=None):
         """Annual energy production [GWh] over a wind rose, with the argument names FLORIS users know:

@@ -341,6 +341,28 @@ class VecWindFarmEnv:
         return self.fi.optimize_yaw(None, farms=farms, bounds=(lo, hi), passes=passes, strict=strict, out=out,
                                     wd_uncertainty=wd_uncertainty)
 
+    def power_gradient(self, cotangent=None, farms=None, step=1.0, strict=False):
+        """How the power changes when a turbine turns, at the farms' CURRENT yaw state and wind: dict(power (n_farms, N) W
+        float32 — the per-turbine power at the current yaw —, gradient (n_farms, N) W/deg float64), torch CUDA tensors when
+        the env returns torch.  gradient[b, i] = sum_j cotangent[b, j] d P_j / d yaw_i; cotangent None: ones, the gradient
+        of the farm power; a one-hot row gives turbine j's credit to every agent's yaw.  The derivative is the DIFFERENCE
+        QUOTIENT of include/wfgrad.h at `step` degrees (backend.WfStep.yaw_gradient; the project's own definition), with
+        the env's yaw limits as bounds: one-sided at a limit.  Run on a handle of its own: the env's yaw state,
+        accumulators, wind and buffers are read, never changed."""
+        lo, hi = self.controls["yaw"][0], self.controls["yaw"][1]
+        yaw = self.fi.env_get_state(as_torch=self.return_torch)["yaw"]
+        if farms is not None:
+            idx = np.ascontiguousarray(farms, dtype=np.int64).reshape(-1)
+            if self.return_torch:
+                import torch
+
+                yaw = yaw[torch.from_numpy(idx).to(yaw.device)]
+            else:
+                yaw = yaw[idx]
+        if cotangent is not None and self.return_torch:
+            cotangent = self._to_device(cotangent).float().reshape(yaw.shape)
+        return self.fi.yaw_gradient(yaw, cotangent, farms=farms, step=step, bounds=(lo, hi), strict=strict)
+
     def lut_target_yaw(self, table_slot: int = 0):
         """The yaw (num_envs, N) the look-up table in `table_slot` (backend.WfStep.set_yaw_table on `self.fi`) holds for
         every farm's CURRENT wind, clipped to the env's yaw bounds — a torch CUDA tensor when the env returns torch.  The
