@@ -198,12 +198,9 @@ _lib = None
 
 def build(force: bool = False) -> Path:
     """Compile csrc/ into libwfstep.so with hipcc for gfx950 (cross-compiles without a GPU)."""
-    srcs = sorted((PKG_DIR / "csrc").glob("*.hip")) + sorted((PKG_DIR / "csrc").glob("*.h"))
-    srcs += sorted((PKG_DIR / "csrc" / "probe").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "probe").glob("*.h"))
-    srcs += sorted((PKG_DIR / "csrc" / "yawopt").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "yawopt").glob("*.h"))
-    srcs += sorted((PKG_DIR / "csrc" / "rose").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "rose").glob("*.h"))
-    srcs += sorted((PKG_DIR / "csrc" / "robust").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "robust").glob("*.h"))
-    srcs += sorted((PKG_DIR / "csrc" / "grad").glob("*.hip")) + sorted((PKG_DIR / "csrc" / "grad").glob("*.h"))
+    srcs = []
+    for d in ("", "ext", "probe", "yawopt", "rose", "robust", "grad"):  # csrc/ itself, the extensions' shared layer, the extensions
+        srcs += sorted((PKG_DIR / "csrc" / d).glob("*.hip")) + sorted((PKG_DIR / "csrc" / d).glob("*.h"))
     srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfprobe.h", "wfyawopt.h", "wfrose.h", "wfrobust.h", "wfgrad.h")]
     stale = (not LIB_PATH.exists()) or any(s.stat().st_mtime > LIB_PATH.stat().st_mtime for s in srcs)
     if force or stale:
@@ -235,9 +232,10 @@ def load() -> C.CDLL:
             build()
         _share_hip_runtime_with_torch()
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in list(ABI.items()) + list(PROBE_ABI.items()) + list(YAWOPT_ABI.items()) + list(ROSE_ABI.items()) + list(ROBUST_ABI.items()) + list(GRAD_ABI.items()):
-            fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
-            fn.restype, fn.argtypes = res, args
+        for table in (ABI, PROBE_ABI, YAWOPT_ABI, ROSE_ABI, ROBUST_ABI, GRAD_ABI):
+            for name, (res, args) in table.items():
+                fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
+                fn.restype, fn.argtypes = res, args
         _lib = lib
     return _lib
 
@@ -246,60 +244,35 @@ class WfError(RuntimeError):
     pass
 
 
-def check_probe(rc: int, probe):
-    """`check` for the probe extension: the text comes from wf_probe_last_error."""
+def check_ext(rc: int, obj, last_error_name: str):
+    """`check` for an extension object: the text comes from the extension's own wf_*_last_error."""
     if rc != WF_OK:
-        msg = load().wf_probe_last_error(probe)
+        msg = getattr(load(), last_error_name)(obj)
         text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
         if rc in (-1, -2):
             raise ValueError(text)
         raise WfError(text)
+
+
+def check_probe(rc: int, probe):
+    check_ext(rc, probe, "wf_probe_last_error")
 
 
 def check_yawopt(rc: int, opt):
-    """`check` for the yaw-optimiser extension: the text comes from wf_yawopt_last_error."""
-    if rc != WF_OK:
-        msg = load().wf_yawopt_last_error(opt)
-        text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
-        if rc in (-1, -2):
-            raise ValueError(text)
-        raise WfError(text)
+    check_ext(rc, opt, "wf_yawopt_last_error")
 
 
 def check_rose(rc: int, rose):
-    """`check` for the rose extension: the text comes from wf_rose_last_error."""
-    if rc != WF_OK:
-        msg = load().wf_rose_last_error(rose)
-        text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
-        if rc in (-1, -2):
-            raise ValueError(text)
-        raise WfError(text)
+    check_ext(rc, rose, "wf_rose_last_error")
 
 
 def check_robust(rc: int, rob):
-    """`check` for the robust extension: the text comes from wf_robust_last_error."""
-    if rc != WF_OK:
-        msg = load().wf_robust_last_error(rob)
-        text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
-        if rc in (-1, -2):
-            raise ValueError(text)
-        raise WfError(text)
+    check_ext(rc, rob, "wf_robust_last_error")
 
 
 def check_grad(rc: int, grad):
-    """`check` for the gradient extension: the text comes from wf_grad_last_error."""
-    if rc != WF_OK:
-        msg = load().wf_grad_last_error(grad)
-        text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
-        if rc in (-1, -2):
-            raise ValueError(text)
-        raise WfError(text)
+    check_ext(rc, grad, "wf_grad_last_error")
 
 
 def check(rc: int, handle=None):
-    if rc != WF_OK:
-        msg = load().wf_last_error(handle)
-        text = f"{WF_E.get(rc, rc)}: {msg.decode() if msg else ''}"
-        if rc in (-1, -2):
-            raise ValueError(text)
-        raise WfError(text)
+    check_ext(rc, handle, "wf_last_error")

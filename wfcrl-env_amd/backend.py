@@ -809,27 +809,12 @@ class WfStep:
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            for name in ("_probe_points", "_probe_plane"):  # a probe goes before its handle (include/wfprobe.h)
-                pr = getattr(self, name, None)
-                if pr is not None:
-                    pr.close()
+            # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h)
+            for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rose_obj", "_robust_obj", "_grad_obj"):
+                ext = getattr(self, name, None)
+                if ext is not None:
+                    ext.close()
                     setattr(self, name, None)
-            yo = getattr(self, "_yawopt_obj", None)  # ... and so does the yaw optimiser (include/wfyawopt.h)
-            if yo is not None:
-                yo.close()
-                self._yawopt_obj = None
-            ro = getattr(self, "_rose_obj", None)  # ... and the rose object (include/wfrose.h)
-            if ro is not None:
-                ro.close()
-                self._rose_obj = None
-            rb = getattr(self, "_robust_obj", None)  # ... and the robust object (include/wfrobust.h)
-            if rb is not None:
-                rb.close()
-                self._robust_obj = None
-            go = getattr(self, "_grad_obj", None)  # ... and the gradient object (include/wfgrad.h)
-            if go is not None:
-                go.close()
-                self._grad_obj = None
             self._lib.wf_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -840,13 +825,99 @@ class WfStep:
             pass
 
 
-class _Probe:
-    """One `wf_probe` object of a WfStep handle (include/wfprobe.h): its points and the two calls on them."""
+class _Ext:
+    """An extension object of a WfStep handle — the `wf_<NAME>` of include/wf<NAME>.h — and what the five wrappers share:
+    create / close, timing, kernel_info, evaluator, and the conversion of farm lists, (n, N) float32 rows and output dicts
+    into the pointers the C ABI takes.  `_r` is the raw object, `KERNELS` names kernel_info's entries in the library's order."""
+
+    NAME = ""
+    KERNELS = ()
 
     def __init__(self, owner: WfStep):
         self._w, self._lib = owner, owner._lib
-        self._p = C.c_void_p()
-        check(self._lib.wf_probe_create(owner._h, C.byref(self._p)), owner._h)
+        self._r = C.c_void_p()
+        check(self._fn("create")(owner._h, C.byref(self._r)), owner._h)
+
+    def _fn(self, name):
+        return getattr(self._lib, f"wf_{self.NAME}_{name}")
+
+    def _call(self, name, *args):
+        """wf_<NAME>_<name>(object, *args); a failure raises with the text of wf_<NAME>_last_error."""
+        _lib.check_ext(self._fn(name)(self._r, *args), self._r, f"wf_{self.NAME}_last_error")
+
+    def timing(self, detail=None):
+        if detail is not None:
+            self._call("set_timing", int(bool(detail)))
+            return None
+        t = [C.c_float(), C.c_float(), C.c_float()]
+        self._call("last_timing", *[C.byref(v) for v in t])
+        return {"total_ms": float(t[0].value), "step_ms": float(t[1].value), "glue_ms": float(t[2].value)}
+
+    def kernel_info(self) -> dict:
+        v = (C.c_int * (3 * len(self.KERNELS)))()
+        self._call("kernel_info", v)
+        keys = ("vgprs", "lds_bytes", "scratch_bytes")
+        return {n: dict(zip(keys, v[3 * i:3 * i + 3])) for i, n in enumerate(self.KERNELS)}
+
+    def evaluator(self):
+        """The evaluator's raw handle (None before the first run; of a robust object: the search's): tools/yawopt_timing.py,
+        robust_timing.py and grad_timing.py time a plain wf_step loop on it."""
+        return self._fn("evaluator")(self._r)
+
+    def close(self):
+        if self._r is not None:
+            self._fn("destroy")(self._r)
+            self._r = None
+
+    def _farms(self, farms):
+        """(the int32 array kept alive, the number of farms served, the list's pointer or None) of a `farms` argument."""
+        fa = None if farms is None else np.ascontiguousarray(farms, dtype=np.int32).reshape(-1)
+        return fa, (self._w.env_batch if fa is None else int(fa.size)), (None if fa is None else fa.ctypes.data)
+
+    def _rows(self, a, n, on_device, name, per="listed"):
+        """(the array kept alive, its pointer) of an (n, N) float32 input, or (None, None)."""
+        N = self._w.num_turbines
+        if a is None:
+            return None, None
+        if on_device:
+            import torch
+
+            assert a.is_cuda and a.dtype == torch.float32 and tuple(a.shape) == (n, N), name
+            a = a.contiguous()
+            return a, a.data_ptr()
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != (n, N):
+            raise ValueError(f"{name} must be (n_farms, num_turbines): a row per {per} farm")
+        return a, a.ctypes.data
+
+    @staticmethod
+    def _outputs(out, spec, on_device, like=None):
+        """The outputs `spec` = {name: (shape, NumPy dtype)} names, and their pointers in spec's order: `out` checked against
+        it, or allocated when None — torch CUDA tensors (on the device of `like`) on the device path, NumPy arrays else."""
+        if on_device:
+            import torch
+
+            kinds = {k: getattr(torch, np.dtype(d).name) for k, (_, d) in spec.items()}
+            if out is None:
+                out = {k: torch.empty(s, device=like.device, dtype=kinds[k]) for k, (s, _) in spec.items()}
+            for k, (s, _) in spec.items():
+                assert out[k].is_cuda and out[k].dtype == kinds[k] and out[k].is_contiguous() and tuple(out[k].shape) == s, k
+            return out, [out[k].data_ptr() for k in spec]
+        if out is None:
+            out = {k: np.empty(s, d) for k, (s, d) in spec.items()}
+        for k, (s, d) in spec.items():
+            assert out[k].dtype == d and out[k].flags.c_contiguous and out[k].shape == s, k
+        return out, [out[k].ctypes.data for k in spec]
+
+
+class _Probe(_Ext):
+    """One `wf_probe` object of a WfStep handle (include/wfprobe.h): its points and the two calls on them."""
+
+    NAME = "probe"
+    KERNELS = ("state", "sample")
+
+    def __init__(self, owner: WfStep):
+        super().__init__(owner)
         self.n_points = 0
         self._host_points = None  # the NumPy points this probe holds (a copy), or None: none yet, or a device tensor's
 
@@ -871,16 +942,14 @@ class _Probe:
         if on_device:
             self._w._follow_torch_stream()
         ptr = pts.data_ptr() if on_device else pts.ctypes.data
-        _lib.check_probe(self._lib.wf_probe_set_points(self._p, shape[-2], ptr, B if per_farm else 1, int(on_device)), self._p)
+        self._call("set_points", shape[-2], ptr, B if per_farm else 1, int(on_device))
         self.n_points = int(shape[-2])
         self._host_points = None if on_device else pts.copy()
 
     def sample(self, yaw, farms, out):
         w = self._w
         B, N, P = w.env_batch, w.num_turbines, self.n_points
-        fa = None if farms is None else np.ascontiguousarray(farms, dtype=np.int32).reshape(-1)
-        n_farms = B if fa is None else int(fa.size)
-        fptr = None if fa is None else fa.ctypes.data
+        fa, n_farms, fptr = self._farms(farms)
         shape = (n_farms, P, 3)
         if _is_torch(yaw) or _is_torch(out):
             import torch
@@ -894,7 +963,7 @@ class _Probe:
             if out is None:
                 out = torch.empty(shape, device=yaw.device, dtype=torch.float32)
             assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and (P == 0 or tuple(out.shape) == shape)
-            _lib.check_probe(self._lib.wf_probe_sample(self._p, yptr, n_farms, fptr, out.data_ptr(), 1), self._p)
+            self._call("sample", yptr, n_farms, fptr, out.data_ptr(), 1)
             return out
         yptr = None
         if yaw is not None:
@@ -903,101 +972,45 @@ class _Probe:
         if out is None:
             out = np.empty(shape, np.float32)
         assert out.dtype == np.float32 and out.flags.c_contiguous and (P == 0 or out.shape == shape)
-        _lib.check_probe(self._lib.wf_probe_sample(self._p, yptr, n_farms, fptr, out.ctypes.data, 0), self._p)
+        self._call("sample", yptr, n_farms, fptr, out.ctypes.data, 0)
         return out
 
     def timing(self) -> dict:
         a, b = C.c_float(), C.c_float()
-        _lib.check_probe(self._lib.wf_probe_last_timing(self._p, C.byref(a), C.byref(b)), self._p)
+        self._call("last_timing", C.byref(a), C.byref(b))
         return {"state_ms": float(a.value), "sample_ms": float(b.value)}
 
-    def kernel_info(self) -> dict:
-        v = (C.c_int * 6)()
-        _lib.check_probe(self._lib.wf_probe_kernel_info(self._p, v), self._p)
-        keys = ("vgprs", "lds_bytes", "scratch_bytes")
-        return {"state": dict(zip(keys, v[0:3])), "sample": dict(zip(keys, v[3:6]))}
 
-    def close(self):
-        if self._p is not None:
-            self._lib.wf_probe_destroy(self._p)
-            self._p = None
+def _passes(passes):
+    return (C.c_int * max(len(passes), 1))(*[int(k) for k in passes])
 
 
-class _YawOpt:
+class _YawOpt(_Ext):
     """The `wf_yawopt` object of a WfStep handle (include/wfyawopt.h)."""
 
-    def __init__(self, owner: WfStep):
-        self._w, self._lib = owner, owner._lib
-        self._o = C.c_void_p()
-        check(self._lib.wf_yawopt_create(owner._h, C.byref(self._o)), owner._h)
+    NAME = "yawopt"
 
     def run(self, yaw0, farms, bounds, passes, strict, max_eval_farms, out):
         w = self._w
-        B, N = w.env_batch, w.num_turbines
-        K = (C.c_int * max(len(passes), 1))(*[int(k) for k in passes])
-        _lib.check_yawopt(self._lib.wf_yawopt_config(self._o, float(bounds[0]), float(bounds[1]), len(passes), K, int(bool(strict)),
-                                                     int(max_eval_farms)), self._o)
-        fa = None if farms is None else np.ascontiguousarray(farms, dtype=np.int32).reshape(-1)
-        n = B if fa is None else int(fa.size)
-        fptr = None if fa is None else fa.ctypes.data
-        shapes = {"yaw": (n, N), "power": (n,), "power_initial": (n,)}
+        N = w.num_turbines
+        self._call("config", float(bounds[0]), float(bounds[1]), len(passes), _passes(passes), int(bool(strict)), int(max_eval_farms))
+        fa, n, fptr = self._farms(farms)
         on_device = _is_torch(yaw0) or (out is not None and _is_torch(out["yaw"]))
         if on_device:
-            import torch
-
             w._follow_torch_stream()
-            yptr = None
-            if yaw0 is not None:
-                assert yaw0.is_cuda and yaw0.dtype == torch.float32 and tuple(yaw0.shape) == (n, N)
-                yaw0 = yaw0.contiguous()
-                yptr = yaw0.data_ptr()
-            if out is None:
-                out = {k: torch.empty(s, device=yaw0.device, dtype=torch.float32) for k, s in shapes.items()}
-            for k, s in shapes.items():
-                assert out[k].is_cuda and out[k].dtype == torch.float32 and out[k].is_contiguous() and tuple(out[k].shape) == s, k
-            ptrs = [out[k].data_ptr() for k in shapes]
-        else:
-            yptr = None
-            if yaw0 is not None:
-                yaw0 = np.ascontiguousarray(yaw0, dtype=np.float32)
-                if yaw0.shape != (n, N):
-                    raise ValueError("yaw0 must be (n_farms, num_turbines): a row per optimised farm")
-                yptr = yaw0.ctypes.data
-            if out is None:
-                out = {k: np.empty(s, np.float32) for k, s in shapes.items()}
-            for k, s in shapes.items():
-                assert out[k].dtype == np.float32 and out[k].flags.c_contiguous and out[k].shape == s, k
-            ptrs = [out[k].ctypes.data for k in shapes]
-        _lib.check_yawopt(self._lib.wf_yawopt_run(self._o, yptr, n, fptr, ptrs[0], ptrs[1], ptrs[2], int(on_device)), self._o)
+        yaw0, yptr = self._rows(yaw0, n, on_device, "yaw0", per="optimised")
+        out, ptrs = self._outputs(out, {"yaw": ((n, N), np.float32), "power": ((n,), np.float32), "power_initial": ((n,), np.float32)},
+                                  on_device, yaw0)
+        self._call("run", yptr, n, fptr, *ptrs, int(on_device))
         return out
 
-    def timing(self, detail=None):
-        if detail is not None:
-            _lib.check_yawopt(self._lib.wf_yawopt_set_timing(self._o, int(bool(detail))), self._o)
-            return None
-        t = [C.c_float(), C.c_float(), C.c_float()]
-        _lib.check_yawopt(self._lib.wf_yawopt_last_timing(self._o, *[C.byref(v) for v in t]), self._o)
-        return {"total_ms": float(t[0].value), "step_ms": float(t[1].value), "glue_ms": float(t[2].value)}
 
-    def evaluator(self):
-        """The evaluator's raw handle (None before the first run): tools/yawopt_timing.py times a plain wf_step loop on it."""
-        return self._lib.wf_yawopt_evaluator(self._o)
-
-    def close(self):
-        if self._o is not None:
-            self._lib.wf_yawopt_destroy(self._o)
-            self._o = None
-
-
-class _Rose:
+class _Rose(_Ext):
     """The `wf_rose` object of a WfStep handle (include/wfrose.h)."""
 
+    NAME = "rose"
+    KERNELS = ("layout", "rowsum", "accumulate", "policy")
     INTERP = {"linear": 0, "nearest": 1}
-
-    def __init__(self, owner: WfStep):
-        self._w, self._lib = owner, owner._lib
-        self._r = C.c_void_p()
-        check(self._lib.wf_rose_create(owner._h, C.byref(self._r)), owner._h)
 
     def set_table(self, table, wd_axis, ws_axis, interp, slot):
         if interp not in self.INTERP:
@@ -1018,8 +1031,7 @@ class _Rose:
             ptrs, on_device = (twd.ctypes.data, tws.ctypes.data, tb.ctypes.data), 0
         if tuple(tb.shape) != (Dt, St, N):
             raise ValueError("a yaw table must be (len(wd_axis), len(ws_axis), num_turbines)")
-        _lib.check_rose(self._lib.wf_rose_set_table(self._r, int(slot), Dt, ptrs[0], St, ptrs[1], ptrs[2], self.INTERP[interp],
-                                                    on_device), self._r)
+        self._call("set_table", int(slot), Dt, ptrs[0], St, ptrs[1], ptrs[2], self.INTERP[interp], on_device)
 
     def _cases(self, cases):
         N = self._w.num_turbines
@@ -1052,25 +1064,21 @@ class _Rose:
         D, S = wd.size, ws.size
         kind, arg, fixed = self._cases(cases)
         Cn = kind.size
-        _lib.check_rose(self._lib.wf_rose_set_rose(self._r, D, wd.ctypes.data, S, ws.ctypes.data, freq.ctypes.data, float(cut_in),
-                                                   0.0 if cut_out is None else float(cut_out)), self._r)
-        _lib.check_rose(self._lib.wf_rose_config(self._r, int(bool(strict)), int(max_eval_farms)), self._r)
-        shapes = {"weighted_power": (Cn,), "weighted_turbine_power": (Cn, N), "condition_power": (Cn, D, S)}
+        self._call("set_rose", D, wd.ctypes.data, S, ws.ctypes.data, freq.ctypes.data, float(cut_in), 0.0 if cut_out is None else float(cut_out))
+        self._call("config", int(bool(strict)), int(max_eval_farms))
         fsum = float(np.sum(freq))
-        if out is not None:
+        on_device = out is not None
+        fptr = None if fixed is None else fixed.ctypes.data
+        if on_device:
             import torch
 
             w._follow_torch_stream()
-            for k, sh in shapes.items():
-                want = torch.float32 if k == "condition_power" else torch.float64
-                assert out[k].is_cuda and out[k].dtype == want and out[k].is_contiguous() and tuple(out[k].shape) == sh, k
-            fx = None if fixed is None else torch.as_tensor(fixed, device=out["condition_power"].device)
-            _lib.check_rose(self._lib.wf_rose_evaluate(self._r, Cn, kind.ctypes.data, arg.ctypes.data, None if fx is None else fx.data_ptr(),
-                                                       *[out[k].data_ptr() for k in shapes], 1), self._r)
-        else:
-            out = {k: np.empty(sh, np.float32 if k == "condition_power" else np.float64) for k, sh in shapes.items()}
-            _lib.check_rose(self._lib.wf_rose_evaluate(self._r, Cn, kind.ctypes.data, arg.ctypes.data, None if fixed is None else fixed.ctypes.data,
-                                                       *[out[k].ctypes.data for k in shapes], 0), self._r)
+        out, ptrs = self._outputs(out, {"weighted_power": ((Cn,), np.float64), "weighted_turbine_power": ((Cn, N), np.float64),
+                                        "condition_power": ((Cn, D, S), np.float32)}, on_device)
+        if on_device and fixed is not None:
+            fixed = torch.as_tensor(fixed, device=out["condition_power"].device)
+            fptr = fixed.data_ptr()
+        self._call("evaluate", Cn, kind.ctypes.data, arg.ctypes.data, fptr, *ptrs, int(on_device))
         wp, wtp = out["weighted_power"], out["weighted_turbine_power"]
         return {"expected_power": wp / fsum, "aep_gwh": wp * (8760.0 / 1.0e9), "turbine_expected_power": wtp / fsum,
                 "condition_power": out["condition_power"], "freq_sum": fsum, "weighted_power": wp, "weighted_turbine_power": wtp}
@@ -1090,69 +1098,27 @@ class _Rose:
         else:
             out = {k: np.empty((B, N), np.float32) for k in keys}
             ptr = {k: v.ctypes.data for k, v in out.items()}
-        _lib.check_rose(self._lib.wf_rose_policy(self._r, int(slot), ptr.get("target_yaw"), ptr.get("action"), int(bool(as_torch))), self._r)
+        self._call("policy", int(slot), ptr.get("target_yaw"), ptr.get("action"), int(bool(as_torch)))
         return out
 
-    def timing(self) -> dict:
-        t = [C.c_float(), C.c_float(), C.c_float()]
-        _lib.check_rose(self._lib.wf_rose_last_timing(self._r, *[C.byref(v) for v in t]), self._r)
-        return {"total_ms": float(t[0].value), "step_ms": float(t[1].value), "glue_ms": float(t[2].value)}
 
-    def kernel_info(self) -> dict:
-        v = (C.c_int * 12)()
-        _lib.check_rose(self._lib.wf_rose_kernel_info(self._r, v), self._r)
-        keys = ("vgprs", "lds_bytes", "scratch_bytes")
-        return {n: dict(zip(keys, v[3 * i:3 * i + 3])) for i, n in enumerate(("layout", "rowsum", "accumulate", "policy"))}
-
-    def close(self):
-        if self._r is not None:
-            self._lib.wf_rose_destroy(self._r)
-            self._r = None
-
-
-class _Robust:
+class _Robust(_Ext):
     """The `wf_robust` object of a WfStep handle (include/wfrobust.h)."""
 
-    FRAME = {"relative": 0, "fixed": 1}
+    NAME = "robust"
     KERNELS = ("order", "layout", "rowsum", "advance", "expect")
-
-    def __init__(self, owner: WfStep):
-        self._w, self._lib = owner, owner._lib
-        self._r = C.c_void_p()
-        check(self._lib.wf_robust_create(owner._h, C.byref(self._r)), owner._h)
+    FRAME = {"relative": 0, "fixed": 1}
 
     def _set_members(self, spec):
         delta, weight, frame = wd_uncertainty_members(spec)
-        _lib.check_robust(self._lib.wf_robust_set_members(self._r, int(delta.size), delta.ctypes.data, weight.ctypes.data,
-                                                          self.FRAME[frame]), self._r)
+        self._call("set_members", int(delta.size), delta.ctypes.data, weight.ctypes.data, self.FRAME[frame])
         s = 0.0
         for v in weight:  # (the library's normalisation: the sum in index order)
             s = s + float(v)
         return delta, weight / s
 
     def _config(self, bounds, passes, strict, max_eval_farms):
-        K = (C.c_int * max(len(passes), 1))(*[int(k) for k in passes])
-        _lib.check_robust(self._lib.wf_robust_config(self._r, float(bounds[0]), float(bounds[1]), len(passes), K, int(bool(strict)),
-                                                     int(max_eval_farms)), self._r)
-
-    def _farms(self, farms):
-        fa = None if farms is None else np.ascontiguousarray(farms, dtype=np.int32).reshape(-1)
-        return fa, (self._w.env_batch if fa is None else int(fa.size)), (None if fa is None else fa.ctypes.data)
-
-    def _yaw_ptr(self, yaw, n, on_device):
-        N = self._w.num_turbines
-        if yaw is None:
-            return None, None
-        if on_device:
-            import torch
-
-            assert yaw.is_cuda and yaw.dtype == torch.float32 and tuple(yaw.shape) == (n, N)
-            yaw = yaw.contiguous()
-            return yaw, yaw.data_ptr()
-        yaw = np.ascontiguousarray(yaw, dtype=np.float32)
-        if yaw.shape != (n, N):
-            raise ValueError("yaw must be (n_farms, num_turbines): a row per listed farm")
-        return yaw, yaw.ctypes.data
+        self._call("config", float(bounds[0]), float(bounds[1]), len(passes), _passes(passes), int(bool(strict)), int(max_eval_farms))
 
     def evaluate(self, yaw, farms, strict, max_eval_farms, out, spec):
         w = self._w
@@ -1160,27 +1126,14 @@ class _Robust:
         delta, wn = self._set_members(spec)
         self._config((-25.0, 25.0), (5, 4), strict, max_eval_farms)  # (bounds and passes play no part in an evaluation)
         fa, n, fptr = self._farms(farms)
-        shapes = {"expected_power": (n,), "turbine_expected_power": (n, N), "member_power": (n, delta.size)}
+        shapes = {"expected_power": ((n,), np.float64), "turbine_expected_power": ((n, N), np.float64),
+                  "member_power": ((n, delta.size), np.float32)}
         on_device = _is_torch(yaw) or (out is not None and _is_torch(out["expected_power"]))
         if on_device:
-            import torch
-
             w._follow_torch_stream()
-            kinds = {k: (torch.float32 if k == "member_power" else torch.float64) for k in shapes}
-            yaw, yptr = self._yaw_ptr(yaw, n, True)
-            if out is None:
-                out = {k: torch.empty(s, device=yaw.device, dtype=kinds[k]) for k, s in shapes.items()}
-            for k, s in shapes.items():
-                assert out[k].is_cuda and out[k].dtype == kinds[k] and out[k].is_contiguous() and tuple(out[k].shape) == s, k
-            ptrs = [out[k].data_ptr() for k in shapes]
-        else:
-            yaw, yptr = self._yaw_ptr(yaw, n, False)
-            if out is None:
-                out = {k: np.empty(s, np.float32 if k == "member_power" else np.float64) for k, s in shapes.items()}
-            for k, s in shapes.items():
-                assert out[k].dtype == (np.float32 if k == "member_power" else np.float64) and out[k].flags.c_contiguous and out[k].shape == s, k
-            ptrs = [out[k].ctypes.data for k in shapes]
-        _lib.check_robust(self._lib.wf_robust_evaluate(self._r, yptr, n, fptr, ptrs[0], ptrs[1], ptrs[2], int(on_device)), self._r)
+        yaw, yptr = self._rows(yaw, n, on_device, "yaw")
+        out, ptrs = self._outputs(out, shapes, on_device, yaw)
+        self._call("evaluate", yptr, n, fptr, *ptrs, int(on_device))
         return {**{k: out[k] for k in shapes}, "delta": delta, "weight": wn}
 
     def optimize(self, yaw0, farms, bounds, passes, strict, max_eval_farms, out, spec):
@@ -1189,114 +1142,40 @@ class _Robust:
         self._set_members(spec)
         self._config(bounds, passes, strict, max_eval_farms)
         fa, n, fptr = self._farms(farms)
-        shapes = {"yaw": (n, N), "power": (n,), "power_initial": (n,)}
         on_device = _is_torch(yaw0) or (out is not None and _is_torch(out["yaw"]))
         if on_device:
-            import torch
-
             w._follow_torch_stream()
-            yaw0, yptr = self._yaw_ptr(yaw0, n, True)
-            if out is None:
-                out = {k: torch.empty(s, device=yaw0.device, dtype=torch.float32) for k, s in shapes.items()}
-            for k, s in shapes.items():
-                assert out[k].is_cuda and out[k].dtype == torch.float32 and out[k].is_contiguous() and tuple(out[k].shape) == s, k
-            ptrs = [out[k].data_ptr() for k in shapes]
-        else:
-            yaw0, yptr = self._yaw_ptr(yaw0, n, False)
-            if out is None:
-                out = {k: np.empty(s, np.float32) for k, s in shapes.items()}
-            for k, s in shapes.items():
-                assert out[k].dtype == np.float32 and out[k].flags.c_contiguous and out[k].shape == s, k
-            ptrs = [out[k].ctypes.data for k in shapes]
-        _lib.check_robust(self._lib.wf_robust_optimize(self._r, yptr, n, fptr, ptrs[0], ptrs[1], ptrs[2], int(on_device)), self._r)
+        yaw0, yptr = self._rows(yaw0, n, on_device, "yaw")
+        out, ptrs = self._outputs(out, {"yaw": ((n, N), np.float32), "power": ((n,), np.float32), "power_initial": ((n,), np.float32)},
+                                  on_device, yaw0)
+        self._call("optimize", yptr, n, fptr, *ptrs, int(on_device))
         return out
 
-    def timing(self, detail=None):
-        if detail is not None:
-            _lib.check_robust(self._lib.wf_robust_set_timing(self._r, int(bool(detail))), self._r)
-            return None
-        t = [C.c_float(), C.c_float(), C.c_float()]
-        _lib.check_robust(self._lib.wf_robust_last_timing(self._r, *[C.byref(v) for v in t]), self._r)
-        return {"total_ms": float(t[0].value), "step_ms": float(t[1].value), "glue_ms": float(t[2].value)}
 
-    def evaluator(self):
-        """The search's evaluator handle (None before the first robust optimize_yaw): tools/robust_timing.py times a plain
-        wf_step loop on it."""
-        return self._lib.wf_robust_evaluator(self._r)
-
-    def kernel_info(self) -> dict:
-        v = (C.c_int * (3 * len(self.KERNELS)))()
-        _lib.check_robust(self._lib.wf_robust_kernel_info(self._r, v), self._r)
-        keys = ("vgprs", "lds_bytes", "scratch_bytes")
-        return {n: dict(zip(keys, v[3 * i:3 * i + 3])) for i, n in enumerate(self.KERNELS)}
-
-    def close(self):
-        if self._r is not None:
-            self._lib.wf_robust_destroy(self._r)
-            self._r = None
-
-
-class _Grad:
+class _Grad(_Ext):
     """The `wf_grad` object of a WfStep handle (include/wfgrad.h)."""
 
+    NAME = "grad"
     KERNELS = ("layout", "reduce")
 
-    def __init__(self, owner: WfStep):
-        self._w, self._lib = owner, owner._lib
-        self._g = C.c_void_p()
-        check(self._lib.wf_grad_create(owner._h, C.byref(self._g)), owner._h)
-
-    def _row_ptr(self, a, n, on_device, name):
-        """(the array kept alive, its pointer) of an (n, N) float32 input, or (None, None)."""
-        N = self._w.num_turbines
-        if a is None:
-            return None, None
-        if on_device:
-            import torch
-
-            assert a.is_cuda and a.dtype == torch.float32 and tuple(a.shape) == (n, N), name
-            a = a.contiguous()
-            return a, a.data_ptr()
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.shape != (n, N):
-            raise ValueError(f"{name} must be (n_farms, num_turbines): a row per listed farm")
-        return a, a.ctypes.data
+    def _config(self, step, bounds, strict, max_eval_farms):
+        self._call("config", float(step), float(bounds[0]), float(bounds[1]), int(bool(strict)), int(max_eval_farms))
 
     def run(self, yaw, cotangent, farms, step, bounds, strict, max_eval_farms, jacobian, out):
         w = self._w
         N = w.num_turbines
-        _lib.check_grad(self._lib.wf_grad_config(self._g, float(step), float(bounds[0]), float(bounds[1]), int(bool(strict)),
-                                                 int(max_eval_farms)), self._g)
-        fa = None if farms is None else np.ascontiguousarray(farms, dtype=np.int32).reshape(-1)
-        n = w.env_batch if fa is None else int(fa.size)
-        fptr = None if fa is None else fa.ctypes.data
-        shapes = {"power": (n, N), "gradient": (n, N)}
+        self._config(step, bounds, strict, max_eval_farms)
+        fa, n, fptr = self._farms(farms)
+        shapes = {"power": ((n, N), np.float32), "gradient": ((n, N), np.float64)}
         if jacobian:
-            shapes["jacobian"] = (n, N, N)
+            shapes["jacobian"] = ((n, N, N), np.float64)
         on_device = _is_torch(yaw) or _is_torch(cotangent) or (out is not None and _is_torch(out["gradient"]))
         if on_device:
-            import torch
-
             w._follow_torch_stream()
-            kinds = {k: (torch.float32 if k == "power" else torch.float64) for k in shapes}
-            yaw, yptr = self._row_ptr(yaw, n, True, "yaw")
-            cotangent, cptr = self._row_ptr(cotangent, n, True, "cotangent")
-            if out is None:
-                dev = (yaw if yaw is not None else cotangent).device
-                out = {k: torch.empty(s, device=dev, dtype=kinds[k]) for k, s in shapes.items()}
-            for k, s in shapes.items():
-                assert out[k].is_cuda and out[k].dtype == kinds[k] and out[k].is_contiguous() and tuple(out[k].shape) == s, k
-            ptrs = {k: out[k].data_ptr() for k in shapes}
-        else:
-            yaw, yptr = self._row_ptr(yaw, n, False, "yaw")
-            cotangent, cptr = self._row_ptr(cotangent, n, False, "cotangent")
-            if out is None:
-                out = {k: np.empty(s, np.float32 if k == "power" else np.float64) for k, s in shapes.items()}
-            for k, s in shapes.items():
-                assert out[k].dtype == (np.float32 if k == "power" else np.float64) and out[k].flags.c_contiguous and out[k].shape == s, k
-            ptrs = {k: out[k].ctypes.data for k in shapes}
-        _lib.check_grad(self._lib.wf_grad_run(self._g, yptr, cptr, n, fptr, ptrs["power"], ptrs["gradient"], ptrs.get("jacobian"),
-                                              int(on_device)), self._g)
+        yaw, yptr = self._rows(yaw, n, on_device, "yaw")
+        cotangent, cptr = self._rows(cotangent, n, on_device, "cotangent")
+        out, ptrs = self._outputs(out, shapes, on_device, yaw if yaw is not None else cotangent)
+        self._call("run", yptr, cptr, n, fptr, ptrs[0], ptrs[1], ptrs[2] if jacobian else None, int(on_device))
         return {k: out[k] for k in shapes}
 
     def backward(self, yaw, cotangent, step, bounds, strict):
@@ -1305,33 +1184,10 @@ class _Grad:
 
         w = self._w
         B, N = w.env_batch, w.num_turbines
-        _lib.check_grad(self._lib.wf_grad_config(self._g, float(step), float(bounds[0]), float(bounds[1]), int(bool(strict)), 0), self._g)
+        self._config(step, bounds, strict, 0)
         w._follow_torch_stream()
-        yaw, yptr = self._row_ptr(yaw, B, True, "yaw")
-        cotangent, cptr = self._row_ptr(cotangent, B, True, "cotangent")
+        yaw, yptr = self._rows(yaw, B, True, "yaw")
+        cotangent, cptr = self._rows(cotangent, B, True, "cotangent")
         grad = torch.empty((B, N), device=yaw.device, dtype=torch.float64)
-        _lib.check_grad(self._lib.wf_grad_run(self._g, yptr, cptr, B, None, None, grad.data_ptr(), None, 1), self._g)
+        self._call("run", yptr, cptr, B, None, None, grad.data_ptr(), None, 1)
         return grad
-
-    def timing(self, detail=None):
-        if detail is not None:
-            _lib.check_grad(self._lib.wf_grad_set_timing(self._g, int(bool(detail))), self._g)
-            return None
-        t = [C.c_float(), C.c_float(), C.c_float()]
-        _lib.check_grad(self._lib.wf_grad_last_timing(self._g, *[C.byref(v) for v in t]), self._g)
-        return {"total_ms": float(t[0].value), "step_ms": float(t[1].value), "glue_ms": float(t[2].value)}
-
-    def evaluator(self):
-        """The evaluator handle (None before the first yaw_gradient): tools/grad_timing.py times a plain wf_step loop on it."""
-        return self._lib.wf_grad_evaluator(self._g)
-
-    def kernel_info(self) -> dict:
-        v = (C.c_int * (3 * len(self.KERNELS)))()
-        _lib.check_grad(self._lib.wf_grad_kernel_info(self._g, v), self._g)
-        keys = ("vgprs", "lds_bytes", "scratch_bytes")
-        return {n: dict(zip(keys, v[3 * i:3 * i + 3])) for i, n in enumerate(self.KERNELS)}
-
-    def close(self):
-        if self._g is not None:
-            self._lib.wf_grad_destroy(self._g)
-            self._g = None

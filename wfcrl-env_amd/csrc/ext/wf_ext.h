@@ -1,0 +1,133 @@
+// wf_ext.h — the host layer every extension object (probe/, yawopt/, rose/, robust/, grad/) stands on: the base struct with
+// the parent handle, the error text and the event pool; a grow-only device buffer that frees itself; the evaluator — a
+// further handle that follows the parent, configured through the public ABI of include/wfstep.h only; the checks an
+// extension asks of its parent and of a farm list; event recording and the step / glue split of a timed run; kernel
+// attributes; the passes' candidate grids.  wf_ext.hip holds the non-template parts, wf_ext_kernels.h the device side.
+// A new extension starts here: derive its object from ext_base, declare its buffers as dev_buf, and call these.
+#pragma once
+#include "../wf_handle.h"
+#include "wf_ext_kernels.h"
+
+namespace wfi {
+
+struct ext_base {
+  wf_handle* h = nullptr;
+  std::string err;
+  // timing: events of the last run; per_chunk == 0: only its first and last, nothing to split
+  int detail = 0;
+  std::vector<hipEvent_t> ev_pool;
+  size_t n_ev = 0, per_chunk = 0;
+  bool timed = false;
+  ~ext_base();
+};
+
+inline int ext_fail(ext_base* x, int code, const std::string& msg) {
+  if (x) x->err = msg;
+  return code;
+}
+#define WFX_HIP(x, call)                                                                             \
+  do {                                                                                               \
+    hipError_t e_ = (call);                                                                          \
+    if (e_ != hipSuccess) return ext_fail(x, WF_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+#define WFX_EV(x, evh, call)                                                     \
+  do {                                                                           \
+    int rc_ = (call);                                                            \
+    if (rc_ != WF_OK) return ext_fail(x, rc_, std::string("evaluator: ") + wf_last_error(evh)); \
+  } while (0)
+#define WFX_ON_DEVICE(x)                 \
+  DeviceGuard guard_((x)->h->device);    \
+  if (guard_.err != hipSuccess) return ext_fail(x, WF_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
+
+// grow-only device buffer; freed with the object that holds it
+template <class T>
+struct dev_buf {
+  T* p = nullptr;
+  size_t cap = 0;
+  dev_buf() = default;
+  dev_buf(const dev_buf&) = delete;
+  dev_buf& operator=(const dev_buf&) = delete;
+  ~dev_buf() { hipFree(p); }
+  operator T*() const { return p; }
+};
+
+// (the stream is drained before a buffer in use is released)
+template <class T>
+int reserve(ext_base* x, dev_buf<T>& buf, size_t n) {
+  if (n <= buf.cap) return WF_OK;
+  WFX_HIP(x, hipStreamSynchronize(x->h->stream));
+  hipFree(buf.p);
+  buf.p = nullptr; buf.cap = 0;
+  WFX_HIP(x, hipMalloc(&buf.p, sizeof(T) * n));
+  buf.cap = n;
+  return WF_OK;
+}
+
+// an evaluator and what it was built from
+struct evaluator {
+  wf_handle* ev = nullptr;
+  int E = 0, mode = -1;
+  wf_model_params model{};
+  std::vector<double> tws, tct, tcp, lx, ly;
+  wf_kernel_choice choice{};
+  double guard = 0.0;
+  hipStream_t stream = nullptr;
+  evaluator() = default;
+  evaluator(const evaluator&) = delete;
+  evaluator& operator=(const evaluator&) = delete;
+  ~evaluator() { if (ev) wf_destroy(ev); }
+};
+// A handle with the parent's model, layout, kernel choice and guard band on the parent's device and stream, E farms.
+// Rebuilt (after draining the stream) when any of these differs from what it was built from; the resolve mode and the
+// stream are just set.
+int ensure_evaluator(ext_base* x, evaluator& s, int E, int mode);
+
+// a farm list: the device copy and the host copy the upload reads from
+struct farm_list {
+  dev_buf<int> d;
+  std::vector<int> host;
+};
+
+// What a call asks of the parent: layout and batch, ONE layout, one turbine definition and, with `call`, a wind.  `what` is
+// the extension's phrase with its verb ("yaw optimisation serves"), `call` the entry point's name (null: no wind needed).
+int check_parent(ext_base* x, const char* what, const char* call);
+int check_wind(ext_base* x, const char* call);
+// ... and of its farm list; without one, n_farms becomes the parent's batch
+int check_farms(ext_base* x, int* n_farms, const int* farms);
+// the list on the device, fl.d reserved (a previous upload may still read the host copy: drain first)
+int upload_farms(ext_base* x, farm_list& fl, const int* farms, int n_farms);
+
+// an event on the parent's stream, from the pool
+int record(ext_base* x);
+// The last run's total, and with per_chunk != 0 its split: per chunk the events are e0 | glue e | step e | glue e | ... ,
+// then the next chunk's e0 (an empty interval) — interval q of a chunk is a step when q is even and not 0.
+int last_timing(ext_base* x, const char* not_run, float* total_ms, float* step_ms, float* glue_ms);
+// numRegs, static LDS bytes and private-segment bytes of an extension's n kernels
+int kernel_info(ext_base* x, int n, hipError_t (*attributes)(int, hipFuncAttributes*), int* info);
+
+// the search's passes (include/wfyawopt.h): K_max, and the grids h_0 = (hi - lo) / (K_0 - 1), h_p = 2 h_{p-1} / (K_p + 1)
+int k_max(int P, const int* K);
+void pass_grids(double lo, double hi, int P, const int* K, WfGrid* grid);
+
+template <class T>
+int ext_create(wf_handle* h, T** out) {
+  if (!h || !out) return WF_E_INVALID;
+  *out = nullptr;
+  T* x = new (std::nothrow) T();
+  if (!x) return fail(h, WF_E_NOMEM, "out of host memory");
+  x->h = h;
+  *out = x;
+  return WF_OK;
+}
+
+// (the object's members go in reverse order of declaration: evaluators, declared last, before the buffers; the events after)
+template <class T>
+int ext_destroy(T* x) {
+  if (!x) return WF_OK;
+  DeviceGuard guard(x->h->device);
+  hipStreamSynchronize(x->h->stream);
+  delete x;
+  return WF_OK;
+}
+
+}  // namespace wfi

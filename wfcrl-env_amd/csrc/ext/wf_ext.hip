@@ -1,0 +1,149 @@
+// wf_ext.hip — the non-template parts of the extensions' shared host layer (wf_ext.h).
+#include "wf_ext.h"
+
+namespace wfi {
+
+ext_base::~ext_base() {
+  for (hipEvent_t e : ev_pool) hipEventDestroy(e);
+}
+
+namespace {
+
+bool same_model(const wf_model_params& a, const wf_model_params& b) {  // (the tables are compared through the handle's vectors)
+  return std::memcmp(&a, &b, offsetof(wf_model_params, n_table)) == 0 && a.n_table == b.n_table &&
+         a.enable_secondary_steering == b.enable_secondary_steering && a.enable_yaw_added_recovery == b.enable_yaw_added_recovery &&
+         a.enable_transverse_velocities == b.enable_transverse_velocities;
+}
+
+}  // namespace
+
+int ensure_evaluator(ext_base* x, evaluator& s, int E, int mode) {
+  wf_handle* h = x->h;
+  const size_t n = (size_t)h->N;
+  const bool same = s.ev && s.E == E && same_model(s.model, h->model) && s.tws == h->tws && s.tct == h->tct && s.tcp == h->tcp &&
+                    s.lx.size() == n && std::equal(s.lx.begin(), s.lx.end(), h->lx.begin()) &&
+                    std::equal(s.ly.begin(), s.ly.end(), h->ly.begin()) &&
+                    std::memcmp(&s.choice, &h->choice, sizeof(wf_kernel_choice)) == 0 && s.guard == h->guard_rel;
+  if (same) {
+    if (s.stream != h->stream) {
+      WFX_EV(x, s.ev, wf_set_stream(s.ev, (void*)h->stream, 1));
+      s.stream = h->stream;
+    }
+    if (s.mode != mode) {
+      WFX_EV(x, s.ev, wf_set_risk_resolve(s.ev, mode));
+      s.mode = mode;
+    }
+    return WF_OK;
+  }
+  WFX_HIP(x, hipStreamSynchronize(h->stream));
+  if (s.ev) wf_destroy(s.ev);
+  s.ev = nullptr;
+  wf_handle* ev = nullptr;
+  if (wf_create(h->device, &ev) != WF_OK) return ext_fail(x, WF_E_HIP, std::string("evaluator: ") + wf_last_error(nullptr));
+  s.ev = ev;
+  wf_model_params m = h->model;
+  m.table_ws = h->tws.data(); m.table_ct = h->tct.data(); m.table_cp = h->tcp.data();
+  WFX_EV(x, ev, wf_set_stream(ev, (void*)h->stream, 1));
+  WFX_EV(x, ev, wf_set_model(ev, &m));
+  WFX_EV(x, ev, wf_set_kernel_choice(ev, &h->choice));
+  if (h->guard_user) WFX_EV(x, ev, wf_set_risk_guard(ev, h->guard_rel));
+  WFX_EV(x, ev, wf_set_layout(ev, h->N, h->lx.data(), h->ly.data()));
+  WFX_EV(x, ev, wf_set_batch(ev, E));
+  WFX_EV(x, ev, wf_set_risk_resolve(ev, mode));
+  s.E = E; s.mode = mode; s.stream = h->stream;
+  s.model = h->model; s.tws = h->tws; s.tct = h->tct; s.tcp = h->tcp;
+  s.lx.assign(h->lx.begin(), h->lx.begin() + n); s.ly.assign(h->ly.begin(), h->ly.begin() + n);
+  s.choice = h->choice; s.guard = h->guard_rel;
+  return WF_OK;
+}
+
+int check_wind(ext_base* x, const char* call) {
+  if (x->h->wind_count == 0)
+    return ext_fail(x, WF_E_INVALID, std::string("no wind has been set: wf_set_wind (or wf_wind_*) must be called before ") + call);
+  return WF_OK;
+}
+
+int check_parent(ext_base* x, const char* what, const char* call) {
+  wf_handle* h = x->h;
+  if (h->N <= 0 || h->B <= 0) return ext_fail(x, WF_E_INVALID, "no layout / batch: wf_set_layout and wf_set_batch come first");
+  if (h->n_layouts > 1 || !h->layout_n.empty())
+    return ext_fail(x, WF_E_UNSUPPORTED, std::string(what) + " a handle with ONE layout: this one holds several layouts (wf_set_layouts / wf_set_layouts_counts)");
+  if (!h->types.empty())
+    return ext_fail(x, WF_E_UNSUPPORTED, std::string(what) + " one turbine definition: this handle holds several turbine definitions (wf_set_turbine_types)");
+  return call ? check_wind(x, call) : WF_OK;
+}
+
+int check_farms(ext_base* x, int* n_farms, const int* farms) {
+  if (!farms) {
+    *n_farms = x->h->B;
+    return WF_OK;
+  }
+  if (*n_farms < 1) return ext_fail(x, WF_E_INVALID, "n_farms must be >= 1");
+  for (int k = 0; k < *n_farms; ++k)
+    if (farms[k] < 0 || farms[k] >= x->h->B) return ext_fail(x, WF_E_INVALID, "farm index out of range (0 .. env_batch - 1)");
+  return WF_OK;
+}
+
+int upload_farms(ext_base* x, farm_list& fl, const int* farms, int n_farms) {
+  WFX_HIP(x, hipStreamSynchronize(x->h->stream));
+  fl.host.assign(farms, farms + n_farms);
+  WFX_HIP(x, hipMemcpyAsync(fl.d, fl.host.data(), sizeof(int) * n_farms, hipMemcpyHostToDevice, x->h->stream));
+  return WF_OK;
+}
+
+int record(ext_base* x) {
+  if (x->n_ev == x->ev_pool.size()) {
+    hipEvent_t e = nullptr;
+    WFX_HIP(x, hipEventCreate(&e));
+    x->ev_pool.push_back(e);
+  }
+  WFX_HIP(x, hipEventRecord(x->ev_pool[x->n_ev++], x->h->stream));
+  return WF_OK;
+}
+
+int last_timing(ext_base* x, const char* not_run, float* total_ms, float* step_ms, float* glue_ms) {
+  if (!x->timed || x->n_ev < 2) return ext_fail(x, WF_E_INVALID, not_run);
+  WFX_ON_DEVICE(x);
+  WFX_HIP(x, hipEventSynchronize(x->ev_pool[x->n_ev - 1]));
+  float total = 0.0f, step = 0.0f, glue = 0.0f;
+  WFX_HIP(x, hipEventElapsedTime(&total, x->ev_pool[0], x->ev_pool[x->n_ev - 1]));
+  for (size_t k = 1; x->per_chunk && k < x->n_ev; ++k) {
+    float ms = 0.0f;
+    WFX_HIP(x, hipEventElapsedTime(&ms, x->ev_pool[k - 1], x->ev_pool[k]));
+    const size_t q = k % x->per_chunk;
+    if (q != 0 && q % 2 == 0) step += ms;
+    else glue += ms;
+  }
+  if (total_ms) *total_ms = total;
+  if (step_ms) *step_ms = step;
+  if (glue_ms) *glue_ms = glue;
+  return WF_OK;
+}
+
+int kernel_info(ext_base* x, int n, hipError_t (*attributes)(int, hipFuncAttributes*), int* info) {
+  WFX_ON_DEVICE(x);
+  for (int k = 0; k < n; ++k) {
+    hipFuncAttributes a{};
+    WFX_HIP(x, attributes(k, &a));
+    info[3 * k] = a.numRegs; info[3 * k + 1] = (int)a.sharedSizeBytes; info[3 * k + 2] = (int)a.localSizeBytes;
+  }
+  return WF_OK;
+}
+
+int k_max(int P, const int* K) {
+  int k = 0;
+  for (int p = 0; p < P; ++p) k = K[p] > k ? K[p] : k;
+  return k;
+}
+
+void pass_grids(double lo, double hi, int P, const int* K, WfGrid* grid) {
+  double hp = (hi - lo) / (double)(K[0] - 1);
+  grid[0] = WfGrid{0, 0, K[0], lo, hp};
+  for (int p = 1; p < P; ++p) {
+    const double s = 2.0 * hp / (double)(K[p] + 1);
+    grid[p] = WfGrid{0, 1, K[p], hp, s};
+    hp = s;
+  }
+}
+
+}  // namespace wfi

@@ -4,22 +4,15 @@
 // Layout of a chunk of C farm SLOTS with R = 2 N + 1 rows: evaluator farm e = slot R + row, so a slot's yaw block [R][N]
 // (and its power block) is contiguous and the chunk's blocks are one contiguous array — what the evaluator's wf_step reads
 // and writes.  Row 0 is the yaw as given, row 2 i + 1 has y_i -> y+_i, row 2 i + 2 has y_i -> y-_i.  Slots beyond the
-// chunk's farms (a ragged last chunk) repeat slot 0's farm and write no output.
+// chunk's farms (a ragged last chunk) repeat slot 0's farm and write no output (WfSlots: ext/wf_ext_kernels.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../../include/wfgrad.h"
-
-// which farm a slot works on: farms[base + s] (or base + s without a list), s = slot for the chunk's own slots, 0 beyond
-struct WfGradSlots {
-  const int* farms;  // device copy of the caller's list, or null
-  int base;          // first entry of the chunk in the list
-  int n_slots;       // farms of this chunk (<= C)
-  int C;             // slots of the evaluator
-};
+#include "../ext/wf_ext_kernels.h"
 
 struct WfGradLayoutArgs {
-  WfGradSlots sl;
+  WfSlots sl;
   const double *ws, *wd;  // the parent's wind
   int wind_stride;        // 0 shared, 1 per farm
   int N;

@@ -25,11 +25,6 @@
 
 namespace {
 
-__device__ __forceinline__ int gr_farm(const WfGradSlots& sl, int slot) {
-  const int s = sl.base + (slot < sl.n_slots ? slot : 0);
-  return sl.farms ? sl.farms[s] : s;
-}
-
 // the perturbed yaws (include/wfgrad.h): float64, clipped, rounded once
 __device__ __forceinline__ float gr_plus(float y, double h, double hi) {
   double p = (double)y + h;
@@ -51,7 +46,7 @@ __global__ __launch_bounds__(256) void wf_grad_layout_kernel(const WfGradLayoutA
   if (e >= a.sl.C * R) return;
   const int slot = e / R, row = e - slot * R;
   if (lane == 0) {
-    const int b = gr_farm(a.sl, slot);
+    const int b = wf_slot_farm(a.sl, slot);
     a.ews[e] = a.ws[(size_t)b * a.wind_stride];
     a.ewd[e] = a.wd[(size_t)b * a.wind_stride];
   }

@@ -2,9 +2,8 @@
 // the coordinate search that maximises it, run on the device (include/wfrobust.h).  The farm solve is the existing wf_step
 // on the object's evaluator handles; these kernels are the glue, so that a whole search is enqueued without a host read:
 //
-//   wf_robust_order_kernel    once per chunk: each slot's visit order under its NOMINAL direction — the float64 rotation and
-//                             stable rank sort of wf_yawopt_order_kernel, restated (yawopt/ stays as it is); one workgroup
-//                             per slot, one thread per turbine.
+//   wf_robust_order_kernel    once per chunk: each slot's visit order under its NOMINAL direction (ext/wf_ext_kernels.h:
+//                             wf_visit_order, shared with the yaw optimiser); one workgroup per slot, one thread per turbine.
 //   wf_robust_layout_kernel   once per chunk: the wind of every evaluator row (slot, candidate, member): ws and
 //                             wd + delta[m] from the parent's device wind; for wf_robust_evaluate also the row's yaw (the
 //                             farm's row, with the FIXED-frame offset).  ONE WAVE PER ROW, lanes over turbines in a loop: a
@@ -27,23 +26,9 @@
 // roundings, as in the NumPy restatement.
 #include <hip/hip_runtime.h>
 
-#include "../wf_f64_math.h"
 #include "wf_robust.h"
 
 namespace {
-
-__device__ __forceinline__ int rb_farm(const WfRobustSlots& sl, int slot) {
-  const int s = sl.base + (slot < sl.n_slots ? slot : 0);
-  return sl.farms ? sl.farms[s] : s;
-}
-
-// candidate j of a visit's grid around `inc` (wf_robust.h: WfRobustGrid)
-__device__ __forceinline__ float rb_candidate(const WfRobustGrid& g, double inc, int j, double lo, double hi) {
-  double c = g.mode == 0 ? g.a + (double)j * g.b : (inc - g.a) + (double)(j + 1) * g.b;
-  c = c < lo ? lo : c;
-  c = c > hi ? hi : c;
-  return (float)c;
-}
 
 // the yaw member m is stepped with (include/wfrobust.h: FRAME)
 __device__ __forceinline__ float rb_member_yaw(float yaw, int frame, double delta) {
@@ -52,35 +37,9 @@ __device__ __forceinline__ float rb_member_yaw(float yaw, int frame, double delt
 
 }  // namespace
 
-#define RB_MAX_N 256
-
-__global__ __launch_bounds__(RB_MAX_N) void wf_robust_order_kernel(const WfRobustOrderArgs a) {
-  __shared__ double sx[RB_MAX_N];
-  const int N = a.N, t = threadIdx.x, slot = blockIdx.x;
-  const int b = rb_farm(a.sl, slot);
-  // wd % 360, rotation about the bounding-box centre [A.1]: the arithmetic of wf_geometry_kernel
-  double wdm = fmod(a.wd[(size_t)b * a.wind_stride], 360.0);
-  if (wdm < 0.0) wdm += 360.0;
-  double dev = fmod(wdm - 270.0, 360.0);
-  if (dev < 0.0) dev += 360.0;
-  dev = fmod(dev + 360.0, 360.0);
-  double ca, sa;
-  sincos_any(dev * (M_PI / 180.0), sa, ca);
-  double xr = 0.0;
-  if (t < N) {
-    const double xo = a.lx[t] - a.xc, yo = a.ly[t] - a.yc;
-    xr = xo * ca - yo * sa + a.xc;
-    sx[t] = xr;
-  }
-  __syncthreads();
-  if (t < N) {
-    int rank = 0;
-    for (int u = 0; u < N; ++u) {
-      const double xu = sx[u];
-      rank += (xu < xr) || (xu == xr && u < t);
-    }
-    a.order[(size_t)slot * N + rank] = t;
-  }
+__global__ __launch_bounds__(WF_ORDER_MAX_N) void wf_robust_order_kernel(const WfRobustOrderArgs a) {
+  __shared__ double sx[WF_ORDER_MAX_N];
+  wf_visit_order(a, sx);
 }
 
 __global__ __launch_bounds__(256) void wf_robust_layout_kernel(const WfRobustLayoutArgs a) {
@@ -89,7 +48,7 @@ __global__ __launch_bounds__(256) void wf_robust_layout_kernel(const WfRobustLay
   const int M = a.mb.M, RM = a.R * M;
   if (e >= a.sl.C * RM) return;
   const int slot = e / RM, m = e % M;
-  const int b = rb_farm(a.sl, slot);
+  const int b = wf_slot_farm(a.sl, slot);
   const double dm = a.mb.delta[m];
   if (lane == 0) {
     a.ews[e] = a.ws[(size_t)b * a.wind_stride];
@@ -174,7 +133,7 @@ __global__ __launch_bounds__(256) void wf_robust_advance_kernel(const WfRobustAd
       if (ek > e_best) { e_best = ek; w = k; }  // strictly greater: the incumbent, then the lowest index, keep a tie
     }
     const float inc = brow[tp];
-    newval = w ? rb_candidate(a.prev, (double)inc, w - 1, a.lo, a.hi) : inc;
+    newval = w ? wf_grid_candidate(a.prev, (double)inc, w - 1, a.lo, a.hi) : inc;
     if (lane == 0) {
       if (w) a.best[row0 + tp] = newval;
       if (writes && a.first) a.out_init[slot] = (float)e_inc;
@@ -188,7 +147,7 @@ __global__ __launch_bounds__(256) void wf_robust_advance_kernel(const WfRobustAd
   int tn = 0;
   if (live && has_next) {
     tn = a.order[row0 + a.next.s];
-    if (lane < a.next.K) cnd[lane] = rb_candidate(a.next, (double)brow[tn], lane, a.lo, a.hi);
+    if (lane < a.next.K) cnd[lane] = wf_grid_candidate(a.next, (double)brow[tn], lane, a.lo, a.hi);
   }
   __syncthreads();
   if (live && has_next) {

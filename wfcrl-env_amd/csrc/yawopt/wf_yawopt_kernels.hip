@@ -2,8 +2,8 @@
 // (include/wfyawopt.h).  Candidate evaluation is the existing wf_step on the optimiser's evaluator handle; these kernels are
 // the glue, so that a whole optimisation is enqueued without a host round trip:
 //
-//   wf_yawopt_order_kernel    once per chunk: each slot's visit order — the float64 rotation and stable rank sort of
-//                             wf_geometry_kernel / wf_probe_state_kernel; one workgroup per slot, one thread per turbine.
+//   wf_yawopt_order_kernel    once per chunk: each slot's visit order (ext/wf_ext_kernels.h: wf_visit_order, shared with
+//                             the robust search); one workgroup per slot, one thread per turbine.
 //   wf_yawopt_wind_kernel     once per chunk, only for a parent with a wind per farm: each farm's wind repeated over its
 //                             candidate rows (device to device), what wf_set_wind on the evaluator then takes.
 //   wf_yawopt_advance_kernel  once per visit, select and expand fused: per slot, sum the power of the previous visit's K + 1
@@ -19,62 +19,17 @@
 // segment, no spill (tests/test_yawopt.py reads the metadata).
 #include <hip/hip_runtime.h>
 
-#include "../wf_f64_math.h"
 #include "wf_yawopt.h"
 
-namespace {
-
-__device__ __forceinline__ int yo_farm(const WfYawoptSlots& sl, int slot) {
-  const int s = sl.base + (slot < sl.n_slots ? slot : 0);
-  return sl.farms ? sl.farms[s] : s;
-}
-
-// candidate j of a visit's grid around `inc` (wf_yawopt.h: WfYawoptGrid).  The library is built with -ffp-contract=off: a
-// product and a sum stay two roundings, as in the NumPy restatement.
-__device__ __forceinline__ float yo_candidate(const WfYawoptGrid& g, double inc, int j, double lo, double hi) {
-  double c = g.mode == 0 ? g.a + (double)j * g.b : (inc - g.a) + (double)(j + 1) * g.b;
-  c = c < lo ? lo : c;
-  c = c > hi ? hi : c;
-  return (float)c;
-}
-
-}  // namespace
-
-#define YO_MAX_N 256
-
-__global__ __launch_bounds__(YO_MAX_N) void wf_yawopt_order_kernel(const WfYawoptOrderArgs a) {
-  __shared__ double sx[YO_MAX_N];
-  const int N = a.N, t = threadIdx.x, slot = blockIdx.x;
-  const int b = yo_farm(a.sl, slot);
-  // wd % 360, rotation about the bounding-box centre [A.1]: the arithmetic of wf_geometry_kernel
-  double wdm = fmod(a.wd[(size_t)b * a.wind_stride], 360.0);
-  if (wdm < 0.0) wdm += 360.0;
-  double dev = fmod(wdm - 270.0, 360.0);
-  if (dev < 0.0) dev += 360.0;
-  dev = fmod(dev + 360.0, 360.0);
-  double ca, sa;
-  sincos_any(dev * (M_PI / 180.0), sa, ca);
-  double xr = 0.0;
-  if (t < N) {
-    const double xo = a.lx[t] - a.xc, yo = a.ly[t] - a.yc;
-    xr = xo * ca - yo * sa + a.xc;
-    sx[t] = xr;
-  }
-  __syncthreads();
-  if (t < N) {
-    int rank = 0;
-    for (int u = 0; u < N; ++u) {
-      const double xu = sx[u];
-      rank += (xu < xr) || (xu == xr && u < t);
-    }
-    a.order[(size_t)slot * N + rank] = t;
-  }
+__global__ __launch_bounds__(WF_ORDER_MAX_N) void wf_yawopt_order_kernel(const WfYawoptOrderArgs a) {
+  __shared__ double sx[WF_ORDER_MAX_N];
+  wf_visit_order(a, sx);
 }
 
 __global__ __launch_bounds__(256) void wf_yawopt_wind_kernel(const WfYawoptWindArgs a) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= a.sl.C * a.R) return;
-  const int b = yo_farm(a.sl, e / a.R);
+  const int b = wf_slot_farm(a.sl, e / a.R);
   a.ews[e] = a.ws[b];
   a.ewd[e] = a.wd[b];
 }
@@ -135,7 +90,7 @@ __global__ __launch_bounds__(256) void wf_yawopt_advance_kernel(const WfYawoptAd
       if (pk > p_best) { p_best = pk; w = k; }  // strictly greater: the incumbent, then the lowest index, keep a tie
     }
     const float inc = brow[tp];
-    newval = w ? yo_candidate(a.prev, (double)inc, w - 1, a.lo, a.hi) : inc;
+    newval = w ? wf_grid_candidate(a.prev, (double)inc, w - 1, a.lo, a.hi) : inc;
     if (lane == 0) {
       if (w) a.best[row0 + tp] = newval;
       if (writes && a.first) a.out_init[slot] = (float)p_inc;
@@ -149,7 +104,7 @@ __global__ __launch_bounds__(256) void wf_yawopt_advance_kernel(const WfYawoptAd
   int tn = 0;
   if (live && has_next) {
     tn = a.order[row0 + a.next.s];
-    if (lane < a.next.K) cnd[lane] = yo_candidate(a.next, (double)brow[tn], lane, a.lo, a.hi);
+    if (lane < a.next.K) cnd[lane] = wf_grid_candidate(a.next, (double)brow[tn], lane, a.lo, a.hi);
   }
   __syncthreads();
   if (live && has_next) {
