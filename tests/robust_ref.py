@@ -69,36 +69,8 @@ def expected_power(x, y, ws, wd, yaw, delta, w, frame="fixed", p=None, step=None
 
 
 def optimize(x, y, ws, wd, delta, w, frame="fixed", yaw0=None, bounds=(-25.0, 25.0), passes=(5, 4), p=None, step=None):
-    """The robust search.  Returns what yawopt_ref.optimize returns (power / power_initial / history are E)."""
-    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
-    ws, wd = np.atleast_1d(np.asarray(ws, np.float64)), np.atleast_1d(np.asarray(wd, np.float64))
-    B, N = ws.size, x.size
-    lo, hi = float(bounds[0]), float(bounds[1])
-    best = np.zeros((B, N), np.float32) if yaw0 is None else np.array(yaw0, dtype=np.float32).reshape(B, N)
-    order = np.stack([yawopt_ref.visit_order(x, y, wd[b]) for b in range(B)])
-    margin = np.full(B, np.inf)
-    history = []
-    rows = np.arange(B)
-    p_init = None
-    for pi, (K, h, _) in enumerate(yawopt_ref.pass_steps(lo, hi, passes)):
-        for s in range(N):
-            t = order[:, s]
-            inc = best[rows, t]
-            cand = (np.broadcast_to(yawopt_ref.pass0_candidates(lo, hi, K), (B, K)) if pi == 0
-                    else yawopt_ref.refine_candidates(inc, h, K, lo, hi))
-            vals = np.concatenate([inc[:, None], cand], axis=1)  # index 0: the incumbent
-            yaw = np.repeat(best[:, None, :], K + 1, axis=1)
-            yaw[rows, :, t] = vals
-            pw = expected_power(x, y, np.repeat(ws, K + 1), np.repeat(wd, K + 1), yaw.reshape(B * (K + 1), N), delta, w, frame, p,
-                                step)[0].reshape(B, K + 1)
-            if p_init is None:
-                p_init = pw[:, 0].copy()
-                history.append(p_init)
-            win = np.argmax(pw, axis=1)  # first maximum: the incumbent, then the lowest index, keep a tie
-            pb = pw[rows, win]
-            rival = np.where(vals != vals[rows, win][:, None], pw, -np.inf).max(axis=1)
-            margin = np.minimum(margin, np.where(np.isfinite(rival), (pb - rival) / pb, np.inf))
-            best[rows, t] = vals[rows, win]
-            history.append(pb)
-    return {"yaw": best, "power": history[-1], "power_initial": p_init, "margin": margin, "history": np.array(history),
-            "order": order}
+    """The robust search: yawopt_ref.optimize over E.  Returns what it returns (power / power_initial / history are E)."""
+    def objective(x, y, ws, wd, yaw, p, step):
+        return expected_power(x, y, ws, wd, yaw, delta, w, frame, p, step)[0]
+
+    return yawopt_ref.optimize(x, y, ws, wd, yaw0, bounds, passes, p, step, objective)

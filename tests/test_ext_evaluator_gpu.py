@@ -6,7 +6,7 @@ band on the parent's stream (csrc/ext/wf_ext.h: ensure_evaluator).  Here each of
 parent is changed, and the call runs again: the second answer has to be, bit for bit, what the same call gives on a fresh
 WfStep constructed in the changed configuration — and, where the change moves the physics, not what the first call gave.
 
-Shapes are the smallest that reach the code: the three-turbine row of tests/test_grad_gpu.py, env_batch = 2 with two
+Shapes are the smallest that reach the code: the three-turbine row of tests/yawopt_ref.py, env_batch = 2 with two
 different winds, one pass of three candidates, three members, 2 directions x 1 speed, R = 2 N + 1 = 7 rows.  Every call is
 strict: every row is solved by the float64 kernel, whose bits depend neither on the batch nor on the kernel family
 (tests/test_grad_gpu.py), so a fresh handle is a bit-exact reference and no tolerance is needed."""
@@ -16,7 +16,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 D = 126.0
-ROW3 = (np.array([0.0, 5 * D, 10 * D]), np.zeros(3))  # three turbines in a row, 5 D apart (tests/test_grad_gpu.py)
+ROW3 = (np.array([0.0, 5 * D, 10 * D]), np.zeros(3))  # three turbines in a row, 5 D apart (tests/yawopt_ref.py: ROW3)
 ROW3_7D = (np.array([0.0, 7 * D, 14 * D]), np.zeros(3))
 WIND = (np.array([8.0, 9.0]), np.array([270.0, 268.0]))
 YAW = np.array([[10.0, 5.0, 0.0], [-8.0, 12.0, 3.0]], np.float32)

@@ -17,8 +17,6 @@ float64 kernel, whose bits do not depend on the batch (level stages, 
 evaluator of another batch size may pick another float32 kernel family (tests/test_yawopt_gpu.py: test_chunking), so there
 only two runs on the same evaluator are compared."""
 import functools
-import json
-import os
 
 import numpy as np
 import pytest
@@ -26,28 +24,19 @@ import pytest
 import grad_ref
 import parity
 import yawopt_ref
-from conftest import ROOT
+from yawopt_ref import ROW3
 
 pytestmark = pytest.mark.gpu
 
-D = 126.0
-ROW3 = (np.array([0.0, 5 * D, 10 * D]), np.zeros(3))  # three turbines in a row, 5 D apart
-ROW3_WIND = (np.array([8.0, 9.0, 7.0, 10.0]), np.array([270.0, 268.0, 90.0, 0.0]))
 BOUNDS = (-25.0, 25.0)
 NAMES = ("row3", "Ablaincourt_", "Turb6_Row2_", "Turb16_Row5_")
-
-
-@functools.lru_cache(maxsize=None)
-def _layouts():
-    with open(os.path.join(ROOT, "wfcrl-env_amd", "environments", "layouts.json")) as f:
-        return json.load(f)
 
 
 @functools.lru_cache(maxsize=None)
 def _case(name):
     """An input with its reference, computed once for the tests that share them: x, y, ws, wd, yaw, a random cotangent, the
     reference at c = 1 and the reference gradient at the random c."""
-    x, y, ws, wd = (ROW3 + ROW3_WIND) if name == "row3" else yawopt_ref.gpu_case(_layouts(), name)
+    x, y, ws, wd = yawopt_ref.gpu_input(name)
     B, N = len(ws), len(x)
     rng = np.random.default_rng(41)
     yaw = rng.uniform(-20.0, 20.0, (B, N)).astype(np.float32)

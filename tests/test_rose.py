@@ -3,27 +3,18 @@ the GPU tests use (tests/rose_ref.py: the yaw-table look-up, the rose reduction 
 float64 oracle)."""
 import glob
 import os
-import re
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT
-
+from ext_checks import CSRC, assert_no_private_segment, compile_kernels, declared, makefile
 from rose_ref import ROW3, ROW3_WD, ROW3_WS
-
-
-def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(wf_[a-z0-9_]+)\s*\(", text)))
 
 
 def test_rose_header_is_bound_and_the_other_tables_are_untouched():
     from wfcrl_env_amd import _lib
 
     lib = _lib.load()
-    syms = _declared("wfrose.h")
+    syms = declared("wfrose.h")
     assert {"wf_rose_create", "wf_rose_destroy", "wf_rose_set_table", "wf_rose_set_rose", "wf_rose_config", "wf_rose_evaluate",
             "wf_rose_policy", "wf_rose_last_timing", "wf_rose_kernel_info", "wf_rose_last_error"} <= set(syms)
     assert all(s.startswith("wf_rose_") for s in syms), syms
@@ -33,8 +24,8 @@ def test_rose_header_is_bound_and_the_other_tables_are_untouched():
         assert getattr(lib, s).argtypes == _lib.ROSE_ABI[s][1]  # bound by load()
     assert set(_lib.ROSE_ABI) == set(syms)
     assert lib.wf_version() == 7
-    assert set(_lib.ABI) == set(_declared("wfstep.h")) and set(_lib.PROBE_ABI) == set(_declared("wfprobe.h"))
-    assert set(_lib.YAWOPT_ABI) == set(_declared("wfyawopt.h"))
+    assert set(_lib.ABI) == set(declared("wfstep.h")) and set(_lib.PROBE_ABI) == set(declared("wfprobe.h"))
+    assert set(_lib.YAWOPT_ABI) == set(declared("wfyawopt.h"))
     assert not (set(_lib.ABI) | set(_lib.PROBE_ABI) | set(_lib.YAWOPT_ABI)) & set(_lib.ROSE_ABI)
 
 
@@ -42,27 +33,15 @@ def test_rose_kernels_have_no_private_segment(tmp_path):
     """Every kernel of csrc/rose/*.hip, compiled with the Makefile's flags: no private segment, no spilled register, no
     out-of-line call (a kernel with a private segment pays ~20 us per launch on MI355X, and an evaluation launches three of
     them per chunk).  Metadata only."""
-    src = os.path.join(ROOT, "wfcrl-env_amd", "csrc")
-    mk = open(os.path.join(src, "Makefile")).read()
-    flags = re.search(r"^FLAGS \?= (.*)$", mk, flags=re.M).group(1).replace("$(ARCH)", "gfx950").split()
+    mk = makefile()
     assert "ROSEOBJ = rose/wf_rose_kernels.o rose/wf_rose_abi.o" in mk and "$(ROSEOBJ): %.o: %.hip" in mk
     seen = {}
-    for k, hip in enumerate(sorted(glob.glob(os.path.join(src, "rose", "*.hip")))):
-        out = tmp_path / f"rose_{k}.s"
-        subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-S", "--cuda-device-only", "-o", str(out), hip], check=True, capture_output=True)
-        text = out.read_text()
+    hips = sorted(glob.glob(os.path.join(CSRC, "rose", "*.hip")))
+    for hip in hips:
+        meta, text = compile_kernels(os.path.relpath(hip, CSRC), tmp_path)
         assert "s_swappc_b64" not in text, hip
-        if "amdhsa.kernels:" not in text:
-            continue
-        meta = text[text.index("amdhsa.kernels:"):]
-        for block in meta.split("  - .agpr_count:")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", block).group(1)
-            seen[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
-                          for k in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "group_segment_fixed_size")}
-    want = ("wf_rose_layout_kernel", "wf_rose_rowsum_kernel", "wf_rose_accumulate_kernel", "wf_rose_policy_kernel")
-    assert len(seen) == len(want) and all(any(k in n for n in seen) for k in want), seen
-    for name, m in seen.items():
-        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (name, m)
+        seen.update(meta)
+    assert_no_private_segment(seen, ("wf_rose_layout_kernel", "wf_rose_rowsum_kernel", "wf_rose_accumulate_kernel", "wf_rose_policy_kernel"))
 
 
 def _table(rng, Dt, St, N):

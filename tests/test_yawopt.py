@@ -1,28 +1,16 @@
 """CPU: the yaw-optimiser extension (include/wfyawopt.h) — header, binding table, kernel metadata — and the properties of
 the reference the GPU tests use (tests/yawopt_ref.py: the coordinate search restated in NumPy over the float64 oracle)."""
-import os
-import re
-import subprocess
-
 import numpy as np
 
-from conftest import ROOT
-
-D = 126.0
-ROW3 = (np.array([0.0, 5 * D, 10 * D]), np.zeros(3))  # three turbines in a row, 5 D apart
-
-
-def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(wf_[a-z0-9_]+)\s*\(", text)))
+from ext_checks import assert_no_private_segment, compile_kernels, declared, makefile
+from yawopt_ref import ROW3
 
 
 def test_yawopt_header_is_bound_and_the_other_tables_are_untouched():
     from wfcrl_env_amd import _lib
 
     lib = _lib.load()
-    syms = _declared("wfyawopt.h")
+    syms = declared("wfyawopt.h")
     assert {"wf_yawopt_create", "wf_yawopt_destroy", "wf_yawopt_config", "wf_yawopt_run", "wf_yawopt_last_timing",
             "wf_yawopt_last_error"} <= set(syms)
     assert all(s.startswith("wf_yawopt_") for s in syms), syms
@@ -32,7 +20,7 @@ def test_yawopt_header_is_bound_and_the_other_tables_are_untouched():
         assert getattr(lib, s).argtypes == _lib.YAWOPT_ABI[s][1]  # bound by load()
     assert set(_lib.YAWOPT_ABI) == set(syms)
     assert lib.wf_version() == 7
-    assert set(_lib.ABI) == set(_declared("wfstep.h")) and set(_lib.PROBE_ABI) == set(_declared("wfprobe.h"))
+    assert set(_lib.ABI) == set(declared("wfstep.h")) and set(_lib.PROBE_ABI) == set(declared("wfprobe.h"))
     assert not (set(_lib.ABI) | set(_lib.PROBE_ABI)) & set(_lib.YAWOPT_ABI)
 
 
@@ -40,23 +28,10 @@ def test_yawopt_kernels_have_no_private_segment(tmp_path):
     """The three glue kernels, compiled with the Makefile's flags: no private segment, no spilled register, no out-of-line
     call (a kernel with a private segment pays ~20 us per launch on MI355X, and the advance kernel runs once per visit).
     Metadata only."""
-    src = os.path.join(ROOT, "wfcrl-env_amd", "csrc")
-    mk = open(os.path.join(src, "Makefile")).read()
-    flags = re.search(r"^FLAGS \?= (.*)$", mk, flags=re.M).group(1).replace("$(ARCH)", "gfx950").split()
+    mk = makefile()
     assert "YAWOPTOBJ = yawopt/wf_yawopt_kernels.o yawopt/wf_yawopt_abi.o" in mk and "$(YAWOPTOBJ): %.o: %.hip" in mk
-    out = tmp_path / "wf_yawopt_kernels.s"
-    subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-S", "--cuda-device-only", "-o", str(out),
-                                                      os.path.join(src, "yawopt", "wf_yawopt_kernels.hip")], check=True, capture_output=True)
-    text = out.read_text()
-    meta = text[text.index("amdhsa.kernels:"):]
-    seen = {}
-    for block in meta.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        seen[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
-                      for k in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "group_segment_fixed_size")}
-    assert len(seen) == 3 and all(any(k in n for n in seen) for k in ("wf_yawopt_order_kernel", "wf_yawopt_wind_kernel", "wf_yawopt_advance_kernel")), seen
-    for name, m in seen.items():
-        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (name, m)
+    seen, text = compile_kernels("yawopt/wf_yawopt_kernels.hip", tmp_path)
+    assert_no_private_segment(seen, ("wf_yawopt_order_kernel", "wf_yawopt_wind_kernel", "wf_yawopt_advance_kernel"))
     assert "s_swappc_b64" not in text
 
 

@@ -15,22 +15,15 @@ import numpy as np
 import pytest
 
 import yawopt_ref
+from yawopt_ref import ROW3, ROW3_WIND
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-D = 126.0
-ROW3 = (np.array([0.0, 5 * D, 10 * D]), np.zeros(3))  # three turbines in a row, 5 D apart
 MARGIN = 1e-5   # smallest reference margin at which a farm's yaw is compared
 YAW_TOL = 1e-4  # degrees
 POW_TOL = 2e-6  # relative; the strict kernels are held to 5e-7 per turbine in tests/test_resolve_gpu.py
 REAL = ("Ablaincourt_", "Turb16_Row5_")
-
-
-@functools.lru_cache(maxsize=None)
-def _layouts():
-    with open(os.path.join(ROOT, "wfcrl-env_amd", "environments", "layouts.json")) as f:
-        return json.load(f)
 
 
 @functools.lru_cache(maxsize=None)
@@ -39,7 +32,7 @@ def _real_case(name):
     computed once for the tests that share them."""
     from wfcrl_env_amd.backend import WfStep
 
-    x, y, ws, wd = yawopt_ref.gpu_case(_layouts(), name)
+    x, y, ws, wd = yawopt_ref.gpu_case(yawopt_ref.layouts(), name)
     ref = yawopt_ref.optimize(x, y, ws, wd)
     w = WfStep(x, y, env_batch=len(ws))
     w.set_wind(ws, wd)
@@ -74,7 +67,7 @@ def test_strict_tiny():
     from wfcrl_env_amd.backend import WfStep
 
     x, y = ROW3
-    ws, wd = np.array([8.0, 9.0, 7.0, 10.0]), np.array([270.0, 268.0, 90.0, 0.0])
+    ws, wd = ROW3_WIND
     ref = yawopt_ref.optimize(x, y, ws, wd)
     assert ref["margin"].min() >= MARGIN  # (all four farms are compared)
     w = WfStep(x, y, env_batch=4)
@@ -120,7 +113,7 @@ def test_shared_wind():
     bits, in both modes; in strict mode they are those of the same farm optimised under a wind per farm."""
     from wfcrl_env_amd.backend import WfStep
 
-    l = _layouts()["Ablaincourt_"]
+    l = yawopt_ref.layouts()["Ablaincourt_"]
     x, y = np.asarray(l["xcoords"], float), np.asarray(l["ycoords"], float)
     ws, wd = 8.5, 285.0  # (along the row of Ablaincourt: the reference gains 34 %, margin 3e-5)
     w = WfStep(x, y, env_batch=64)
@@ -213,7 +206,7 @@ def test_the_parent_is_untouched():
     from wfcrl_env_amd import environments as envs
     from wfcrl_env_amd.backend import WfStep
 
-    x, y, ws, wd = yawopt_ref.gpu_case(_layouts(), "Ablaincourt_", 16)
+    x, y, ws, wd = yawopt_ref.gpu_case(yawopt_ref.layouts(), "Ablaincourt_", 16)
     w = WfStep(x, y, env_batch=16)
     w.set_wind(ws, wd)
     w.env_config()
@@ -324,7 +317,7 @@ def test_smallest_farms(n):
 def test_interface_optimize_yaw():
     from wfcrl_env_amd.interface import HipFlorisInterface
 
-    l = _layouts()["Ablaincourt_"]
+    l = yawopt_ref.layouts()["Ablaincourt_"]
     x, y = np.asarray(l["xcoords"], float), np.asarray(l["ycoords"], float)
     fi = HipFlorisInterface(len(x), list(x), list(y))
     fi.init(wind_speed=8.5, wind_direction=285.0)

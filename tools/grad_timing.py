@@ -15,7 +15,6 @@ first builds the evaluator and times its kernel families):
                wind) with the perturbed yaws and the weighted sums in torch float64 — the same quotient; the three alternate
     kernels    wf_grad_kernel_info: vgprs / static LDS bytes / private-segment bytes
 Run from the repo root on an MI355X:  python tools/grad_timing.py [reps, default 10] [output file]"""
-import ctypes as C
 import json
 import os
 import sys
@@ -25,6 +24,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools.ext_timing import plain_loop_ms  # noqa: E402
 from wfcrl_env_amd.backend import WfStep  # noqa: E402
 
 assert torch.cuda.is_available(), "this tool measures on the GPU: there is nothing to fall back to"
@@ -33,21 +33,6 @@ REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 OUT = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "grad_timing.json")
 H, LO, HI = 1.0, -45.0, 45.0
 ROBUST_GLUE_SHARE = 0.022  # profiles/robust_timing.json, HornsRev1 x 256: glue over step time of the robust search
-
-
-def plain_loop_ms(w, n_steps, n_eval):
-    """n_steps wf_step calls on the gradient object's evaluator (its batch, its wind), between two events on the shared stream."""
-    lib, ev = w._lib, C.c_void_p(w._grad().evaluator())
-    yaw = torch.zeros((n_eval, w.num_turbines), dtype=torch.float32, device="cuda")
-    power = torch.empty_like(yaw)
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n_steps):
-        rc = lib.wf_step(ev, yaw.data_ptr(), power.data_ptr(), None, None, None, 1)
-        assert rc == 0, rc
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
 
 
 def python_loop(w, yaw, c):
@@ -94,7 +79,7 @@ def workload(label, name, B):
         w.grad_timing()
         w.yaw_gradient(yaw, c, jacobian=True, out=outj, **kw)
         w.grad_timing()
-        plain_loop_ms(w, chunks, n_eval)
+        plain_loop_ms(w, w._grad(), chunks, n_eval)
         python_loop(w, yaw, c)
     total, jac, plain, loop = [], [], [], []
     for _ in range(REPS):  # alternating: they share whatever else the machine is doing
@@ -102,7 +87,7 @@ def workload(label, name, B):
         total.append(w.grad_timing()["total_ms"])
         w.yaw_gradient(yaw, c, jacobian=True, out=outj, **kw)
         jac.append(w.grad_timing()["total_ms"])
-        plain.append(plain_loop_ms(w, chunks, n_eval))
+        plain.append(plain_loop_ms(w, w._grad(), chunks, n_eval))
         ms, p_loop, g_loop = python_loop(w, yaw, c)
         loop.append(ms)
     w.grad_timing(detail=True)

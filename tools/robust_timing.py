@@ -16,7 +16,6 @@ runs (the first builds the evaluator and times its kernel families):
 Default against strict: Ablaincourt x 32 (tests/yawopt_ref.gpu_case), both frames — the largest relative distance between the
 expected power the default mode reports and the strict run's; tests/test_robust_gpu.py asserts twice that, or 2e-4.
 Run from the repo root on an MI355X:  python tools/robust_timing.py [reps, default 10] [output file]"""
-import ctypes as C
 import json
 import os
 import sys
@@ -29,6 +28,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import robust_ref  # noqa: E402
 import yawopt_ref  # noqa: E402
+from tools.ext_timing import plain_loop_ms  # noqa: E402
 from wfcrl_env_amd.backend import WfStep  # noqa: E402
 
 assert torch.cuda.is_available(), "this tool measures on the GPU: there is nothing to fall back to"
@@ -40,23 +40,6 @@ MEMBERS = dict(delta=robust_ref.MEMBERS5[0], weight=robust_ref.MEMBERS5[1], fram
 M = len(MEMBERS["delta"])
 
 
-def plain_loop_ms(w, n_steps):
-    """n_steps wf_step calls on the search's evaluator (its batch, its wind), between two events on the shared stream."""
-    lib, ev = w._lib, C.c_void_p(w._robust().evaluator())
-    rows = (max(PASSES) + 1) * M
-    n_eval = min(w.env_batch, 65536 // rows) * rows
-    yaw = torch.zeros((n_eval, w.num_turbines), dtype=torch.float32, device="cuda")
-    power = torch.empty_like(yaw)
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n_steps):
-        rc = lib.wf_step(ev, yaw.data_ptr(), power.data_ptr(), None, None, None, 1)
-        assert rc == 0, rc
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), n_eval
-
-
 def workload(label, name, B):
     lay = LAYOUTS[name]
     x, y = np.asarray(lay["xcoords"], float), np.asarray(lay["ycoords"], float)
@@ -66,22 +49,23 @@ def workload(label, name, B):
     w.set_wind(rng.uniform(6.0, 12.0, B), rng.uniform(0.0, 360.0, B))
     out, nom = ({"yaw": torch.empty((B, N), dtype=torch.float32, device="cuda"), "power": torch.empty(B, dtype=torch.float32, device="cuda"),
                  "power_initial": torch.empty(B, dtype=torch.float32, device="cuda")} for _ in range(2))
-    chunks = -(-B // (65536 // ((max(PASSES) + 1) * M)))  # (the evaluator holds 65 536 rows: longer farm lists run in chunks)
+    rows = (max(PASSES) + 1) * M
+    chunks = -(-B // (65536 // rows))  # (the evaluator holds 65 536 rows: longer farm lists run in chunks)
+    n_eval = min(B, 65536 // rows) * rows  # the farms of the search's evaluator
     n_steps = len(PASSES) * N * chunks
     for _ in range(2):
         w.optimize_yaw(passes=PASSES, out=out, wd_uncertainty=MEMBERS)
         w.robust_timing()
         w.optimize_yaw(passes=PASSES, out=nom)
         w.yawopt_timing()
-    plain_loop_ms(w, n_steps)
+    plain_loop_ms(w, w._robust(), n_steps, n_eval)
     total, nominal, plain = [], [], []
     for _ in range(REPS):  # alternating: the three share whatever else the machine is doing
         w.optimize_yaw(passes=PASSES, out=out, wd_uncertainty=MEMBERS)
         total.append(w.robust_timing()["total_ms"])
         w.optimize_yaw(passes=PASSES, out=nom)
         nominal.append(w.yawopt_timing()["total_ms"])
-        ms, n_eval = plain_loop_ms(w, n_steps)
-        plain.append(ms)
+        plain.append(plain_loop_ms(w, w._robust(), n_steps, n_eval))
     w.robust_timing(detail=True)
     det = []
     for _ in range(REPS):

@@ -12,8 +12,7 @@ Timing, default passes (5, 4), one MI355X, HIP events on the handle's stream:
     farms_per_s, farm_steps_per_s (evaluated candidate farms, the rows that pad a pass below K_max included)
 Default against strict: the farms of tests/test_yawopt_gpu.py (tests/yawopt_ref.gpu_case) — the largest relative distance between
 the farm power the default mode reports and the strict run's; the test asserts twice that, or 2e-4.
-Run from the repo root on an MI355X:  python tools/yawopt_timing.py [reps, default 10]"""
-import ctypes as C
+Run from the repo root on an MI355X:  python tools/yawopt_timing.py [reps, default 10] [output directory, default profiles]"""
 import json
 import os
 import sys
@@ -25,30 +24,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import yawopt_ref  # noqa: E402
+from tools.ext_timing import plain_loop_ms  # noqa: E402
 from wfcrl_env_amd.backend import WfStep  # noqa: E402
 
 assert torch.cuda.is_available(), "this tool measures on the GPU: there is nothing to fall back to"
 LAYOUTS = json.load(open(os.path.join(ROOT, "wfcrl-env_amd", "environments", "layouts.json")))
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+OUT_DIR = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles")
 PASSES = (5, 4)
-
-
-def plain_loop_ms(w, n_steps):
-    """n_steps wf_step calls on the optimiser's evaluator (its batch, its wind), between two events on the shared stream."""
-    lib, ev = w._lib, C.c_void_p(w._yawopt().evaluator())
-    B, N = (w.env_batch // 1), w.num_turbines
-    rows = max(PASSES) + 1
-    n_eval = min(B, 65536 // rows) * rows
-    yaw = torch.zeros((n_eval, N), dtype=torch.float32, device="cuda")
-    power = torch.empty_like(yaw)
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n_steps):
-        rc = lib.wf_step(ev, yaw.data_ptr(), power.data_ptr(), None, None, None, 1)
-        assert rc == 0, rc
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), n_eval
 
 
 def workload(label, name, B, per_farm):
@@ -64,16 +47,17 @@ def workload(label, name, B, per_farm):
     out = {"yaw": torch.empty((B, N), dtype=torch.float32, device="cuda"), "power": torch.empty(B, dtype=torch.float32, device="cuda"),
            "power_initial": torch.empty(B, dtype=torch.float32, device="cuda")}
     n_steps = len(PASSES) * N
+    rows = max(PASSES) + 1
+    n_eval = min(B, 65536 // rows) * rows  # the farms of the optimiser's evaluator
     for _ in range(2):
         w.optimize_yaw(passes=PASSES, out=out)
         w.yawopt_timing()
-    plain_loop_ms(w, n_steps)
+    plain_loop_ms(w, w._yawopt(), n_steps, n_eval)
     total, plain = [], []
     for _ in range(REPS):  # alternating: the two share whatever else the machine is doing
         w.optimize_yaw(passes=PASSES, out=out)
         total.append(w.yawopt_timing()["total_ms"])
-        ms, n_eval = plain_loop_ms(w, n_steps)
-        plain.append(ms)
+        plain.append(plain_loop_ms(w, w._yawopt(), n_steps, n_eval))
     w.yawopt_timing(detail=True)
     det = []
     for _ in range(REPS):
@@ -119,11 +103,11 @@ if __name__ == "__main__":
     res = [workload("HornsRev1 x 1024, shared wind", "HornsRev1_", 1024, False),
            workload("HornsRev1 x 1024, a wind per farm", "HornsRev1_", 1024, True),
            workload("Ablaincourt x 4096, a wind per farm", "Ablaincourt_", 4096, True)]
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "yawopt_default_vs_strict.json"), "w") as f:
+    os.makedirs(OUT_DIR, exist_ok=True)
+    with open(os.path.join(OUT_DIR, "yawopt_default_vs_strict.json"), "w") as f:
         json.dump(gap, f, indent=1)
         f.write("\n")
-    with open(os.path.join(ROOT, "profiles", "yawopt_timing.json"), "w") as f:
+    with open(os.path.join(OUT_DIR, "yawopt_timing.json"), "w") as f:
         json.dump({"device": torch.cuda.get_device_name(0), "method": "HIP events on the handle's stream; 2 warm-up runs, median of `reps`; "
                    "optimisation and plain wf_step loop alternate", "workloads": res}, f, indent=1)
         f.write("\n")

@@ -2,9 +2,12 @@
 // the parent handle, the error text and the event pool; a grow-only device buffer that frees itself; the evaluator — a
 // further handle that follows the parent, configured through the public ABI of include/wfstep.h only; the checks an
 // extension asks of its parent and of a farm list; event recording and the step / glue split of a timed run; kernel
-// attributes; the passes' candidate grids.  wf_ext.hip holds the non-template parts, wf_ext_kernels.h the device side.
+// attributes; and the coordinate search over yaw that yawopt/ and robust/ run — its configuration, its buffers and the
+// driver that enqueues it (run_search).  wf_ext.hip holds the non-template parts, wf_ext_kernels.h the device side.
 // A new extension starts here: derive its object from ext_base, declare its buffers as dev_buf, and call these.
 #pragma once
+#include <functional>
+
 #include "../wf_handle.h"
 #include "wf_ext_kernels.h"
 
@@ -97,6 +100,28 @@ int check_farms(ext_base* x, int* n_farms, const int* farms);
 // the list on the device, fl.d reserved (a previous upload may still read the host copy: drain first)
 int upload_farms(ext_base* x, farm_list& fl, const int* farms, int n_farms);
 
+// the slots of the chunk that starts at entry `base` of the list (or of the batch), for an evaluator of C slots
+inline WfSlots chunk_slots(const farm_list& fl, const int* farms, int base, int n_farms, int C) {
+  return WfSlots{farms ? fl.d.p : nullptr, base, n_farms - base < C ? n_farms - base : C, C};
+}
+
+// A host caller's n input values go through the staging buffer `buf` (reserved by the caller); *d is where the kernels read
+// them: `src` itself for a device caller or none.
+template <class T>
+int stage_in(ext_base* x, const dev_buf<T>& buf, const T* src, size_t n, int on_device, const T** d) {
+  *d = src;
+  if (!src || on_device) return WF_OK;
+  WFX_HIP(x, hipMemcpyAsync(buf.p, src, sizeof(T) * n, hipMemcpyHostToDevice, x->h->stream));
+  *d = buf.p;
+  return WF_OK;
+}
+// where the kernels write an output: the device caller's array, a host caller's place in the staging buffer, null when not
+// asked for
+template <class T>
+T* out_ptr(T* user, const dev_buf<T>& staging, size_t offset, int on_device) {
+  return user ? (on_device ? user : staging.p + offset) : nullptr;
+}
+
 // an event on the parent's stream, from the pool
 int record(ext_base* x);
 // The last run's total, and with per_chunk != 0 its split: per chunk the events are e0 | glue e | step e | glue e | ... ,
@@ -105,9 +130,45 @@ int last_timing(ext_base* x, const char* not_run, float* total_ms, float* step_m
 // numRegs, static LDS bytes and private-segment bytes of an extension's n kernels
 int kernel_info(ext_base* x, int n, hipError_t (*attributes)(int, hipFuncAttributes*), int* info);
 
-// the search's passes (include/wfyawopt.h): K_max, and the grids h_0 = (hi - lo) / (K_0 - 1), h_p = 2 h_{p-1} / (K_p + 1)
+// ---- the coordinate search over yaw (include/wfyawopt.h; include/wfrobust.h: "with farm power replaced by E") ----
+struct search_config {
+  double lo = -25.0, hi = 25.0;
+  int P = 2, K[WF_SEARCH_MAX_PASSES] = {5, 4, 0, 0};
+  int strict = 0, max_eval = 65536;
+};
+// The validating setter.  rows_per_candidate: evaluator rows a candidate row takes (1; the robust search's members, 1 before
+// any are set); rows_msg: the refusal when max_eval_farms cannot hold one farm's rows.
+int set_search_config(ext_base* x, search_config& c, double lo, double hi, int n_passes, const int* K, int strict, int max_eval_farms,
+                      int rows_per_candidate, const char* rows_msg);
+// the passes: K_max, and the grids h_0 = (hi - lo) / (K_0 - 1), h_p = 2 h_{p-1} / (K_p + 1)
 int k_max(int P, const int* K);
 void pass_grids(double lo, double hi, int P, const int* K, WfGrid* grid);
+
+// what a searching object holds: the configuration and the device buffers (grow-only) every search needs
+struct yaw_search {
+  search_config cfg;
+  dev_buf<float> d_yaw, d_pow, d_best;  // [E][N] the evaluator's input and output, [C][N] best yaw so far
+  dev_buf<int> d_order;                 // [C][N]
+  farm_list farms;
+  dev_buf<float> d_in, d_out;  // staging for host callers: yaw0; yaw_opt, power_opt, power_init
+};
+
+// What differs between the searches.  Every hook returns a WF_* code (and has set the error text).
+struct search_policy {
+  const char *what, *name;  // check_parent's phrase and the entry point's name
+  int rows_per_candidate;   // evaluator rows a candidate row takes: 1, or the robust search's members
+  std::string no_rows;      // ... <= 0 is refused with this, after the parent's checks
+  const char* rows_msg;     // max_eval_farms cannot hold one farm's rows
+  std::function<int(int E)> reserve;  // the extension's own buffers for E evaluator farms; nothing is enqueued yet
+  std::function<int(const WfSlots&, int R, int E)> begin_chunk;  // the evaluator's wind for this chunk, then the order kernel
+  std::function<int(const WfAdvanceArgs&, int v)> visit;  // launch v: what turns the powers of visit v - 1 into the yaw of visit v
+};
+// The whole search on the parent's stream, the arguments those of wf_yawopt_run.  Chunks of C slots of R = K_max + 1 candidate
+// rows, E = C R rows_per_candidate evaluator farms.  Per chunk: begin_chunk, then launches v = 0 .. V (V = P N visits), each
+// followed — for v < V — by one wf_step on the evaluator from s.d_yaw into s.d_pow.  Events: the run's first and last, or with
+// detail per chunk e0 | glue e | step e | glue e | ... | glue e (2 V + 2; last_timing's per_chunk layout).
+int run_search(ext_base* x, yaw_search& s, evaluator& es, const search_policy& k, const float* yaw0, int n_farms, const int* farms,
+               float* yaw_opt, float* power_opt, float* power_init, int on_device);
 
 template <class T>
 int ext_create(wf_handle* h, T** out) {

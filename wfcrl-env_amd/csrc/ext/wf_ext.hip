@@ -130,6 +130,21 @@ int kernel_info(ext_base* x, int n, hipError_t (*attributes)(int, hipFuncAttribu
   return WF_OK;
 }
 
+int set_search_config(ext_base* x, search_config& c, double lo, double hi, int n_passes, const int* K, int strict, int max_eval_farms,
+                      int rows_per_candidate, const char* rows_msg) {
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) return ext_fail(x, WF_E_INVALID, "yaw bounds must be finite with lo < hi");
+  if (n_passes < 1 || n_passes > WF_SEARCH_MAX_PASSES) return ext_fail(x, WF_E_INVALID, "the number of passes must be in 1..4");
+  if (K[0] < 2 || K[0] > WF_SEARCH_MAX_K0) return ext_fail(x, WF_E_INVALID, "the first pass needs 2..31 candidates (K_0)");
+  for (int p = 1; p < n_passes; ++p)
+    if (K[p] < 1 || K[p] > WF_SEARCH_MAX_K) return ext_fail(x, WF_E_INVALID, "a refining pass needs 1..15 candidates (K_p)");
+  if (max_eval_farms <= 0) max_eval_farms = 65536;
+  if (max_eval_farms < (k_max(n_passes, K) + 1) * rows_per_candidate) return ext_fail(x, WF_E_INVALID, rows_msg);
+  c.lo = lo; c.hi = hi; c.P = n_passes;
+  for (int p = 0; p < WF_SEARCH_MAX_PASSES; ++p) c.K[p] = p < n_passes ? K[p] : 0;
+  c.strict = strict != 0; c.max_eval = max_eval_farms;
+  return WF_OK;
+}
+
 int k_max(int P, const int* K) {
   int k = 0;
   for (int p = 0; p < P; ++p) k = K[p] > k ? K[p] : k;
@@ -144,6 +159,78 @@ void pass_grids(double lo, double hi, int P, const int* K, WfGrid* grid) {
     grid[p] = WfGrid{0, 1, K[p], hp, s};
     hp = s;
   }
+}
+
+
+int run_search(ext_base* x, yaw_search& s, evaluator& es, const search_policy& k, const float* yaw0, int n_farms, const int* farms,
+               float* yaw_opt, float* power_opt, float* power_init, int on_device) {
+  wf_handle* h = x->h;
+  const search_config& cf = s.cfg;
+  int rc = check_parent(x, k.what, k.name);
+  if (rc != WF_OK) return rc;
+  if (k.rows_per_candidate <= 0) return ext_fail(x, WF_E_INVALID, k.no_rows);
+  if ((rc = check_farms(x, &n_farms, farms)) != WF_OK) return rc;
+  const int N = h->N, R = k_max(cf.P, cf.K) + 1, rows = R * k.rows_per_candidate;
+  if (cf.max_eval < rows) return ext_fail(x, WF_E_INVALID, k.rows_msg);
+  WFX_ON_DEVICE(x);
+  int C = cf.max_eval / rows;
+  if (C > n_farms) C = n_farms;
+  const int E = C * rows;
+  if ((rc = ensure_evaluator(x, es, E, cf.strict ? 2 : h->resolve_mode)) != WF_OK) return rc;
+  const size_t en = (size_t)E * N, fn = (size_t)n_farms * N;
+  rc = reserve(x, s.d_yaw, en);
+  if (rc == WF_OK) rc = reserve(x, s.d_pow, en);
+  if (rc == WF_OK) rc = k.reserve(E);
+  if (rc == WF_OK) rc = reserve(x, s.d_best, (size_t)C * N);
+  if (rc == WF_OK) rc = reserve(x, s.d_order, (size_t)C * N);
+  if (rc == WF_OK && farms) rc = reserve(x, s.farms.d, (size_t)n_farms);
+  if (rc == WF_OK && !on_device && yaw0) rc = reserve(x, s.d_in, fn);
+  if (rc == WF_OK && !on_device) rc = reserve(x, s.d_out, fn + 2 * (size_t)n_farms);
+  if (rc != WF_OK) return rc;
+  if (farms && (rc = upload_farms(x, s.farms, farms, n_farms)) != WF_OK) return rc;
+  const float* d_yaw0 = nullptr;
+  if ((rc = stage_in(x, s.d_in, yaw0, fn, on_device, &d_yaw0)) != WF_OK) return rc;
+  float* d_oyaw = out_ptr(yaw_opt, s.d_out, 0, on_device);
+  float* d_opow = out_ptr(power_opt, s.d_out, fn, on_device);
+  float* d_oini = out_ptr(power_init, s.d_out, fn + n_farms, on_device);
+
+  WfGrid grid[WF_SEARCH_MAX_PASSES];
+  pass_grids(cf.lo, cf.hi, cf.P, cf.K, grid);
+  const WfGrid none{-1, 0, 0, 0.0, 0.0};
+  const int V = cf.P * N;  // visits
+  x->n_ev = 0; x->timed = false;
+  const bool detail = x->detail != 0;
+  for (int base = 0; base < n_farms; base += C) {
+    if (base == 0 || detail) { rc = record(x); if (rc != WF_OK) return rc; }  // (detail: 2 V + 2 events per chunk)
+    WfAdvanceArgs aa{};
+    aa.sl = chunk_slots(s.farms, farms, base, n_farms, C);
+    if ((rc = k.begin_chunk(aa.sl, R, E)) != WF_OK) return rc;
+    aa.N = N; aa.R = R; aa.lo = cf.lo; aa.hi = cf.hi;
+    aa.order = s.d_order; aa.yaw = s.d_yaw; aa.best = s.d_best;
+    aa.yaw0 = d_yaw0 ? d_yaw0 + (size_t)base * N : nullptr;
+    aa.out_yaw = d_oyaw + (size_t)base * N; aa.out_power = d_opow + base; aa.out_init = d_oini + base;
+    for (int v = 0; v <= V; ++v) {  // launch v lays out visit v (v < V) from the powers of visit v - 1 (v > 0)
+      aa.prev = none; aa.next = none;
+      if (v > 0) { aa.prev = grid[(v - 1) / N]; aa.prev.s = (v - 1) % N; }
+      if (v < V) { aa.next = grid[v / N]; aa.next.s = v % N; }
+      aa.first = v == 1;
+      if ((rc = k.visit(aa, v)) != WF_OK) return rc;
+      if (detail) { rc = record(x); if (rc != WF_OK) return rc; }
+      if (v < V) {
+        WFX_EV(x, es.ev, wf_step(es.ev, s.d_yaw, s.d_pow, nullptr, nullptr, nullptr, 1));
+        if (detail) { rc = record(x); if (rc != WF_OK) return rc; }
+      }
+    }
+  }
+  if (!detail) { rc = record(x); if (rc != WF_OK) return rc; }
+  x->timed = true; x->per_chunk = detail ? 2 * (size_t)V + 2 : 0;
+  if (!on_device) {
+    WFX_HIP(x, hipMemcpyAsync(yaw_opt, d_oyaw, sizeof(float) * fn, hipMemcpyDeviceToHost, h->stream));
+    WFX_HIP(x, hipMemcpyAsync(power_opt, d_opow, sizeof(float) * n_farms, hipMemcpyDeviceToHost, h->stream));
+    WFX_HIP(x, hipMemcpyAsync(power_init, d_oini, sizeof(float) * n_farms, hipMemcpyDeviceToHost, h->stream));
+    WFX_HIP(x, hipStreamSynchronize(h->stream));
+  }
+  return WF_OK;
 }
 
 }  // namespace wfi

@@ -1,5 +1,6 @@
-// wf_ext_kernels.h — the device side the extensions share (yawopt/, robust/, grad/): which farm a chunk's slot works on,
-// a visit's candidate grid, and the visit order of a slot's turbines.  The per-extension headers build their kernels'
+// wf_ext_kernels.h — the device side the extensions share (yawopt/, robust/, rose/, grad/): which farm a chunk's slot works
+// on, a visit's candidate grid, the visit order of a slot's turbines, the phases the two searches' advance kernels have in
+// common, and the staged row sum of the rose and the robust search.  The per-extension headers build their kernels'
 // argument structs from these; wf_ext.h is the host side.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,6 +37,27 @@ struct WfOrderArgs {
 };
 
 #define WF_ORDER_MAX_N 256
+
+// the limits of a search (include/wfyawopt.h and include/wfrobust.h name them once each; their *_abi.hip assert they agree)
+#define WF_SEARCH_MAX_PASSES 4
+#define WF_SEARCH_MAX_K0 31
+#define WF_SEARCH_MAX_K 15
+#define WF_SEARCH_ROWS_MAX 32  // K_0 <= 31 candidates + the incumbent
+
+// What the two advance kernels share (WfYawoptAdvanceArgs and WfRobustAdvanceArgs derive from it): the host driver
+// (wf_ext.h: run_search) fills it per chunk and per visit, the extension adds where the previous visit's powers are.
+struct WfAdvanceArgs {
+  WfSlots sl;
+  int N, R;
+  double lo, hi;
+  WfGrid prev, next;  // the visit whose powers are in (prev.s < 0: none, initialise from yaw0) / the one to lay out
+  int first;                // prev is the run's first visit: its incumbent's power is power_init
+  const int* order;         // [C][N]
+  float* yaw;               // the evaluator's input for next: [C][R][N], or [C][R][M][N] under M members
+  float* best;              // [C][N] best (nominal) yaw so far
+  const float* yaw0;        // [n_slots][N] rows of this chunk, or null = zeros
+  float *out_yaw, *out_power, *out_init;  // rows of this chunk: [n_slots][N], [n_slots], [n_slots]; written when next.s < 0 / first
+};
 
 __device__ __forceinline__ int wf_slot_farm(const WfSlots& sl, int slot) {
   const int s = sl.base + (slot < sl.n_slots ? slot : 0);
@@ -79,4 +101,97 @@ __device__ __forceinline__ void wf_visit_order(const WfOrderArgs& a, double* sx)
     }
     a.order[(size_t)slot * N + rank] = t;
   }
+}
+
+// ---- the phases of an advance kernel (wf_yawopt_advance_kernel, wf_robust_advance_kernel): ONE WAVE PER SLOT, `lane` its
+// lane; sums[WF_SEARCH_ROWS_MAX], cnd[WF_SEARCH_ROWS_MAX] and brow[N] are the wave's own LDS.  `live` (the slot exists) is
+// wave-uniform and is tested INSIDE the phases that hold a barrier: every wave of the block calls them. ----
+
+// the slot's best yaw -> brow: seeded from yaw0 (or zeros) and stored before the first visit, loaded afterwards.  No barrier.
+__device__ __forceinline__ void wf_advance_load_best(const WfAdvanceArgs& a, int slot, int lane, float* brow) {
+  const int N = a.N;
+  const size_t row0 = (size_t)slot * N;
+  if (a.prev.s < 0) {
+    const size_t src = (size_t)(slot < a.sl.n_slots ? slot : 0) * N;
+    for (int t = lane; t < N; t += 64) {
+      const float v = a.yaw0 ? a.yaw0[src + t] : 0.0f;
+      brow[t] = v;
+      a.best[row0 + t] = v;
+    }
+  } else {
+    for (int t = lane; t < N; t += 64) brow[t] = a.best[row0 + t];
+  }
+}
+
+// The winner of the previous visit from sums[0 .. prev.K] (every lane finds it: K + 1 LDS broadcasts), the writes of best /
+// out_init / out_power, and the hand-over of the winner into brow between two barriers.  The caller's barrier after sums[]
+// comes first.
+__device__ __forceinline__ void wf_advance_pick(const WfAdvanceArgs& a, int slot, int lane, bool live, const double* sums, float* brow) {
+  const bool has_prev = a.prev.s >= 0, writes = live && slot < a.sl.n_slots;
+  const size_t row0 = (size_t)slot * a.N;
+  int tp = 0;
+  float newval = 0.0f;
+  if (live && has_prev) {
+    tp = a.order[row0 + a.prev.s];
+    const double p_inc = sums[0];
+    double p_best = p_inc;
+    int w = 0;
+    for (int k = 1; k <= a.prev.K; ++k) {
+      const double pk = sums[k];
+      if (pk > p_best) { p_best = pk; w = k; }  // strictly greater: the incumbent, then the lowest index, keep a tie
+    }
+    const float inc = brow[tp];
+    newval = w ? wf_grid_candidate(a.prev, (double)inc, w - 1, a.lo, a.hi) : inc;
+    if (lane == 0) {
+      if (w) a.best[row0 + tp] = newval;
+      if (writes && a.first) a.out_init[slot] = (float)p_inc;
+      if (writes && a.next.s < 0) a.out_power[slot] = (float)p_best;
+    }
+  }
+  __syncthreads();  // (every lane has read brow[tp])
+  if (live && has_prev && lane == 0) brow[tp] = newval;
+  __syncthreads();
+}
+
+// the next visit's candidates -> cnd; returns the turbine they replace.  The caller's barrier follows.
+__device__ __forceinline__ int wf_advance_candidates(const WfAdvanceArgs& a, int slot, int lane, bool live, const float* brow, float* cnd) {
+  if (!live || a.next.s < 0) return 0;
+  const int tn = a.order[(size_t)slot * a.N + a.next.s];
+  if (lane < a.next.K) cnd[lane] = wf_grid_candidate(a.next, (double)brow[tn], lane, a.lo, a.hi);
+  return tn;
+}
+
+// after the last visit: the slot's best yaw is the answer
+__device__ __forceinline__ void wf_advance_write_best(const WfAdvanceArgs& a, int slot, int lane, const float* brow) {
+  for (int t = lane; t < a.N; t += 64) a.out_yaw[(size_t)slot * a.N + t] = brow[t];
+}
+
+// ---- the staged row sum (wf_rose_rowsum_kernel, wf_robust_rowsum_kernel): a block of ONE wave stages the N float32 powers of
+// its `nr` rows (<= 64, contiguous at src) in LDS with coalesced loads — consecutive lanes on consecutive floats; odd row
+// stride: no bank conflict — then lane k adds row k in turbine order in float64.  Returns lane k's sum (0 for k >= nr). ----
+__device__ __forceinline__ double wf_staged_rowsum(const float* __restrict__ src, int nr, int N, int stride, float* pw, int lane) {
+  const int n_load = nr * N;
+  for (int i = lane; i < n_load; i += 64) {
+    const int r = i / N, t = i - r * N;
+    pw[r * stride + t] = src[i];
+  }
+  __syncthreads();
+  double sum = 0.0;
+  if (lane < nr) {
+    const float* row = pw + lane * stride;
+    for (int t = 0; t < N; ++t) sum += (double)row[t];
+  }
+  return sum;
+}
+
+// its launch: rows per block — what fits in 32 KiB of LDS, at most a row per lane —, the odd row stride and the LDS bytes
+struct WfRowsumLaunch {
+  int rows_per_block, stride, blocks;
+  size_t lds_bytes;
+};
+inline WfRowsumLaunch wf_rowsum_launch(int n_rows, int N) {
+  const int stride = N | 1;
+  int rpb = 32768 / (4 * stride);
+  rpb = rpb < 1 ? 1 : (rpb > 64 ? 64 : rpb);
+  return WfRowsumLaunch{rpb, stride, (n_rows + rpb - 1) / rpb, sizeof(float) * rpb * stride};
 }

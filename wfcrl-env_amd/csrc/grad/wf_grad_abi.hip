@@ -91,18 +91,17 @@ int wf_grad_run(wf_grad* g, const float* yaw, const float* cotangent, int n_farm
       d_cot = dst;
     }
   }
-  float* d_power = power ? (on_device ? power : g->d_outf) : nullptr;
-  double* d_grad = gradient ? (on_device ? gradient : g->d_outd) : nullptr;
-  double* d_jac = jacobian ? (on_device ? jacobian : g->d_outd + (gradient ? fn : 0)) : nullptr;
+  float* d_power = out_ptr(power, g->d_outf, 0, on_device);
+  double* d_grad = out_ptr(gradient, g->d_outd, 0, on_device);
+  double* d_jac = out_ptr(jacobian, g->d_outd, gradient ? fn : 0, on_device);
   const int wind_stride = h->wind_count == 1 ? 0 : 1;
   const bool detail = g->detail != 0;
   g->n_ev = 0; g->timed = false;
   for (int base = 0; base < n_farms; base += C) {
-    const int n_slots = n_farms - base < C ? n_farms - base : C;
     const size_t off = (size_t)base * N;
     if (base == 0 || detail) { rc = record(g); if (rc != WF_OK) return rc; }  // (detail: four events per chunk)
     WfGradLayoutArgs la{};
-    la.sl = WfSlots{farms ? g->farms.d.p : nullptr, base, n_slots, C};
+    la.sl = chunk_slots(g->farms, farms, base, n_farms, C);
     la.ws = h->d_ws; la.wd = h->d_wd; la.wind_stride = wind_stride; la.N = N;
     la.h = g->step; la.lo = g->lo; la.hi = g->hi;
     la.yaw_in = d_yaw_in ? d_yaw_in + off : nullptr; la.yaw = g->d_yaw;
@@ -113,7 +112,7 @@ int wf_grad_run(wf_grad* g, const float* yaw, const float* cotangent, int n_farm
     WFX_EV(g, ev, wf_step(ev, g->d_yaw, g->d_pow, nullptr, nullptr, nullptr, 1));
     if (detail) { rc = record(g); if (rc != WF_OK) return rc; }
     WfGradReduceArgs ra{};
-    ra.n_slots = n_slots; ra.N = N; ra.power_ev = g->d_pow; ra.d = g->d_div;
+    ra.n_slots = la.sl.n_slots; ra.N = N; ra.power_ev = g->d_pow; ra.d = g->d_div;
     ra.cot = d_cot ? d_cot + off : nullptr;
     ra.power = d_power ? d_power + off : nullptr;
     ra.gradient = d_grad ? d_grad + off : nullptr;

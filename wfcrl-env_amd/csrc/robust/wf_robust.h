@@ -6,7 +6,8 @@
 // contiguous array — what the evaluator's wf_step reads and writes.  Row 0 is the incumbent, rows 1 .. K the candidates,
 // rows K+1 .. R-1 copies of the incumbent (a pass with fewer candidates than K_max); wf_robust_evaluate has R = 1.  Slots
 // beyond the chunk's farms (a ragged last chunk) repeat slot 0's farm and write no output.
-// The slots (WfSlots), the candidate grid (WfGrid) and the order kernel's arguments are ext/wf_ext_kernels.h's.
+// The slots (WfSlots), the candidate grid (WfGrid), the order kernel's arguments and what the advance kernel shares with the
+// yaw optimiser's (WfAdvanceArgs) are ext/wf_ext_kernels.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -42,19 +43,9 @@ struct WfRobustRowsumArgs {
   double* rowsum;      // [n_rows] farm power of every row
 };
 
-struct WfRobustAdvanceArgs {
-  WfSlots sl;
+struct WfRobustAdvanceArgs : WfAdvanceArgs {  // (yaw: [C][R][M][N])
   WfRobustMembers mb;
-  int N, R;
-  double lo, hi;
-  WfGrid prev, next;  // the visit whose row sums are in `rowsum` (prev.s < 0: none, initialise from yaw0) / the one to lay out
-  int first;                // prev is the run's first visit: its incumbent's E is power_init
-  const int* order;         // [C][N]
-  const double* rowsum;     // [C][R][M] farm power of prev's rows
-  float* yaw;               // [C][R][M][N] the evaluator's input for next
-  float* best;              // [C][N] best (nominal) yaw so far
-  const float* yaw0;        // [n_slots][N] rows of this chunk, or null = zeros
-  float *out_yaw, *out_power, *out_init;  // rows of this chunk: [n_slots][N], [n_slots], [n_slots]; written when next.s < 0 / first
+  const double* rowsum;  // [C][R][M] farm power of prev's rows
 };
 
 struct WfRobustExpectArgs {

@@ -9,8 +9,7 @@
 //                             farm's row, with the FIXED-frame offset).  ONE WAVE PER ROW, lanes over turbines in a loop: a
 //                             row's N floats are contiguous, so every store is a whole line.
 //   wf_robust_rowsum_kernel   once per visit: the farm power of every row — its N float32 powers added in caller order in
-//                             float64.  A block stages its rows' powers in LDS with coalesced loads (consecutive lanes on
-//                             consecutive floats; odd row stride: no bank conflict), then lane k adds row k in turbine order.
+//                             float64: the staged row sum of ext/wf_ext_kernels.h (wf_staged_rowsum), shared with the rose.
 //   wf_robust_advance_kernel  once per visit, select and expand fused: per slot, E of the previous visit's K + 1 candidates
 //                             from the [R][M] row sums in member order, the winner (strictly greater than the incumbent;
 //                             lowest index among equals), the slot's best yaw, and the next visit's [R][M][N] yaw block —
@@ -63,92 +62,45 @@ __global__ __launch_bounds__(256) void wf_robust_layout_kernel(const WfRobustLay
 
 __global__ __launch_bounds__(64) void wf_robust_rowsum_kernel(const WfRobustRowsumArgs a, int rows_per_block, int stride) {
   extern __shared__ float rb_pw[];
-  const int lane = threadIdx.x, N = a.N;
+  const int lane = threadIdx.x;
   const int e0 = blockIdx.x * rows_per_block;
   int nr = a.n_rows - e0;
   nr = nr > rows_per_block ? rows_per_block : nr;
-  const float* __restrict__ src = a.power + (size_t)e0 * N;
-  const int n_load = nr * N;
-  for (int i = lane; i < n_load; i += 64) {
-    const int r = i / N, t = i - r * N;
-    rb_pw[r * stride + t] = src[i];
-  }
-  __syncthreads();
-  if (lane < nr) {
-    const float* row = rb_pw + lane * stride;
-    double sum = 0.0;
-    for (int t = 0; t < N; ++t) sum += (double)row[t];
-    a.rowsum[e0 + lane] = sum;
-  }
+  const double sum = wf_staged_rowsum(a.power + (size_t)e0 * a.N, nr, a.N, stride, rb_pw, lane);
+  if (lane < nr) a.rowsum[e0 + lane] = sum;
 }
 
 // Dynamic LDS per wave: 32 doubles (the candidates' E), 32 floats (the next candidates), N floats (the slot's best yaw); the
-// launcher sizes the region (a multiple of 16 bytes).
+// launcher sizes the region (a multiple of 16 bytes).  The phases shared with the yaw optimiser (best yaw, winner,
+// candidates) are ext/wf_ext_kernels.h's.
 #define RB_HDR_BYTES (WF_ROBUST_ROWS_MAX * 8 + WF_ROBUST_ROWS_MAX * 4)
 
 __global__ __launch_bounds__(256) void wf_robust_advance_kernel(const WfRobustAdvanceArgs a, int region_bytes) {
   extern __shared__ double rb_dyn[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int slot = blockIdx.x * 4 + wv;
-  const bool live = slot < a.sl.C;  // (wave-uniform; the barriers below are reached by every wave)
+  const bool live = slot < a.sl.C;  // (wave-uniform; the barriers below, and those of the phases, are reached by every wave)
   char* region = (char*)rb_dyn + (size_t)wv * region_bytes;
   double* sums = (double*)region;
   float* cnd = (float*)(region + WF_ROBUST_ROWS_MAX * 8);
   float* brow = (float*)(region + RB_HDR_BYTES);
   const int N = a.N, M = a.mb.M, RM = a.R * M;
   const bool has_prev = a.prev.s >= 0, has_next = a.next.s >= 0;
-  const bool writes = live && slot < a.sl.n_slots;
-  const size_t row0 = (size_t)slot * N;
 
   // ---- the slot's best yaw -> LDS; E of each candidate of the previous visit: lane k, members in index order, float64 ----
   if (live) {
-    if (!has_prev) {
-      const size_t src = (size_t)(slot < a.sl.n_slots ? slot : 0) * N;
-      for (int t = lane; t < N; t += 64) {
-        const float v = a.yaw0 ? a.yaw0[src + t] : 0.0f;
-        brow[t] = v;
-        a.best[row0 + t] = v;
-      }
-    } else {
-      for (int t = lane; t < N; t += 64) brow[t] = a.best[row0 + t];
-      if (lane <= a.prev.K) {
-        const double* __restrict__ rs = a.rowsum + ((size_t)slot * a.R + lane) * M;
-        double e = 0.0;
-        for (int m = 0; m < M; ++m) e += a.mb.w[m] * rs[m];
-        sums[lane] = e;
-      }
+    wf_advance_load_best(a, slot, lane, brow);
+    if (has_prev && lane <= a.prev.K) {
+      const double* __restrict__ rs = a.rowsum + ((size_t)slot * a.R + lane) * M;
+      double e = 0.0;
+      for (int m = 0; m < M; ++m) e += a.mb.w[m] * rs[m];
+      sums[lane] = e;
     }
   }
   __syncthreads();
-  // ---- the winner (every lane finds it: K + 1 LDS broadcasts) ----
-  int tp = 0;
-  float newval = 0.0f;
-  if (live && has_prev) {
-    tp = a.order[row0 + a.prev.s];
-    const double e_inc = sums[0];
-    double e_best = e_inc;
-    int w = 0;
-    for (int k = 1; k <= a.prev.K; ++k) {
-      const double ek = sums[k];
-      if (ek > e_best) { e_best = ek; w = k; }  // strictly greater: the incumbent, then the lowest index, keep a tie
-    }
-    const float inc = brow[tp];
-    newval = w ? wf_grid_candidate(a.prev, (double)inc, w - 1, a.lo, a.hi) : inc;
-    if (lane == 0) {
-      if (w) a.best[row0 + tp] = newval;
-      if (writes && a.first) a.out_init[slot] = (float)e_inc;
-      if (writes && !has_next) a.out_power[slot] = (float)e_best;
-    }
-  }
-  __syncthreads();  // (every lane has read brow[tp])
-  if (live && has_prev && lane == 0) brow[tp] = newval;
-  __syncthreads();
+  wf_advance_pick(a, slot, lane, live, sums, brow);
   // ---- the next visit's candidates, then its yaw block: per (row, member) the best yaw, one entry replaced per candidate row ----
-  int tn = 0;
-  if (live && has_next) {
-    tn = a.order[row0 + a.next.s];
-    if (lane < a.next.K) cnd[lane] = wf_grid_candidate(a.next, (double)brow[tn], lane, a.lo, a.hi);
-  }
+  const int tn = wf_advance_candidates(a, slot, lane, live, brow, cnd);
   __syncthreads();
   if (live && has_next) {
     float* __restrict__ blk = a.yaw + (size_t)slot * RM * N;
@@ -160,8 +112,8 @@ __global__ __launch_bounds__(256) void wf_robust_advance_kernel(const WfRobustAd
       if (t == tn && k >= 1 && k <= a.next.K) v = cnd[k - 1];
       blk[i] = rb_member_yaw(v, a.mb.frame, a.mb.delta[m]);
     }
-  } else if (writes) {
-    for (int t = lane; t < N; t += 64) a.out_yaw[row0 + t] = brow[t];
+  } else if (live && slot < a.sl.n_slots) {
+    wf_advance_write_best(a, slot, lane, brow);
   }
 }
 
@@ -199,11 +151,8 @@ extern "C" hipError_t wfk_launch_robust_layout(const WfRobustLayoutArgs* a, hipS
   return hipGetLastError();
 }
 extern "C" hipError_t wfk_launch_robust_rowsum(const WfRobustRowsumArgs* a, hipStream_t s) {
-  const int stride = a->N | 1;
-  int rpb = 32768 / (4 * stride);  // rows per block: what fits in 32 KiB of LDS, at most a row per lane
-  rpb = rpb < 1 ? 1 : (rpb > 64 ? 64 : rpb);
-  hipLaunchKernelGGL(wf_robust_rowsum_kernel, dim3((a->n_rows + rpb - 1) / rpb), dim3(64), sizeof(float) * rpb * stride, s, *a, rpb,
-                     stride);
+  const WfRowsumLaunch l = wf_rowsum_launch(a->n_rows, a->N);
+  hipLaunchKernelGGL(wf_robust_rowsum_kernel, dim3(l.blocks), dim3(64), l.lds_bytes, s, *a, l.rows_per_block, l.stride);
   return hipGetLastError();
 }
 extern "C" hipError_t wfk_launch_robust_advance(const WfRobustAdvanceArgs* a, hipStream_t s) {

@@ -182,7 +182,7 @@ int wf_rose_evaluate(wf_rose* r, int n_cases, const int* case_kind, const int* c
   WfRoseReduceArgs ra{};
   ra.ws = r->d_ws; ra.freq = r->d_freq; ra.cut_in = r->cut_in; ra.cut_out = r->cut_out;
   ra.power = r->d_pow; ra.rowsum = r->d_rowsum;
-  ra.condition_power = condition_power ? (on_device ? condition_power : r->d_cond) : nullptr;
+  ra.condition_power = out_ptr(condition_power, r->d_cond, 0, on_device);
   ra.acc_turbine = r->d_acc; ra.acc_farm = r->d_acc + cn;
   r->n_ev = 0; r->timed = false;
   for (int row0 = 0; row0 < R; row0 += E) {
@@ -228,8 +228,8 @@ int wf_rose_policy(wf_rose* r, int slot, float* target_yaw, float* action, int o
   pa.B = h->B; pa.N = h->N; pa.wind_stride = h->wind_count == h->B ? 1 : 0;
   pa.ws = h->d_ws; pa.wd = h->d_wd; pa.yaw_state = h->d_env_yaw;
   pa.lo = h->env.yaw_lo; pa.hi = h->env.yaw_hi; pa.step = h->env.yaw_step; pa.discrete = h->env.discrete;
-  pa.target = target_yaw ? (on_device ? target_yaw : r->d_pol) : nullptr;
-  pa.action = action ? (on_device ? action : r->d_pol + bn) : nullptr;
+  pa.target = out_ptr(target_yaw, r->d_pol, 0, on_device);
+  pa.action = out_ptr(action, r->d_pol, bn, on_device);
   WFX_HIP(r, wfk_launch_rose_policy(&pa, h->stream));
   if (!on_device) {
     if (target_yaw) WFX_HIP(r, hipMemcpyAsync(target_yaw, r->d_pol, sizeof(float) * bn, hipMemcpyDeviceToHost, h->stream));

@@ -6,9 +6,8 @@
 //                              table look-up of include/wfrose.h in float64.  ONE WAVE PER ROW, lanes over turbines in a loop
 //                              (N can exceed 64): a row's N floats are contiguous, so every store is a whole line.
 //   wf_rose_rowsum_kernel      once per chunk: the farm power of every row — its N float32 powers added in caller order in
-//                              float64 — masked by cut-in / cut-out, to the partial-sum input and to condition_power.  A block
-//                              stages its rows' powers in LDS with coalesced loads (odd row stride: no bank conflict), then
-//                              lane k adds row k in turbine order.
+//                              float64 — masked by cut-in / cut-out, to the partial-sum input and to condition_power: the
+//                              staged row sum of ext/wf_ext_kernels.h (wf_staged_rowsum), shared with the robust search.
 //   wf_rose_accumulate_kernel  once per chunk: the frequency-weighted sums.  ONE THREAD PER SUM (case x turbine, and case x
 //                              farm) walks this chunk's conditions in (d, s) index order in float64, starting from the partial
 //                              the previous chunk left in the device buffer: a fixed order whatever the scheduling and
@@ -24,6 +23,7 @@
 // and a sum stay two roundings, as in the NumPy restatement.
 #include <hip/hip_runtime.h>
 
+#include "../ext/wf_ext_kernels.h"
 #include "wf_rose.h"
 
 namespace {
@@ -135,17 +135,8 @@ __global__ __launch_bounds__(64) void wf_rose_rowsum_kernel(const WfRoseReduceAr
   const int e0 = blockIdx.x * rows_per_block;
   int nr = a.sh.n_rows - e0;
   nr = nr > rows_per_block ? rows_per_block : nr;
-  const float* __restrict__ src = a.power + (size_t)e0 * N;
-  const int n_load = nr * N;
-  for (int i = lane; i < n_load; i += 64) {
-    const int r = i / N, t = i - r * N;
-    rs_pw[r * stride + t] = src[i];
-  }
-  __syncthreads();
+  double sum = wf_staged_rowsum(a.power + (size_t)e0 * N, nr, N, stride, rs_pw, lane);
   if (lane < nr) {
-    const float* row = rs_pw + lane * stride;
-    double sum = 0.0;
-    for (int t = 0; t < N; ++t) sum += (double)row[t];
     const int e = e0 + lane, g = a.sh.row0 + e;
     const int s = g % S, dc = g / S;
     const int c = dc % C, d = dc / C;
@@ -233,11 +224,8 @@ extern "C" hipError_t wfk_launch_rose_layout(const WfRoseLayoutArgs* a, hipStrea
   return hipGetLastError();
 }
 extern "C" hipError_t wfk_launch_rose_rowsum(const WfRoseReduceArgs* a, hipStream_t s) {
-  const int stride = a->sh.N | 1;
-  int rpb = 32768 / (4 * stride);  // rows per block: what fits in 32 KiB of LDS, at most a row per lane
-  rpb = rpb < 1 ? 1 : (rpb > 64 ? 64 : rpb);
-  hipLaunchKernelGGL(wf_rose_rowsum_kernel, dim3((a->sh.n_rows + rpb - 1) / rpb), dim3(64), sizeof(float) * rpb * stride, s, *a, rpb,
-                     stride);
+  const WfRowsumLaunch l = wf_rowsum_launch(a->sh.n_rows, a->sh.N);
+  hipLaunchKernelGGL(wf_rose_rowsum_kernel, dim3(l.blocks), dim3(64), l.lds_bytes, s, *a, l.rows_per_block, l.stride);
   return hipGetLastError();
 }
 extern "C" hipError_t wfk_launch_rose_accumulate(const WfRoseReduceArgs* a, hipStream_t s) {

@@ -6,7 +6,8 @@
 // wf_step reads and writes.  Row 0 is the incumbent, rows 1 .. K the candidates, rows K+1 .. R-1 copies of the incumbent
 // (a pass with fewer candidates than K_max).  Slots beyond the chunk's farms (a ragged last chunk) repeat slot 0's farm
 // and write no output.
-// The slots (WfSlots), the candidate grid (WfGrid) and the order kernel's arguments are ext/wf_ext_kernels.h's.
+// The slots (WfSlots), the candidate grid (WfGrid), the order kernel's arguments and what the advance kernel shares with the
+// robust search's (WfAdvanceArgs) are ext/wf_ext_kernels.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,18 +24,8 @@ struct WfYawoptWindArgs {
   double *ews, *ewd;      // [C R] each farm's wind repeated over its rows
 };
 
-struct WfYawoptAdvanceArgs {
-  WfSlots sl;
-  int N, R;
-  double lo, hi;
-  WfGrid prev, next;  // the visit whose powers are in `power` (prev.s < 0: none, initialise from yaw0) / the one to lay out
-  int first;                // prev is the run's first visit: its incumbent power is power_init
-  const int* order;         // [C][N]
-  const float* power;       // [C][R][N] the evaluator's output for prev
-  float* yaw;               // [C][R][N] the evaluator's input for next
-  float* best;              // [C][N] best yaw so far
-  const float* yaw0;        // [n_slots][N] rows of this chunk, or null = zeros
-  float *out_yaw, *out_power, *out_init;  // rows of this chunk: [n_slots][N], [n_slots], [n_slots]; written when next.s < 0 / first
+struct WfYawoptAdvanceArgs : WfAdvanceArgs {
+  const float* power;  // [C][R][N] the evaluator's output for prev
 };
 
 extern "C" hipError_t wfk_launch_yawopt_order(const WfYawoptOrderArgs* a, hipStream_t s);

@@ -36,13 +36,14 @@ __global__ __launch_bounds__(256) void wf_yawopt_wind_kernel(const WfYawoptWindA
 
 // Dynamic LDS per wave: 32 doubles (the candidates' power sums), 32 floats (the next candidates), N floats (the slot's best
 // yaw), R N floats (the power block); the launcher sizes the region (a multiple of 16 bytes) and the waves per block.
+// The phases shared with the robust search (best yaw, winner, candidates) are ext/wf_ext_kernels.h's.
 #define YO_HDR_BYTES (WF_YAWOPT_ROWS_MAX * 8 + WF_YAWOPT_ROWS_MAX * 4)
 
 __global__ __launch_bounds__(256) void wf_yawopt_advance_kernel(const WfYawoptAdvanceArgs a, int region_bytes) {
   extern __shared__ double yo_dyn[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int slot = blockIdx.x * (blockDim.x >> 6) + wv;
-  const bool live = slot < a.sl.C;  // (wave-uniform; the barriers below are reached by every wave)
+  const bool live = slot < a.sl.C;  // (wave-uniform; the barriers below, and those of the phases, are reached by every wave)
   char* region = (char*)yo_dyn + (size_t)wv * region_bytes;
   double* sums = (double*)region;
   float* cnd = (float*)(region + WF_YAWOPT_ROWS_MAX * 8);
@@ -50,20 +51,12 @@ __global__ __launch_bounds__(256) void wf_yawopt_advance_kernel(const WfYawoptAd
   const int N = a.N, RN = a.R * a.N;
   float* pw = brow + N;
   const bool has_prev = a.prev.s >= 0, has_next = a.next.s >= 0;
-  const bool writes = live && slot < a.sl.n_slots;
-  const size_t row0 = (size_t)slot * N, blk0 = (size_t)slot * RN;
+  const size_t blk0 = (size_t)slot * RN;
 
   // ---- the slot's best yaw and the previous visit's power block -> LDS (coalesced) ----
   if (live) {
-    if (!has_prev) {
-      const size_t src = (size_t)(slot < a.sl.n_slots ? slot : 0) * N;
-      for (int t = lane; t < N; t += 64) {
-        const float v = a.yaw0 ? a.yaw0[src + t] : 0.0f;
-        brow[t] = v;
-        a.best[row0 + t] = v;
-      }
-    } else {
-      for (int t = lane; t < N; t += 64) brow[t] = a.best[row0 + t];
+    wf_advance_load_best(a, slot, lane, brow);
+    if (has_prev) {
       const int n_load = (a.prev.K + 1) * N;
       for (int i = lane; i < n_load; i += 64) pw[i] = a.power[blk0 + i];
     }
@@ -77,35 +70,9 @@ __global__ __launch_bounds__(256) void wf_yawopt_advance_kernel(const WfYawoptAd
     sums[lane] = s;
   }
   __syncthreads();
-  // ---- the winner (every lane finds it: K + 1 LDS broadcasts) ----
-  int tp = 0;
-  float newval = 0.0f;
-  if (live && has_prev) {
-    tp = a.order[row0 + a.prev.s];
-    const double p_inc = sums[0];
-    double p_best = p_inc;
-    int w = 0;
-    for (int k = 1; k <= a.prev.K; ++k) {
-      const double pk = sums[k];
-      if (pk > p_best) { p_best = pk; w = k; }  // strictly greater: the incumbent, then the lowest index, keep a tie
-    }
-    const float inc = brow[tp];
-    newval = w ? wf_grid_candidate(a.prev, (double)inc, w - 1, a.lo, a.hi) : inc;
-    if (lane == 0) {
-      if (w) a.best[row0 + tp] = newval;
-      if (writes && a.first) a.out_init[slot] = (float)p_inc;
-      if (writes && !has_next) a.out_power[slot] = (float)p_best;
-    }
-  }
-  __syncthreads();  // (every lane has read brow[tp])
-  if (live && has_prev && lane == 0) brow[tp] = newval;
-  __syncthreads();
+  wf_advance_pick(a, slot, lane, live, sums, brow);
   // ---- the next visit's candidates, then its yaw block: the best yaw, one entry replaced per candidate row ----
-  int tn = 0;
-  if (live && has_next) {
-    tn = a.order[row0 + a.next.s];
-    if (lane < a.next.K) cnd[lane] = wf_grid_candidate(a.next, (double)brow[tn], lane, a.lo, a.hi);
-  }
+  const int tn = wf_advance_candidates(a, slot, lane, live, brow, cnd);
   __syncthreads();
   if (live && has_next) {
     for (int i = lane; i < RN; i += 64) {
@@ -114,8 +81,8 @@ __global__ __launch_bounds__(256) void wf_yawopt_advance_kernel(const WfYawoptAd
       if (t == tn && k >= 1 && k <= a.next.K) v = cnd[k - 1];
       a.yaw[blk0 + i] = v;
     }
-  } else if (writes) {
-    for (int t = lane; t < N; t += 64) a.out_yaw[row0 + t] = brow[t];
+  } else if (live && slot < a.sl.n_slots) {
+    wf_advance_write_best(a, slot, lane, brow);
   }
 }
 
