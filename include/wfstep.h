@@ -399,6 +399,19 @@ int wf_get_fly_calibration(wf_handle* h, int* choice, float* ms);
  * per step the calibration measured for it (0: not timed — the rounds model decided).  Either pointer may be NULL. */
 int wf_get_mixed_launch(wf_handle* h, int* main_farms, float* mixed_ms);
 int wf_get_kernel_choice(wf_handle* h, wf_kernel_choice* c);
+/* The own-source stage of wf_step_ll_kernel (table path, no wind veer, every family but 16x1; csrc/wf_kernels_ll.hip): a target
+ * block whose turbines do not reach each other with their wakes runs its own sources' chain once per turbine, lane-parallel,
+ * instead of once per lane of the farm and one source after the other; a check inside the kernel (the far bound of
+ * wf_kernel_choice::far_skip, without which there is no stage) falls back to the sequential chain, so results are bit for
+ * bit the same with the stage on and off.  mode: -1 / 1 the blocks that pass a geometric pre-test, 0 never, 2 every block
+ * speculates (tests of the fallback).  Like a kernel choice, a change drops the current wind: set it again before the next
+ * step. */
+int wf_set_own_stage(wf_handle* h, int mode);
+ /* wf_get_own_stage: *mode as set; *spec_blocks of the *blocks (direction group, target block) pairs of the current wind may
+ * run as a stage (0 of 0 before the first step after the wind was set: the flags are written with the pair tables; the launch
+ * may still decline where the stage's LDS room would cost a resident block).  Reading the counts synchronises.  Any pointer
+ * may be NULL. */
+int wf_get_own_stage(wf_handle* h, int* mode, int* spec_blocks, int* blocks);
 /* Time the kernel families NOW for the handle's current layout / batch / wind (after wf_set_wind*), on scratch buffers with
  * zero yaw, ignoring and then refreshing the process cache; synchronises.  Lets a caller keep the timing out of its first
  * step (stream capture, asynchronous pipelines).  A configuration that has nothing to calibrate (forced kernel choice,

@@ -1,12 +1,14 @@
 """Register / spill / occupancy table of the wf_step_ll_kernel instantiations (hipcc -Rpass-analysis=kernel-resource-usage,
-the Makefile's flags for wf_kernels_ll.hip; no GPU needed).  usage: python tools/kernel_resources_ll.py [extra hipcc flags]"""
+the Makefile's flags for the two parts of wf_kernels_ll.hip: the two-slot table-path kernels without machine LICM, everything else with the default passes;
+no GPU needed).  usage: python tools/kernel_resources_ll.py [extra hipcc flags]"""
 import re, subprocess, sys
 from pathlib import Path
 src = Path(__file__).resolve().parents[1] / "wfcrl-env_amd" / "csrc"
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fno-fast-math", "-ffp-contract=off", "-fno-slp-vectorize",
+base = ["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fno-fast-math", "-ffp-contract=off", "-fno-slp-vectorize",
        "-mllvm", "-amdgpu-sched-strategy=iterative-ilp", "-c", "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null",
        str(src / "wf_kernels_ll.hip")] + sys.argv[1:]
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+out = "".join(subprocess.run(base + part, capture_output=True, text=True).stderr
+              for part in (["-DWF_LL_PART=1", "-mllvm", "-disable-machine-licm"], ["-DWF_LL_PART=2"]))
 rows, cur = [], None
 for line in out.splitlines():
     m = re.search(r"remark:\s+(.*?)\s*\[-Rpass", line)

@@ -49,3 +49,6 @@ print(f"  {'prologue/rest':14s} {(buf[4] - sum(buf[:4])) / nw:10.0f} cycles  {(b
 print("  own-source step, cycles per source (the stamps themselves add ~10 %):")
 for k, nm in zip(range(6, 11), ["A state + broadcasts", "B cbrt, Ct lookup, induction", "C transverse pass in the block", "D steering, deflection/deficit constants, log store", "E deficit / TI pass in the block"]):
     print(f"    {nm:52s} {buf[k] / nw / N:8.0f}")
+nblk = -(-N // (w.kernel_info()["lanes_per_env"] * w.kernel_info()["slots_per_lane"]))
+print(f"  own-source stage: {buf[12] / nw / nblk:.3f} of the blocks speculated, check failed in {buf[13] / nw / nblk:.3f} of the blocks "
+      f"(pre-test: {w.own_stage()})")

@@ -119,6 +119,8 @@ ABI = {
     "wf_get_kernel_info": (C.c_int, [_P, C.POINTER(KernelInfo)]),
     "wf_set_kernel_choice": (C.c_int, [_P, C.POINTER(KernelChoice)]),
     "wf_get_kernel_choice": (C.c_int, [_P, C.POINTER(KernelChoice)]),
+    "wf_set_own_stage": (C.c_int, [_P, C.c_int]),
+    "wf_get_own_stage": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "wf_get_calibration": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "wf_get_fly_calibration": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "wf_get_mixed_launch": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float)]),

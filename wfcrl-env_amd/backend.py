@@ -724,7 +724,8 @@ class WfStep:
         check(self._lib.wf_timing_end(self._h, C.byref(ms)), self._h)
         return float(ms.value)
 
-    def set_kernel_choice(self, slot=None, one_block=None, pair_table=None, fly_one_block=None, far_skip=None, calibrate=None, mixed=None):
+    def set_kernel_choice(self, slot=None, one_block=None, pair_table=None, fly_one_block=None, far_skip=None, calibrate=None, mixed=None,
+                          own_stage=None):
         """Which kernels may serve THIS handle (include/wfstep.h: wf_set_kernel_choice); None = automatic.
           slot=(G, S) or "16x5"      wf_step_kernel<G,S>
           one_block=False            never wf_step_ll_kernel;  one_block=(G, S) / "4x2" / "8": always, with that shape
@@ -733,6 +734,7 @@ class WfStep:
           far_skip=False             wf_step_ll_kernel evaluates every (source, target) pair (no far-source / far-pair skip)
           calibrate=False            the rounds model's guess stands: no timing of the kernel families before the first step
           mixed=False                always ONE launch per step (no whole-rounds + remainder split of the batch)
+          own_stage=False / "always" wf_step_ll_kernel's own-source stage (set_own_stage): never / every block speculates
         Drops the current wind: set it again before the next step."""
         def gs(v, default_s=1):
             if isinstance(v, bool):
@@ -765,6 +767,22 @@ class WfStep:
         if mixed is not None:
             c.mixed = 0 if mixed is False or mixed == 0 else -1
         check(self._lib.wf_set_kernel_choice(self._h, C.byref(c)), self._h)
+        if own_stage is not None:
+            self.set_own_stage(own_stage)
+
+    def set_own_stage(self, mode):
+        """The one-block kernel's own-source stage (include/wfstep.h: wf_set_own_stage): None / True where the kernel's
+        pre-test allows, False never, "always" every block speculates (the fallback inside the kernel then does the work where
+        the check fails: for tests).  Results are bit for bit the same in every setting.  Drops the current wind."""
+        m = {None: -1, True: 1, False: 0, "always": 2}.get(mode, mode)
+        check(self._lib.wf_set_own_stage(self._h, int(m)), self._h)
+
+    def own_stage(self) -> dict:
+        """{"mode": as set, "spec_blocks": (direction group, target block) pairs of the current wind that may run as a stage,
+        "blocks": all of them} — the counts are 0 before the first step after the wind was set; reading them synchronises."""
+        m, n, t = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self._lib.wf_get_own_stage(self._h, C.byref(m), C.byref(n), C.byref(t)), self._h)
+        return {"mode": int(m.value), "spec_blocks": int(n.value), "blocks": int(t.value)}
 
     def kernel_choice(self) -> dict:
         c = KernelChoice()

@@ -73,6 +73,7 @@ struct evaluator {
   wf_model_params model{};
   std::vector<double> tws, tct, tcp, lx, ly;
   wf_kernel_choice choice{};
+  int own_stage = -1;
   double guard = 0.0;
   hipStream_t stream = nullptr;
   evaluator() = default;

@@ -23,7 +23,7 @@ int ensure_evaluator(ext_base* x, evaluator& s, int E, int mode) {
   const bool same = s.ev && s.E == E && same_model(s.model, h->model) && s.tws == h->tws && s.tct == h->tct && s.tcp == h->tcp &&
                     s.lx.size() == n && std::equal(s.lx.begin(), s.lx.end(), h->lx.begin()) &&
                     std::equal(s.ly.begin(), s.ly.end(), h->ly.begin()) &&
-                    std::memcmp(&s.choice, &h->choice, sizeof(wf_kernel_choice)) == 0 && s.guard == h->guard_rel;
+                    std::memcmp(&s.choice, &h->choice, sizeof(wf_kernel_choice)) == 0 && s.own_stage == h->own_stage && s.guard == h->guard_rel;
   if (same) {
     if (s.stream != h->stream) {
       WFX_EV(x, s.ev, wf_set_stream(s.ev, (void*)h->stream, 1));
@@ -46,6 +46,7 @@ int ensure_evaluator(ext_base* x, evaluator& s, int E, int mode) {
   WFX_EV(x, ev, wf_set_stream(ev, (void*)h->stream, 1));
   WFX_EV(x, ev, wf_set_model(ev, &m));
   WFX_EV(x, ev, wf_set_kernel_choice(ev, &h->choice));
+  WFX_EV(x, ev, wf_set_own_stage(ev, h->own_stage));
   if (h->guard_user) WFX_EV(x, ev, wf_set_risk_guard(ev, h->guard_rel));
   WFX_EV(x, ev, wf_set_layout(ev, h->N, h->lx.data(), h->ly.data()));
   WFX_EV(x, ev, wf_set_batch(ev, E));
@@ -53,7 +54,7 @@ int ensure_evaluator(ext_base* x, evaluator& s, int E, int mode) {
   s.E = E; s.mode = mode; s.stream = h->stream;
   s.model = h->model; s.tws = h->tws; s.tct = h->tct; s.tcp = h->tcp;
   s.lx.assign(h->lx.begin(), h->lx.begin() + n); s.ly.assign(h->ly.begin(), h->ly.begin() + n);
-  s.choice = h->choice; s.guard = h->guard_rel;
+  s.choice = h->choice; s.own_stage = h->own_stage; s.guard = h->guard_rel;
   return WF_OK;
 }
 

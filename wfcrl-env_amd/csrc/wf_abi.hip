@@ -26,8 +26,8 @@ void free_batch(wf_handle* h) {
   h->d_env_moves = nullptr;
   hipFree(h->d_series_ws); hipFree(h->d_series_wd); hipFree(h->d_series_start); hipFree(h->d_ws_prev);
   hipFree(h->d_pair_tab); hipFree(h->d_pair_first); h->d_pair_tab = nullptr; h->d_pair_first = nullptr; h->pair_dirty = true;
-  hipFree(h->d_ll_tab); hipFree(h->d_ll_flag); hipFree(h->d_src_log);
-  h->d_ll_tab = h->d_src_log = nullptr; h->d_ll_flag = nullptr; h->ll_groups_cap = h->log_records_cap = 0;
+  hipFree(h->d_ll_tab); hipFree(h->d_ll_flag); hipFree(h->d_ll_own); hipFree(h->d_src_log);
+  h->d_ll_tab = h->d_src_log = nullptr; h->d_ll_flag = h->d_ll_own = nullptr; h->ll_groups_cap = h->log_records_cap = 0;
   hipFree(h->d_perm); hipFree(h->d_blk_group); hipFree(h->d_group_wd); hipFree(h->d_bins);
   h->d_perm = h->d_blk_group = h->d_bins = nullptr; h->d_group_wd = nullptr;
   h->perm_cap = h->blk_cap = h->pair_groups_cap = 0; h->n_groups = 0; h->grid_step = 0.0;
@@ -70,6 +70,8 @@ int wf_create(int device_id, wf_handle** out) {
     if (off && off[0] == '0') c.one_block = 0;
     const char* fs = getenv("WF_LL_FAR_SKIP");
     if (fs && fs[0] == '0') c.far_skip = 0;
+    const char* ost = getenv("WF_LL_OWN_STAGE");  // "0" off, "2" every block speculates
+    if (ost && (ost[0] == '0' || ost[0] == '2') && ost[1] == 0) h->own_stage = ost[0] - '0';
     const char* rr = getenv("WF_RISK_RESOLVE");  // "0": float32 only (the tests that hold the float32 kernels to their flag contract)
     if (rr && rr[0] >= '0' && rr[0] <= '2' && rr[1] == 0) h->resolve_mode = rr[0] - '0';
     const char* cal = getenv("WF_CALIBRATE");

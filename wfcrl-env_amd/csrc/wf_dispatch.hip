@@ -247,8 +247,8 @@ void apply_kernel_pick(wf_handle* h, int N, int B, bool* variant_changed) {
 // made sure no launch is in flight.
 void set_ll_shape(wf_handle* h, int G, int S) {
   if (G == h->ll_G && S == h->ll_S) return;
-  hipFree(h->d_ll_tab); hipFree(h->d_ll_flag); hipFree(h->d_src_log);
-  h->d_ll_tab = h->d_src_log = nullptr; h->d_ll_flag = nullptr; h->ll_groups_cap = h->log_records_cap = 0;
+  hipFree(h->d_ll_tab); hipFree(h->d_ll_flag); hipFree(h->d_ll_own); hipFree(h->d_src_log);
+  h->d_ll_tab = h->d_src_log = nullptr; h->d_ll_flag = h->d_ll_own = nullptr; h->ll_groups_cap = h->log_records_cap = 0;
   h->ll_G = G; h->ll_S = S; h->pair_dirty = true;
 }
 // Shared wind: (re)build the geometry-only pair table after the geometry kernel (same stream).  Returns the table
@@ -292,13 +292,24 @@ int pair_table(wf_handle* h, const float** out) {
     WF_HIP(h, wfk_launch_pair_table(&pc, (int)ng, h->d_gx, h->d_gy, h->d_pair_tab, h->d_pair_first, h->stream));
     if (h->ll_G) {  // the same records in target-block order, and the per-direction cross-block-tie flag
       if (!h->d_ll_tab || h->ll_groups_cap < ng) {
-        hipFree(h->d_ll_tab); hipFree(h->d_ll_flag);
-        h->d_ll_tab = nullptr; h->d_ll_flag = nullptr; h->ll_groups_cap = 0;
+        hipFree(h->d_ll_tab); hipFree(h->d_ll_flag); hipFree(h->d_ll_own);
+        h->d_ll_tab = nullptr; h->d_ll_flag = h->d_ll_own = nullptr; h->ll_groups_cap = 0;
         WF_HIP(h, hipMalloc(&h->d_ll_tab, sizeof(float) * ng * wfk_ll_table_floats(h->N, h->ll_G * h->ll_S)));
         WF_HIP(h, hipMalloc(&h->d_ll_flag, sizeof(int) * ng));
+        WF_HIP(h, hipMalloc(&h->d_ll_own, sizeof(int) * ng * (size_t)((h->N + h->ll_G * h->ll_S - 1) / (h->ll_G * h->ll_S))));
         h->ll_groups_cap = ng;
       }
-      WF_HIP(h, wfk_launch_pair_table_ll(&pc, h->ll_G * h->ll_S, (int)ng, h->d_gx, h->d_gy, h->d_ll_tab, h->d_ll_flag, h->stream));
+      // Pre-test of the own-source stage (wf_kernels_ll.hip): a block speculates unless two of its turbines tie in x' or one
+      // sits within reach0 + reach_k dx of the other's centre line — the far bound's shape, 6.12 sigma_y + D/4 + |deflection|,
+      // at state-independent, generous values: sigma_y from sigma_z0 = D / sqrt 8 at a growth rate taken at TI = 0.25, one
+      // diameter of yaw deflection, the model's linear offset.  (HornsRev at 7 D spacing: 5.3 D at dx = 3 D — half a column
+      // speculates at 270 deg and at the oblique directions.)  The kernel's own check decides; this only spares the fallback.
+      const double D_ = m.rotor_diameter;
+      const double reach0 = 6.12 * D_ / std::sqrt(8.0) + 0.25 * D_ + 1.0 * D_ + std::fabs(m.ad);
+      const double reach_k = 6.12 * std::max(m.ka * 0.25 + m.kb, 0.0) + std::fabs(m.bd);
+      const int own_mode = h->own_stage == 0 ? 0 : (h->own_stage == 2 ? 2 : 1);
+      WF_HIP(h, wfk_launch_pair_table_ll(&pc, h->ll_G * h->ll_S, (int)ng, h->d_gx, h->d_gy, h->d_ll_tab, h->d_ll_flag, h->d_ll_own, own_mode,
+                                         reach0, reach_k, h->stream));
       // which kernel serves which direction is decided on the device (no host round trip on the asynchronous path);
       // where the wind came through a synchronising call anyway, the flags are read back once so that a launch nobody
       // needs is not enqueued at all
@@ -430,7 +441,7 @@ int launch_step_f32(wf_handle* h, const float* yaw, float* power, float* wspd, f
     if (M) { ga.env_base = 0; ga.env_end = M; }
     if (h->ll_ties != 1)
       WF_HIP(h, wfk_launch_step_ll(h->ll_G, h->ll_S, &h->consts, h->d_tab, h->d_gidx, h->d_ws, h->d_wd, wstride, yaw, power, wspd, wdir,
-                                   load, h->B, ea, h->d_ll_tab, h->d_ll_flag, h->d_src_log,
+                                   load, h->B, ea, h->d_ll_tab, h->d_ll_flag, h->own_stage != 0 ? h->d_ll_own : nullptr, h->d_src_log,
                                    log_records, &ga, h->stream));
     if (M) {
       if (h->ll_ties != 0) {  // (a direction with a cross-block tie: the family's share is wf_step_kernel's too)
@@ -498,12 +509,12 @@ static bool calibration_due(const wf_handle* h) {
 
 // ---- process-wide cache of calibration results ----
 struct CalibKey {
-  int device, N, B, n_cu, far_skip;
+  int device, N, B, n_cu, far_skip, own_stage;
   int mixed, slot_G, slot_S;  // (a handle created with mixed = 0, or with a forced register-slot shape, must not inherit the split / the timing of one without)
   unsigned long long layout_hash, model_hash;
   bool operator<(const CalibKey& o) const {
-    return std::tie(device, N, B, n_cu, far_skip, mixed, slot_G, slot_S, layout_hash, model_hash) <
-           std::tie(o.device, o.N, o.B, o.n_cu, o.far_skip, o.mixed, o.slot_G, o.slot_S, o.layout_hash, o.model_hash);
+    return std::tie(device, N, B, n_cu, far_skip, own_stage, mixed, slot_G, slot_S, layout_hash, model_hash) <
+           std::tie(o.device, o.N, o.B, o.n_cu, o.far_skip, o.own_stage, o.mixed, o.slot_G, o.slot_S, o.layout_hash, o.model_hash);
   }
 };
 struct CalibVal {
@@ -521,7 +532,7 @@ static unsigned long long fnv(const void* p, size_t n, unsigned long long hsh = 
 }
 static CalibKey calib_key(const wf_handle* h) {
   CalibKey k{};
-  k.device = h->device; k.N = h->N; k.B = h->B; k.n_cu = h->n_cu; k.far_skip = h->choice.far_skip;
+  k.device = h->device; k.N = h->N; k.B = h->B; k.n_cu = h->n_cu; k.far_skip = h->choice.far_skip; k.own_stage = h->own_stage;
   k.mixed = h->choice.mixed != 0; k.slot_G = h->choice.slot_G; k.slot_S = h->choice.slot_S;
   k.layout_hash = fnv(h->ly.data(), sizeof(double) * h->ly.size(), fnv(h->lx.data(), sizeof(double) * h->lx.size()));
   const wf_model_params& m = h->model;  // every scalar up to the table (the pointers behind it are this handle's own copies)
@@ -890,6 +901,43 @@ int wf_set_kernel_choice(wf_handle* h, const wf_kernel_choice* c) {
   }
   // geometry, groups and tables of the current wind were laid out for the previous choice: the wind has to be set again
   h->wind_count = 0; h->shared_dir = false; h->n_groups = 0; h->grid_step = 0.0; h->series_T = 0; h->pair_dirty = true;
+  return WF_OK;
+}
+
+int wf_set_own_stage(wf_handle* h, int mode) {
+  if (!h) return WF_E_INVALID;
+  if (mode < -1 || mode > 2) return fail(h, WF_E_INVALID, "wf_set_own_stage: -1 / 1 (where the pre-test allows), 0 (never) or 2 (every block)");
+  WF_ON_DEVICE(h);
+  WF_HIP(h, hipStreamSynchronize(h->stream));
+  if (mode != h->own_stage) {  // the per-block flags are written with the pair tables and the kernel timings depend on it: as after a kernel choice
+    h->own_stage = mode;
+    if (h->N > 0) apply_kernel_pick(h, h->N, h->B, nullptr);
+    h->wind_count = 0; h->shared_dir = false; h->n_groups = 0; h->grid_step = 0.0; h->series_T = 0; h->pair_dirty = true;
+  }
+  return WF_OK;
+}
+
+int wf_get_own_stage(wf_handle* h, int* mode, int* spec_blocks, int* blocks) {
+  if (!h) return WF_E_INVALID;
+  if (mode) *mode = h->own_stage;
+  if (spec_blocks) *spec_blocks = 0;
+  if (blocks) *blocks = 0;
+  if (!spec_blocks && !blocks) return WF_OK;
+  // the per-block flags are written with the pair tables, at the first step after the wind was set
+  if (!h->ll_G || !h->d_ll_own || h->pair_dirty || h->wind_count == 0) return WF_OK;
+  WF_ON_DEVICE(h);
+  const int GS = h->ll_G * h->ll_S, nblk = (h->N + GS - 1) / GS;
+  const size_t ng = h->n_groups > 0 ? (size_t)h->n_groups : 1;
+  if (ng > h->ll_groups_cap) return WF_OK;
+  std::vector<int> f(ng * nblk);
+  WF_HIP(h, hipMemcpyAsync(f.data(), h->d_ll_own, sizeof(int) * f.size(), hipMemcpyDeviceToHost, h->stream));
+  WF_HIP(h, hipStreamSynchronize(h->stream));
+  // (what the kernel is handed: no stage without the far bound, with wind veer, or in the 16x1 family — wf_kernels_ll.hip)
+  const bool used = h->own_stage != 0 && h->consts.far_on && !h->consts.veer_on && GS <= 64 / GS;
+  int n = 0;
+  for (int v : f) n += v != 0;
+  if (spec_blocks) *spec_blocks = used ? n : 0;
+  if (blocks) *blocks = (int)f.size();
   return WF_OK;
 }
 

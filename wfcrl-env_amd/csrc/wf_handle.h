@@ -54,11 +54,12 @@ extern "C" hipError_t wfk_launch_wind_sample(int B, unsigned long long seed, con
 extern "C" size_t wfk_ll_table_floats(int N, int G);
 extern "C" int wfk_ll_farms_per_block(int G);
 extern "C" hipError_t wfk_launch_pair_table_ll(const WfPairConsts* pc, int G, int n_groups, const double* gx, const double* gy,
-                                               float* tab, int* cross_tie, hipStream_t s);
+                                               float* tab, int* cross_tie, int* own_ok, int own_mode, double reach0,
+                                               double reach_k, hipStream_t s);
 extern "C" hipError_t wfk_launch_step_ll(int G, int S, const WfConsts* c, const WfTables* tab, const int* gidx, const double* ws,
                                          const double* wd, int wind_stride, const float* yaw, float* power, float* o_ws,
                                          float* o_wd, float* load, int B, const WfEnvArgs* env, const float* ll_tab,
-                                         const int* cross_tie, float* src_log, size_t log_records,
+                                         const int* cross_tie, const int* own_ok, float* src_log, size_t log_records,
                                          const WfGroupArgs* grp, hipStream_t s);
 extern "C" hipError_t wfk_ll_func_attributes(int G, int S, int shared_speed, int table, int veer, int occ2, hipFuncAttributes* a);
 extern "C" hipError_t wfk_launch_fill(int n, double* a, hipStream_t s);  // a[1..n) = a[0]
@@ -158,6 +159,7 @@ struct wf_handle {
   int ll_G = 0, ll_S = 1;      // lanes per farm and target slots per lane of that kernel; ll_G = 0: not used
   float* d_ll_tab = nullptr;   // [groups][wfk_ll_table_floats]
   int* d_ll_flag = nullptr;    // [groups] 1 = cross-block tie
+  int* d_ll_own = nullptr;     // [groups][target blocks] 1 = the block may run its own sources as one stage (wf_pair_table_ll_kernel's pre-test)
   float* d_src_log = nullptr;  // R = launch slots x padded N records: [R][2] hot, [R][12] cold, [R][4] side (wf_device.h)
   size_t ll_groups_cap = 0, log_records_cap = 0;
   int* d_farm_tie = nullptr;   // [B] + 1: per-farm cross-block-tie flag of the per-farm geometry, then the "any" flag
@@ -175,6 +177,7 @@ struct wf_handle {
   int ll_ties = 2;             // cross-block ties of the current directions: 0 none, 1 all of them, 2 some / not read back
   // which kernels may serve this handle (wf_set_kernel_choice; the WF_* environment variables only seed it at wf_create)
   wf_kernel_choice choice{0, 0, -1, 0, 0, -1, -1, -1, -1, -1};
+  int own_stage = -1;          // wf_set_own_stage: the one-block kernel's own-source stage — -1 / 1 where the pre-test allows, 0 never, 2 every block
   int n_cu = 256;              // compute units of the handle's device (hipDeviceProp_t::multiProcessorCount)
   // per-handle calibration of the kernel family (wf_dispatch.hip: calibrate_families): whether the families have been
   // timed (or taken from the process cache / wf_set_calibration) for the current configuration

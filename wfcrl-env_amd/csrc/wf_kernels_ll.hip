@@ -49,10 +49,22 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <mutex>
 #include <type_traits>
 #include <utility>
 
 #include "wf_kernel_common.h"
+
+// Compiled in two parts (csrc/Makefile): 1 = the two-slot kernels of the table path without veer (2x2: the headline, 4x2) and
+// their launch, WITHOUT machine LICM — hoisted out of the block loop, the addresses and constants of the own-source stage
+// live through the replay, which has no register to spare: 82 spilled registers in the headline shape with the pass, none
+// and 236 registers without it —; 2 = everything else (pair table, one-slot and veer kernels of the table path, on the fly)
+// with the default passes, as before the stage: the one-slot families keep their two builds (168 registers with a private
+// segment / two waves per SIMD without), and on the fly the option would cost the 2x2 shapes 8-16 bytes of scratch.
+// 0 (A/B builds): everything in one unit.
+#ifndef WF_LL_PART
+#define WF_LL_PART 0
+#endif
 
 namespace {
 
@@ -100,6 +112,36 @@ __device__ __forceinline__ float wave_max(float v) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
+// max over the lanes of the wave that share this lane's sub = lane % G (one value per farm and sub; every lane gets its own
+// class's total): quad swap and row rotations by 4 and 8 — none changes lane % G for G <= 8 — then the four rows through LDS
+// permutes (the row broadcasts of wave_max carry lane 15's class only).  The own-source stage calls it three times per slot
+// and block, where the sequential chain calls wave_max three times per SOURCE.
+template <int G>
+__device__ __forceinline__ float sub_max(float v) {
+  auto dpp = [](float x, auto ctrl) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), decltype(ctrl)::value, 0xf, 0xf, false));
+  };
+  static_assert(G >= 2 && G <= 8, "sub_max: lanes per farm");
+  if constexpr (G < 4) v = fmaxf(v, dpp(v, std::integral_constant<int, 0x4E>{}));   // quad_perm [2,3,0,1]
+  if constexpr (G < 8) v = fmaxf(v, dpp(v, std::integral_constant<int, 0x124>{}));  // row_ror:4
+  v = fmaxf(v, dpp(v, std::integral_constant<int, 0x128>{}));                       // row_ror:8
+  v = fmaxf(v, __shfl_xor(v, 16));
+  v = fmaxf(v, __shfl_xor(v, 32));
+  return v;
+}
+
+// the value lane OS of every lane group holds, in all lanes of the group (G <= 4: a quad permutation, no LDS traffic)
+template <int G, int OS>
+__device__ __forceinline__ float group_bcast(float v, int gbase) {
+  if constexpr (G == 2) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), OS | (OS << 2) | ((2 + OS) << 4) | ((2 + OS) << 6), 0xf, 0xf, false));
+  } else if constexpr (G == 4) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), OS * 0x55, 0xf, 0xf, false));
+  } else {
+    return __shfl(v, gbase + OS);
+  }
+}
+
 // What a source leaves behind for the target blocks after its own, in registers (SrcLog) and in the per-wave source log:
 //   HOT  (8 bytes per farm):   {Gy / Gwt, Gwt} — the two circulations, all the transverse pass needs; read by EVERY later block;
 //   COLD (48 bytes per farm):  three float4 {sy0d, sz0d, sM, tan_th0} {sy0v, x0d, kyd, pj} {x0v, kyv, +-ch_pref, 1 / x0v} —
@@ -128,22 +170,36 @@ struct SrcLog {
 struct ColdRec { float4 a, b, c; };  // the cold part as stored: {sy0d, sz0d, sM, tan_th0} {sy0v, x0d, kyd, pj} {x0v, kyv, ch_pref, ix0v}
 static_assert(WF_LOG_HOT_FLOATS == 2 && WF_LOG_COLD_FLOATS == 12, "source log record");
 struct WfLogSide { float TI0, TI1, TI2, dTI; };  // the source's column TIs before mixing, the yaw-added-recovery increment
+// The source chain in parts, shared by the sequential own-source step (every lane of the farm's group holds the source) and the
+// own-source stage (every lane holds its OWN turbine): what follows from the deficit sums alone (src_part_b), and what needs the
+// transverse velocities at the source as well (src_part_d)
+struct SrcB { float ubar, ct, a, Gwr, Gy, Gwt; unsigned risk; };
+struct SrcD { SrcLog Sc; WfLogSide X; bool split; float x0num_d, pfac, b2om_d; };
 
 }  // namespace
 
+#if WF_LL_PART != 1
 // ---------------------------------------------------------------------------------------------
 // Pair table in target-block order.  One thread per (source i, target t); the record is the one wf_pair_table_kernel
 // writes (wf_device.h: WF_PAIR_*), at  block_offset(J) + (i * G + t - J G) * 44,  J = t / G, for i < (J + 1) G.
 // ---------------------------------------------------------------------------------------------
 __global__ void wf_pair_table_ll_kernel(const WfPairConsts pc, int G, const double* __restrict__ gx,
                                         const double* __restrict__ gy, float* __restrict__ tab, size_t group_floats,
-                                        int* __restrict__ cross_tie) {
+                                        int* __restrict__ cross_tie, int* __restrict__ own_ok, int own_mode, double reach0,
+                                        double reach_k) {
   const int i = blockIdx.x, t = threadIdx.x, grp = blockIdx.y;
   const int nblk = (pc.N + G - 1) / G;
   if (t >= nblk * G) return;
   gx += (size_t)grp * pc.N;
   gy += (size_t)grp * pc.N;
   const int J = t / G;
+  // Pre-test of the own-source stage (wf_step_ll_kernel): own_ok[grp][J], preset to 1, is cleared when two turbines of block J
+  // tie in x' or sit within a generous, state-independent lateral reach of each other's wake — such a block runs the
+  // sequential chain at once instead of speculating and falling back.  A heuristic only: the kernel's own check decides.
+  if (own_mode == 1 && i >= J * G && i < t && t < pc.N) {
+    const double dx = gx[t] - gx[i], dy = gy[t] - gy[i];
+    if (dx <= 0.0 || fabs(dy) < reach0 + reach_k * dx) own_ok[(size_t)grp * nblk + J] = 0;
+  }
   if (i >= (J + 1) * G) {  // a source of a later block: never applied to this target — unless it ties with it in x'
     if (t < pc.N && gx[t] - gx[i] >= 0.0) atomicOr(&cross_tie[grp], 1);
     return;
@@ -155,15 +211,22 @@ __global__ void wf_pair_table_ll_kernel(const WfPairConsts pc, int G, const doub
 extern "C" size_t wfk_ll_table_floats(int N, int G) { return wf_ll_block_offset((N + G - 1) / G, N, G); }
 
 extern "C" hipError_t wfk_launch_pair_table_ll(const WfPairConsts* pc, int G, int n_groups, const double* gx, const double* gy,
-                                               float* tab, int* cross_tie, hipStream_t s) {
+                                               float* tab, int* cross_tie, int* own_ok, int own_mode, double reach0,
+                                               double reach_k, hipStream_t s) {
   const int nblk = (pc->N + G - 1) / G;
   const int threads = ((nblk * G + 63) / 64) * 64;
   hipError_t e = hipMemsetAsync(cross_tie, 0, sizeof(int) * (size_t)n_groups, s);
   if (e != hipSuccess) return e;
+  // own_mode: 0 no block speculates, 1 the blocks that pass the pre-test, 2 every block (tests of the fallback)
+  e = hipMemsetD32Async((hipDeviceptr_t)own_ok, own_mode ? 1 : 0, (size_t)n_groups * nblk, s);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(wf_pair_table_ll_kernel, dim3(pc->N, n_groups), dim3(threads), 0, s, *pc, G, gx, gy, tab,
-                     wfk_ll_table_floats(pc->N, G), cross_tie);
+                     wfk_ll_table_floats(pc->N, G), cross_tie, own_ok, own_mode, reach0, reach_k);
   return hipGetLastError();
 }
+#else
+extern "C" size_t wfk_ll_table_floats(int N, int G);
+#endif  // WF_LL_PART != 1
 
 // ---------------------------------------------------------------------------------------------
 // The farm step, one target block at a time
@@ -177,7 +240,7 @@ extern "C" hipError_t wfk_launch_pair_table_ll(const WfPairConsts* pc, int G, in
 // registers), nothing is staged and no barrier is needed after the start.  MC1 (on the fly only): compile-time skip of
 // the ground-mirror vortex cores that are exactly 1.0f in float32 (WfConsts::mirror_core_n <= 1).
 #ifdef WF_LL_STAMP  // debug build (tools/ll_stamps.py): wave cycles per phase, summed over the launch
-__device__ unsigned long long wf_ll_stamp[16];
+static __device__ unsigned long long wf_ll_stamp[16];
 #define WF_T(v) const unsigned long long v = __builtin_readcyclecounter()
 #define WF_ACC(k, a, b) st_acc[k] += (b) - (a)
 #else
@@ -201,16 +264,19 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
     float* __restrict__ o_ws, float* __restrict__ o_wd, float* __restrict__ o_load, int B, const WfEnvArgs ea,
     const float* __restrict__ ll_tab, size_t group_floats, const int* __restrict__ cross_tie, float* __restrict__ src_log,
     size_t log_cold_offset, size_t log_side_offset, int n_pad, const WfGroupArgs ga, const double* __restrict__ gx,
-    const double* __restrict__ gy) {
+    const double* __restrict__ gy, const int* __restrict__ own_ok) {
   constexpr int EPW = 64 / G;   // farms per wave
   constexpr int GS = G * S;     // turbines per block
   constexpr int CH = 64 / GS;   // sources per staged chunk (64 records)
+  // The own-source stage (own_stage below): table path without veer, a block's sources within ONE staged chunk (GS <= CH:
+  // every family but 16x1, whose sixteen sources span four chunks and keep the sequential chain)
+  constexpr bool STAGE = TAB && !VEER && GS <= CH;
   constexpr int CHUNK_FLOATS = TAB ? 64 * WF_PAIR_STRIDE : 4;
   __shared__ TableLds T;
   __shared__ __attribute__((aligned(16))) float prow[2][CHUNK_FLOATS];
   __shared__ unsigned risk_lds[WPB][EPW];
   __shared__ int env_lds[WPB][EPW];  // farm index of every farm slot of the block (-1 - index: results dropped)
-  extern __shared__ __attribute__((aligned(16))) float yaw_lds[];  // [WPB][n_pad] float4 far bounds, then (table path) [WPB][2][HOT_F4] float4 hot records
+  extern __shared__ __attribute__((aligned(16))) float yaw_lds[];  // [WPB][n_pad] float4 far bounds, then (table path) [WPB][2][HOT_F4] float4 hot records, then (own-source stage) [WPB][9 S][64] float2 {V, W} of the block
 
   if (ga.res_zero && blockIdx.x == 0 && threadIdx.x == 0) *ga.res_zero = 0;  // the re-solve counter of the NEXT step (before any early return)
   int grp = 0;
@@ -624,7 +690,7 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
   float psum = 0.0f, lsum = 0.0f;  // per-lane partial sums for the fused reward
   const int n_real = ga.n_real ? ga.n_real[env] : N;  // turbines the farm really has (padded layouts: WfGroupArgs)
 #ifdef WF_LL_STAMP
-  unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long st_acc[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   WF_T(st_begin);
 #endif
   int q = 0;                        // running chunk index (LDS buffer q & 1)
@@ -647,7 +713,14 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
   // wave-instructions (a run shorter than 1 KiB reads on into the following records, which nobody looks at).
   constexpr int HOT_INSTR = (CH / 2) * EPW * 16 >= 1024 ? (CH / 2) * EPW * 16 / 1024 : 1;  // wave-instructions per chunk
   constexpr int HOT_F4 = HOT_INSTR * 64;                                                   // float4 per wave and buffer
-  float4* const hotL = reinterpret_cast<float4*>(yaw_lds) + (size_t)WPB * n_pad + (size_t)wave * (2 * HOT_F4);
+  // (own-source stage: the wave's two hot buffers are idle while a block's own sources run — the last chunk of a block stages no
+  // hot records, the next block's are staged behind its sources — so the stage's copy of V and W lies over them; the launch
+  // widens a wave's region to 9 S x 64 float2 where that is more)
+  constexpr int SAVE_F4 = 9 * S * 32;
+  const int wave_f4 = (STAGE && own_ok && SAVE_F4 > 2 * HOT_F4) ? SAVE_F4 : 2 * HOT_F4;
+  float4* const hotL = reinterpret_cast<float4*>(yaw_lds) + (size_t)WPB * n_pad + (size_t)wave * wave_f4;
+  // own-source stage: the block's V and W as they stand in front of its own sources, for the fallback (own_ok: the launch made room)
+  float2* const saveL = reinterpret_cast<float2*>(hotL);
   auto stage_hot = [&](int qq, int i_first) {  // the hot records of sources i_first .. i_first + CH - 1 -> buffer qq & 1
     const char* g0 = reinterpret_cast<const char*>(reinterpret_cast<const float4*>(log_hot) + (size_t)(i_first >> 1) * EPW);
     char* l0 = reinterpret_cast<char*>(hotL + (qq & 1) * HOT_F4);
@@ -680,6 +753,132 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
     return R;
   };
   float* const logx = src_log + log_side_offset + (size_t)slot * n_pad * WF_LOG_SIDE_FLOATS;
+  // B. circulations [A.3-1, A.3-4] of a source with rotor-grid cube sum m3, cos / sin of the commanded yaw cg / sg
+  auto src_part_b = [&](float m3, float cg, float sg) {
+    SrcB b;
+    b.ubar = fcbrt_pos(m3 * (1.0f / 9.0f));
+    b.ct = table_ct(c, T, b.ubar, b.risk) * cg;
+    const float sq1 = fsqrt(1.0f - b.ct * cg);
+    b.a = 0.5f * b.ct * frcp(1.0f + sq1);
+    b.Gwr = c.gam_wr * (b.a - b.a * b.a) * b.ubar;
+    const float scg = sg * cg * c.sw_tv;
+    b.Gy = scg * b.ct * ws;
+    b.Gwt = b.Gwr * c.sw_tv;
+    return b;
+  };
+  // B2. steering + deflection constants [A.3-2, A.3-3], D. yaw-added recovery [A.3-5] and deficit constants [A.3-6]: Vmean the
+  // source's mean V BEFORE its own transverse pass, vbar / wbar its mean V / W after it, TIs its column TIs.  any_of: whether some
+  // farm's copy of THIS source meets a condition (the libm branch of the arcsine is taken per source, not per lane)
+  auto src_part_d = [&](const SrcB& b, float Vmean, float vbar, float wbar, const float* TIs, float yaw_i, float cg, float sg,
+                        auto any_of) {
+    SrcD d;
+    SrcLog& Sc = d.Sc;
+    const float ubar = b.ubar, ct = b.ct, a = b.a, Gwr = b.Gwr;
+    Sc.Gy = b.Gy;
+    Sc.Gwt = b.Gwt;
+    const float gt = c.gam_top * ws * ct, gb = c.gam_bot * ws * ct;
+    float val = c.sw_steer * (Vmean - Gwr * c.ks_core) * frcp(gt * c.ks_top - gb * c.ks_bot);
+    val = fminf(fmaxf(val, -1.0f), 1.0f);
+    const float asv = any_of(fabsf(val) > 0.3f) ? asinf(val) : asin_small(val);
+    const float gd = -(yaw_i * kDeg2Rad + 0.5f * asv);
+    const float c2h = fsqrt(fmaxf(fmaf(-val, val, 1.0f), 0.0f));
+    const float chh = fsqrt(0.5f * (1.0f + c2h));
+    const float shh = 0.5f * val * frcp(chh);
+    const float cgd = fmaf(cg, chh, -sg * shh);
+    const float s_cc = fsqrt(1.0f - ct * cgd), s_c = fsqrt(1.0f - ct);
+    const float om_scc = ct * cgd * frcp(1.0f + s_cc);
+    const float om_sc = ct * frcp(1.0f + s_c);
+    Sc.sM = fsqrt(ct);
+    const float E0 = fmaf(om_sc, om_sc, fmaf(-c.e0c1, om_sc, c.e0c2));
+    Sc.sz0d = 0.5f * c.D * fsqrt((1.0f + s_cc) * frcp(2.0f * (1.0f + s_c)));
+    Sc.sy0d = Sc.sz0d * cgd;
+    if constexpr (VEER) Sc.sy0d *= c.cos_veer;
+    const float th0 = c.dm03 * gd * frcp(cgd) * om_scc;
+    {
+      const float t2 = th0 * th0;
+      const float poly = th0 * fmaf(t2, fmaf(t2, fmaf(t2, fmaf(t2, fmaf(t2, 0.0088632355f, 0.0218694885f), 0.0539682540f),
+                                                        0.1333333333f), 0.3333333333f), 1.0f);
+      Sc.tan_th0 = poly;
+      if (__any(fabsf(th0) > 0.35f)) {
+        const float rev = th0 * 0.15915494309189535f;
+        const float hw = __builtin_amdgcn_sinf(rev) * frcp(__builtin_amdgcn_cosf(rev));
+        Sc.tan_th0 = (fabsf(th0) > 0.35f) ? hw : poly;
+      }
+    }
+    d.pfac = th0 * E0 * (1.0f / 5.2f) * fsqrt(Sc.sy0d * Sc.sz0d * frcp(ct)) * kLn2;
+    d.x0num_d = c.D * cgd * (1.0f + s_cc) * (1.0f / 1.41421356237f);
+    const float I0 = TIs[0];
+    const float uI = ubar * I0;
+    const float mix2 = (vbar * vbar + wbar * wbar) * (1.0f / 3.0f);
+    const float inv_ubar = frcp(ubar);
+    const float Itot = fsqrt(fmaf(uI, uI, mix2)) * inv_ubar;
+    const float Imix = mix2 * inv_ubar * inv_ubar * frcp(Itot + I0);
+    WfLogSide& X = d.X;
+    X.dTI = c.gch_gain * Imix;
+    Sc.sy0v = c.sz0v * cg;
+    if constexpr (VEER) Sc.sy0v *= c.cos_veer;
+    Sc.snw = c.near_c * fsqrt(0.5f * ct);
+    Sc.kdef = ct * cg * c.kdef;
+    Sc.ch_pref = c.ch_c * fexp2(c.ch_ai * flog2(a));
+    const float x0num_v = c.D * cg * (1.0f + s_c) * (1.0f / 1.41421356237f);
+    const float b2om = c.beta2 * om_sc;
+    d.b2om_d = c.beta2_d * om_sc;
+    Sc.x0d = d.x0num_d * frcp(fmaf(c.alpha4_d, TIs[0], d.b2om_d));
+    Sc.kyd = fmaf(c.ka_d, TIs[0], c.kb_d);
+    Sc.pj = d.pfac * frcp(Sc.kyd);
+    Sc.x0v = x0num_v * frcp(fmaf(c.alpha4, TIs[0] + X.dTI, b2om));
+    Sc.kyv = fmaf(c.ka, TIs[0] + X.dTI, c.kb);
+    X.TI0 = TIs[0]; X.TI1 = TIs[1]; X.TI2 = TIs[2];
+    d.split = !((TIs[0] == TIs[1]) && (TIs[1] == TIs[2]));
+    Sc.ch_pref = d.split ? -Sc.ch_pref : Sc.ch_pref;  // the flag travels in the sign
+    Sc.ix0v = frcp(Sc.x0v);
+    Sc.inv_s0d = frcp(Sc.sy0d * Sc.sz0d);
+    Sc.d0 = Sc.tan_th0 * Sc.x0d;
+    return d;
+  };
+  // the source's log records (the caller picks the lanes that write: one per farm)
+  auto log_store = [&](int i, const SrcD& d) {
+    const SrcLog& Sc = d.Sc;
+    // (Gwt == 0: transverse velocities switched off, Gy is 0 as well)
+    log_hot[hot_index(i)] = make_float2(Sc.Gwt != 0.0f ? Sc.Gy * frcp(Sc.Gwt) : 0.0f, Sc.Gwt);
+    float4* lp = log_cold + (size_t)i * (3 * EPW);           // EPW * 16 each
+    lp[0] = make_float4(Sc.sy0d, Sc.sz0d, Sc.sM, Sc.tan_th0);
+    lp[EPW] = make_float4(Sc.sy0v, Sc.x0d, Sc.kyd, Sc.pj);
+    lp[2 * EPW] = make_float4(Sc.x0v, Sc.kyv, Sc.ch_pref, Sc.ix0v);
+    if (d.split) *reinterpret_cast<float4*>(logx + (size_t)i * WF_LOG_SIDE_FLOATS) = make_float4(d.X.TI0, d.X.TI1, d.X.TI2, d.X.dTI);
+  };
+  // Far bound of a source for THIS farm (the caller takes the maximum over the farms of the wave): for every dx >= 0
+  //   sigma_y(dx) <= max(kyv dx + (sy0v - kyv x0v), max(snw, sy0v))   [far wake: equality; near wake: sigma_y lies
+  //                                                                    between snw and sy0v]
+  //   |deflection - (ad + bd dx)| <= |tan_th0 x0d| + 2.2 |pj|         [near wake: |dx tan_th0| <= |tan_th0| x0d; far
+  //        wake: d0 + pj log2(arg) with arg rising from 1 at sigma = sigma_0 to (1.6 + sM) / (1.6 - sM), whose log2
+  //        is <= 2.115 for sM = sqrt(ct) <= 1 — ct is clipped to 0.9999 — and the wake only widens: kyd >= 0]
+  // hold; with per-column constants (split TI) the growth rate is taken at the largest column TI, the near-wake
+  // length and the log prefactor at the smallest (both fall with TI), and the near-wake credit is dropped.
+  // (wind veer: the Gaussian is rotated — r = a yy^2 - 2 b yy zz + c zz^2 >= yy^2 / (2 sigma_max^2), the smaller
+  // eigenvalue of the form — so the bound takes the larger of the two widths: sigma_z, which starts from sz0v >= sy0v and
+  // grows at the same rate)
+  auto src_far_bound = [&](const SrcD& d, const float* TIs, float& k6, float& b6, float& n6) {
+    const SrcLog& Sc = d.Sc;
+    const float s0 = VEER ? c.sz0v : Sc.sy0v;
+    float kyv_m = Sc.kyv, bb = fmaf(-Sc.kyv, Sc.x0v, s0);
+    float db = fabsf(Sc.tan_th0 * Sc.x0d) + 2.2f * fabsf(Sc.pj);
+    if (__any(d.split)) {
+      const float TImax = fmaxf(TIs[0], fmaxf(TIs[1], TIs[2])), TImin = fminf(TIs[0], fminf(TIs[1], TIs[2]));
+      const float x0d_m = d.x0num_d * frcp(fmaf(c.alpha4_d, TImin, d.b2om_d));
+      const float pj_m = d.pfac * frcp(fmaf(c.ka_d, TImin, c.kb_d));
+      kyv_m = fmaf(c.ka, TImax + d.X.dTI, c.kb);
+      bb = d.split ? s0 : bb;
+      db = fabsf(Sc.tan_th0 * x0d_m) + 2.2f * fabsf(pj_m);
+    }
+    const float dbo = db + c.off[2];
+    k6 = c.far_k * kyv_m;
+    b6 = fmaf(c.far_k, bb, dbo);
+    n6 = fmaf(c.far_k, fmaxf(Sc.snw, s0), dbo);
+  };
+  auto within_bound = [&](const float4 bnd, float dx, float dy) {  // lin = ad + bd dx: the model's linear deflection offset
+    return fabsf(dy) < fmaxf(fmaf(bnd.x, dx, bnd.y), bnd.z) + fabsf(fmaf(c.bd, dx, c.ad));
+  };
   // caller's (unsorted) index of this lane's turbines — the current block's, the next block's, the one after — and the next
   // block's commanded yaw: indices are fetched two blocks ahead, the yaw behind them one block ahead
   int oidx[S], oidx_nx[S], oidx_n2[S];
@@ -776,18 +975,8 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
       // B. circulations [A.3-1, A.3-4]
       WF_T(so_1);
       WF_ACC(6, so_0, so_1);
-      SrcLog Sc;
-      const float ubar = fcbrt_pos(m3 * (1.0f / 9.0f));
-      unsigned trisk;
-      const float ct = table_ct(c, T, ubar, trisk) * cg;
-      if (trisk) atomicOr(&risk_lds[wave][eiw], trisk);
-      const float sq1 = fsqrt(1.0f - ct * cg);
-      const float a = 0.5f * ct * frcp(1.0f + sq1);
-      const float Gwr = c.gam_wr * (a - a * a) * ubar;
-      const float gt = c.gam_top * ws * ct, gb = c.gam_bot * ws * ct;
-      const float scg = sg * cg * c.sw_tv;
-      Sc.Gy = scg * ct * ws;
-      Sc.Gwt = Gwr * c.sw_tv;
+      const SrcB Bs = src_part_b(m3, cg, sg);
+      if (Bs.risk) atomicOr(&risk_lds[wave][eiw], Bs.risk);
       WF_T(so_2);
       WF_ACC(7, so_1, so_2);
       // C. pass 1: the source's own slot (lanes upstream of it carry dx < 0 in their record), every later slot of the
@@ -805,13 +994,13 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
           ex[p] = *reinterpret_cast<const float4*>(rec + WF_PAIR_DX);  // {dx, dy, tipow, decision bits}
           const bool act1 = (p > ps) ? tvalid[p] : (ex[p].x >= 0.0f);
           if (p >= ps || __any(act1)) {
-            if (act1) apply_tab(PP, reinterpret_cast<const float4*>(rec), Sc.Gy, Sc.Gwt);
+            if (act1) apply_tab(PP, reinterpret_cast<const float4*>(rec), Bs.Gy, Bs.Gwt);
           }
         } else {
           ex[p] = fly_record(PP, xi_d, yi_d);
           const bool act1 = (p > ps) ? tvalid[p] : (ex[p].x >= 0.0f);
           if (p >= ps || __any(act1)) {
-            if (act1) apply_fly(PP, ex[p].x, ex[p].y, Sc.Gy, Sc.Gwt);
+            if (act1) apply_fly(PP, ex[p].x, ex[p].y, Bs.Gy, Bs.Gwt);
           }
         }
       };
@@ -823,105 +1012,21 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
       for (int k2 = 0; k2 < 9; ++k2) { vbar += V[ps][k2]; wbar += W[ps][k2]; }
       vbar = __shfl(vbar, src) * (1.0f / 9.0f);
       wbar = __shfl(wbar, src) * (1.0f / 9.0f);
-      // B2. steering + deflection constants [A.3-2, A.3-3]
-      float val = c.sw_steer * (Vmean - Gwr * c.ks_core) * frcp(gt * c.ks_top - gb * c.ks_bot);
-      val = fminf(fmaxf(val, -1.0f), 1.0f);
-      const float asv = __any(fabsf(val) > 0.3f) ? asinf(val) : asin_small(val);
-      const float gd = -(yaw_i * kDeg2Rad + 0.5f * asv);
-      const float c2h = fsqrt(fmaxf(fmaf(-val, val, 1.0f), 0.0f));
-      const float chh = fsqrt(0.5f * (1.0f + c2h));
-      const float shh = 0.5f * val * frcp(chh);
-      const float cgd = fmaf(cg, chh, -sg * shh);
-      const float s_cc = fsqrt(1.0f - ct * cgd), s_c = fsqrt(1.0f - ct);
-      const float om_scc = ct * cgd * frcp(1.0f + s_cc);
-      const float om_sc = ct * frcp(1.0f + s_c);
-      Sc.sM = fsqrt(ct);
-      const float E0 = fmaf(om_sc, om_sc, fmaf(-c.e0c1, om_sc, c.e0c2));
-      Sc.sz0d = 0.5f * c.D * fsqrt((1.0f + s_cc) * frcp(2.0f * (1.0f + s_c)));
-      Sc.sy0d = Sc.sz0d * cgd;
-      if constexpr (VEER) Sc.sy0d *= c.cos_veer;
-      const float th0 = c.dm03 * gd * frcp(cgd) * om_scc;
-      {
-        const float t2 = th0 * th0;
-        const float poly = th0 * fmaf(t2, fmaf(t2, fmaf(t2, fmaf(t2, fmaf(t2, 0.0088632355f, 0.0218694885f), 0.0539682540f),
-                                                          0.1333333333f), 0.3333333333f), 1.0f);
-        Sc.tan_th0 = poly;
-        if (__any(fabsf(th0) > 0.35f)) {
-          const float rev = th0 * 0.15915494309189535f;
-          const float hw = __builtin_amdgcn_sinf(rev) * frcp(__builtin_amdgcn_cosf(rev));
-          Sc.tan_th0 = (fabsf(th0) > 0.35f) ? hw : poly;
-        }
-      }
-      const float pfac = th0 * E0 * (1.0f / 5.2f) * fsqrt(Sc.sy0d * Sc.sz0d * frcp(ct)) * kLn2;
-      const float x0num_d = c.D * cgd * (1.0f + s_cc) * (1.0f / 1.41421356237f);
-      // D. yaw-added recovery [A.3-5] and deficit constants [A.3-6]
-      const float I0 = TIs[0];
-      const float uI = ubar * I0;
-      const float mix2 = (vbar * vbar + wbar * wbar) * (1.0f / 3.0f);
-      const float inv_ubar = frcp(ubar);
-      const float Itot = fsqrt(fmaf(uI, uI, mix2)) * inv_ubar;
-      const float Imix = mix2 * inv_ubar * inv_ubar * frcp(Itot + I0);
-      WfLogSide X;
-      X.dTI = c.gch_gain * Imix;
+      // B2. steering + deflection constants; D. yaw-added recovery and deficit constants (src_part_d)
+      const SrcD Ds = src_part_d(Bs, Vmean, vbar, wbar, TIs, yaw_i, cg, sg, [](bool f) { return __any(f) != 0; });
+      const SrcLog& Sc = Ds.Sc;
+      const WfLogSide& X = Ds.X;
       if (lane == src) {
 #pragma unroll
         // (the stored TI: max(ambient, TI + dTI), as FLORIS' maximum over all turbines at the end of the source step leaves it —
         // see wf_kernels.hip; the passes of this source go on with TI + dTI)
         for (int j = 0; j < 3; ++j) TI[ps][j] = fmaxf(TI[ps][j] + X.dTI, amb0);
       }
-      Sc.sy0v = c.sz0v * cg;
-      if constexpr (VEER) Sc.sy0v *= c.cos_veer;
-      Sc.snw = c.near_c * fsqrt(0.5f * ct);
-      Sc.kdef = ct * cg * c.kdef;
-      Sc.ch_pref = c.ch_c * fexp2(c.ch_ai * flog2(a));
-      const float x0num_v = c.D * cg * (1.0f + s_c) * (1.0f / 1.41421356237f);
-      const float b2om = c.beta2 * om_sc, b2om_d = c.beta2_d * om_sc;
-      Sc.x0d = x0num_d * frcp(fmaf(c.alpha4_d, TIs[0], b2om_d));
-      Sc.kyd = fmaf(c.ka_d, TIs[0], c.kb_d);
-      Sc.pj = pfac * frcp(Sc.kyd);
-      Sc.x0v = x0num_v * frcp(fmaf(c.alpha4, TIs[0] + X.dTI, b2om));
-      Sc.kyv = fmaf(c.ka, TIs[0] + X.dTI, c.kb);
-      X.TI0 = TIs[0]; X.TI1 = TIs[1]; X.TI2 = TIs[2];
-      const bool split = !((TIs[0] == TIs[1]) && (TIs[1] == TIs[2]));
-      Sc.ch_pref = split ? -Sc.ch_pref : Sc.ch_pref;  // the flag travels in the sign
-      Sc.ix0v = frcp(Sc.x0v);
-      Sc.inv_s0d = frcp(Sc.sy0d * Sc.sz0d);
-      Sc.d0 = Sc.tan_th0 * Sc.x0d;
       // the later blocks replay this source from the log
       if (J + 1 < nblk) {
-        if (sub == 0) {
-          // (Gwt == 0: transverse velocities switched off, Gy is 0 as well)
-          log_hot[hot_index(i)] = make_float2(Sc.Gwt != 0.0f ? Sc.Gy * frcp(Sc.Gwt) : 0.0f, Sc.Gwt);
-          float4* lp = log_cold + (size_t)i * (3 * EPW);           // EPW * 16 each
-          lp[0] = make_float4(Sc.sy0d, Sc.sz0d, Sc.sM, Sc.tan_th0);
-          lp[EPW] = make_float4(Sc.sy0v, Sc.x0d, Sc.kyd, Sc.pj);
-          lp[2 * EPW] = make_float4(Sc.x0v, Sc.kyv, Sc.ch_pref, Sc.ix0v);
-          if (split) *reinterpret_cast<float4*>(logx + (size_t)i * WF_LOG_SIDE_FLOATS) = make_float4(X.TI0, X.TI1, X.TI2, X.dTI);
-        }
-        // Far bound of this source over the farms of the wave (far_bound): for every dx >= 0 and every farm
-        //   sigma_y(dx) <= max(kyv dx + (sy0v - kyv x0v), max(snw, sy0v))   [far wake: equality; near wake: sigma_y lies
-        //                                                                    between snw and sy0v]
-        //   |deflection - (ad + bd dx)| <= |tan_th0 x0d| + 2.2 |pj|         [near wake: |dx tan_th0| <= |tan_th0| x0d; far
-        //        wake: d0 + pj log2(arg) with arg rising from 1 at sigma = sigma_0 to (1.6 + sM) / (1.6 - sM), whose log2
-        //        is <= 2.115 for sM = sqrt(ct) <= 1 — ct is clipped to 0.9999 — and the wake only widens: kyd >= 0]
-        // hold; with per-column constants (split TI) the growth rate is taken at the largest column TI, the near-wake
-        // length and the log prefactor at the smallest (both fall with TI), and the near-wake credit is dropped.
-        // (wind veer: the Gaussian is rotated — r = a yy^2 - 2 b yy zz + c zz^2 >= yy^2 / (2 sigma_max^2), the smaller
-        // eigenvalue of the form — so the bound takes the larger of the two widths: sigma_z, which starts from sz0v >= sy0v and
-        // grows at the same rate)
-        const float s0 = VEER ? c.sz0v : Sc.sy0v;
-        float kyv_m = Sc.kyv, bb = fmaf(-Sc.kyv, Sc.x0v, s0);
-        float db = fabsf(Sc.tan_th0 * Sc.x0d) + 2.2f * fabsf(Sc.pj);
-        if (__any(split)) {
-          const float TImax = fmaxf(TIs[0], fmaxf(TIs[1], TIs[2])), TImin = fminf(TIs[0], fminf(TIs[1], TIs[2]));
-          const float x0d_m = x0num_d * frcp(fmaf(c.alpha4_d, TImin, b2om_d));
-          const float pj_m = pfac * frcp(fmaf(c.ka_d, TImin, c.kb_d));
-          kyv_m = fmaf(c.ka, TImax + X.dTI, c.kb);
-          bb = split ? s0 : bb;
-          db = fabsf(Sc.tan_th0 * x0d_m) + 2.2f * fabsf(pj_m);
-        }
-        const float dbo = db + c.off[2];
-        float k6 = c.far_k * kyv_m, b6 = fmaf(c.far_k, bb, dbo), n6 = fmaf(c.far_k, fmaxf(Sc.snw, s0), dbo);
+        if (sub == 0) log_store(i, Ds);
+        float k6, b6, n6;
+        src_far_bound(Ds, TIs, k6, b6, n6);
         k6 = wave_max<G>(k6);
         b6 = wave_max<G>(b6);
         n6 = wave_max<G>(n6);
@@ -942,6 +1047,132 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
       WF_ACC(10, so_4, so_5);
       __builtin_amdgcn_s_setprio(0);
     };
+
+    // ---- the block's own sources as ONE lane-parallel stage (table path, no veer).  The sequential chain above runs every
+    // source's arithmetic in all G lanes of the farm, one source after the other.  A block's turbines usually do not reach each
+    // other with their wakes (HornsRev: half a column, 7 D apart across the wind); then every deficit / turbulence call inside
+    // the block is the far skip's no-op, a member's deficit sums and TI are final when the block's replay ends, and all that
+    // still couples the members is the transverse pass.  So: every lane runs the chain ONCE, for its own turbines, from its own
+    // registers (parts B, then D); in between the transverse pass walks the members in their order as before, the circulations
+    // broadcast from the owner lane, which notes its mean V before and its mean V / W after its own pass; the owner writes the
+    // log.  Then one lane per ordered member pair tests the pair against the source's far bound: no pair within reach — the
+    // stage stands, bit for bit what the chain computes.  Otherwise V and W are put back from LDS and the chain runs.
+    // buf: the staged chunk, k0: the chunk record of the block's first source, nm: the block's sources.  Returns false when
+    // the chain has to run (state restored). ---------------------------------------------------------------------------
+    auto own_stage = [&](const float* buf, int k0, int nm) -> bool {
+      if constexpr (STAGE) {
+        __builtin_amdgcn_s_setprio(3);
+        // (what the stage derives from the lane index is derived HERE, from an opaque copy: hoisted out of the block loop these
+        // values — addresses, masks — would live through the replay, which has no register to spare)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int sub = ln & (G - 1), gbase = ln & ~(G - 1), eiw = ln / G;
+        float2* const sv = saveL + ln;
+#pragma unroll
+        for (int p = 0; p < S; ++p)
+#pragma unroll
+          for (int k2 = 0; k2 < 9; ++k2) sv[(p * 9 + k2) * 64] = make_float2(V[p][k2], W[p][k2]);
+        SrcB Bm[S];
+        float Vmean[S], vbar[S], wbar[S];
+#pragma unroll
+        for (int p = 0; p < S; ++p) {
+          Bm[p] = src_part_b(cube_sum(esq[p]), cg_t[p], sg_t[p]);
+          Vmean[p] = 0.0f; vbar[p] = 0.0f; wbar[p] = 0.0f;
+        }
+        // the transverse pass, member by member (as part C of the chain: the member's own slot from its record's dx on, every
+        // later slot, and the lanes of earlier slots that tie with it in x')
+        static_for<GS>([&](auto MM) {
+          constexpr int m = decltype(MM)::value;
+          constexpr int ps = m / G, os = m % G;
+          if (m < nm) {
+            float vs = 0.0f;
+#pragma unroll
+            for (int k2 = 0; k2 < 9; ++k2) vs += V[ps][k2];
+            Vmean[ps] = (sub == os) ? vs * (1.0f / 9.0f) : Vmean[ps];
+            const float Gy = group_bcast<G, os>(Bm[ps].Gy, gbase), Gwt = group_bcast<G, os>(Bm[ps].Gwt, gbase);
+            const float* recs = buf + ((k0 + m) * GS) * WF_PAIR_STRIDE;
+            static_for<S>([&](auto PP) {
+              constexpr int p = decltype(PP)::value;
+              const float* rec = recs + (p * G + sub) * WF_PAIR_STRIDE;
+              const bool act1 = (p > ps) ? tvalid[p] : (rec[WF_PAIR_DX] >= 0.0f);
+              if (p >= ps || __any(act1)) {
+                if (act1) apply_tab(PP, reinterpret_cast<const float4*>(rec), Gy, Gwt);
+              }
+            });
+            float vb = 0.0f, wb = 0.0f;
+#pragma unroll
+            for (int k2 = 0; k2 < 9; ++k2) { vb += V[ps][k2]; wb += W[ps][k2]; }
+            vbar[ps] = (sub == os) ? vb * (1.0f / 9.0f) : vbar[ps];
+            wbar[ps] = (sub == os) ? wb * (1.0f / 9.0f) : wbar[ps];
+          }
+        });
+        // the lanes that hold the same member as this one (one per farm): the chain's wave-wide questions are asked per source
+        unsigned long long sub_lanes = 0ull;
+#pragma unroll
+        for (int e = 0; e < EPW; ++e) sub_lanes |= 1ull << (e * G);
+        sub_lanes <<= sub;
+        float dTI[S];
+#pragma unroll
+        for (int p = 0; p < S; ++p) {
+          const float TIs[3] = {TI[p][0], TI[p][1], TI[p][2]};
+          const SrcD Dm = src_part_d(Bm[p], Vmean[p], vbar[p], wbar[p], TIs, yaw_t[p], cg_t[p], sg_t[p],
+                                     [&](bool f) { return (__ballot(f) & sub_lanes) != 0ull; });
+          dTI[p] = Dm.X.dTI;
+          int it = tt[p];  // (opaque: no per-lane induction pointers into the log across the block loop)
+          asm volatile("" : "+v"(it));
+          if (J + 1 < nblk && tvalid[p]) log_store(it, Dm);
+          float k6, b6, n6;
+          src_far_bound(Dm, TIs, k6, b6, n6);
+          k6 = sub_max<G>(k6);
+          b6 = sub_max<G>(b6);
+          n6 = sub_max<G>(n6);
+          if (!c.far_on) { k6 = 0.0f; b6 = 0.0f; n6 = 3.0e38f; }  // never far
+          if (ln < G && tvalid[p]) bndL[tt[p]] = make_float4(k6, b6, n6, 0.0f);
+        }
+        // the check: member a's wake against member b, a before b (lane a GS + b)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        bool reach = false;
+        {
+          const int ma = ln / GS, mb = ln % GS;
+          if (ma < mb && mb < nm) {
+            const float2 e = *reinterpret_cast<const float2*>(buf + ((k0 + ma) * GS + mb) * WF_PAIR_STRIDE + WF_PAIR_DX);
+            reach = within_bound(bndL[first_own + ma], e.x, e.y);
+          }
+        }
+        const bool stands = __ballot(reach) == 0ull;
+#ifdef WF_LL_STAMP
+        st_acc[12] += 1ull;
+        st_acc[13] += stands ? 0ull : 1ull;
+#endif
+        if (stands) {
+#pragma unroll
+          for (int p = 0; p < S; ++p) {
+            if (tvalid[p] && Bm[p].risk) atomicOr(&risk_lds[wave][eiw], Bm[p].risk);
+            // (the stored TI: max(ambient, TI + dTI), as in the chain)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) TI[p][j] = fmaxf(TI[p][j] + dTI[p], amb0);
+          }
+        } else {
+#pragma unroll
+          for (int p = 0; p < S; ++p)
+#pragma unroll
+            for (int k2 = 0; k2 < 9; ++k2) {
+              const float2 vw = sv[(p * 9 + k2) * 64];
+              V[p][k2] = vw.x; W[p][k2] = vw.y;
+            }
+        }
+        __builtin_amdgcn_s_setprio(0);
+        return stands;
+      } else {
+        return false;
+      }
+    };
+    bool spec_J = false;  // this block may run its own sources as a stage: the launch made room and the pre-test agrees
+    if constexpr (STAGE) {
+      if (own_ok) spec_J = own_ok[(size_t)grp * nblk + J] != 0;
+    }
 
     for (int cq = 0; cq < n_chunks; ++cq, ++q) {
       if constexpr (TAB) {
@@ -964,9 +1195,6 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
       // (V, W / deficit sums, TI) and each keeps its own order of sources, so they run as two loops per chunk: the results
       // are bit for bit those of one loop.
       WF_T(st_a);
-      auto within_bound = [&](const float4 bnd, float dx, float dy) {  // lin = ad + bd dx: the model's linear deflection offset
-        return fabsf(dy) < fmaxf(fmaf(bnd.x, dx, bnd.y), bnd.z) + fabsf(fmaf(c.bd, dx, c.ad));
-      };
       if constexpr (TAB) {
         if (k_log > 0) {
           // Which logged sources of this chunk are within reach of the block?  On the table path the farms of a wave share
@@ -1094,8 +1322,12 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
       // ---- sources of this block ------------------------------------------------------------------------
       WF_T(st_b);
       WF_ACC(0, st_a, st_b);
+      bool staged = false;
+      if constexpr (STAGE) {
+        if (spec_J && k_log < k_end) staged = own_stage(buf, k_log, k_end - k_log);
+      }
 #pragma unroll 1
-      for (int k = k_log; k < k_end; ++k) {
+      for (int k = staged ? k_end : k_log; k < k_end; ++k) {
         const int i = i0 + k;
         const float* recs = buf + (k * GS) * WF_PAIR_STRIDE;
         const int slot_of_source = (i - first_own) / G;
@@ -1199,7 +1431,7 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
     st_acc[4] = __builtin_readcyclecounter() - st_begin;
     for (int k = 0; k < 5; ++k) atomicAdd(&wf_ll_stamp[k], st_acc[k]);
     atomicAdd(&wf_ll_stamp[5], 1ull);
-    for (int k = 6; k < 12; ++k) atomicAdd(&wf_ll_stamp[k], st_acc[k]);  // parts of an own-source step; 11: transverse pass of the replay (tools/ll_stamps.py)
+    for (int k = 6; k < 14; ++k) atomicAdd(&wf_ll_stamp[k], st_acc[k]);  // 12, 13: blocks that ran their sources as a stage / whose check failed  // parts of an own-source step; 11: transverse pass of the replay (tools/ll_stamps.py)
   }
 #endif
 
@@ -1235,7 +1467,7 @@ template <int G, int S, bool TAB, bool MC1, bool VEER = false>
 static hipError_t launch_ll(const WfConsts* c, const WfTables* tab, const int* gidx, const double* ws, const double* wd,
                             int wind_stride, const float* yaw, float* power, float* o_ws, float* o_wd, float* load, int B,
                             const WfEnvArgs* env, const float* ll_tab, const int* cross_tie, float* src_log, size_t log_records,
-                            const WfGroupArgs* grp, const double* gx, const double* gy, hipStream_t s) {
+                            const WfGroupArgs* grp, const double* gx, const double* gy, const int* own_ok, hipStream_t s) {
   constexpr int fpb = kLLWaves * (64 / G);
   WfGroupArgs ga = *grp;
   const int n_farms = ga.env_end ? ga.env_end - ga.env_base : B;  // (a mixed launch serves a range of the batch)
@@ -1248,11 +1480,11 @@ static hipError_t launch_ll(const WfConsts* c, const WfTables* tab, const int* g
   // dynamic LDS: the far bounds of every wave (16 bytes per source)
   // ... then (table path) two buffers per wave for the hot records of a chunk's logged sources (stage_hot)
   constexpr int hot_bytes = 32768 / (G * G * S) >= 1024 ? 32768 / (G * G * S) : 1024;  // (CH / 2) x EPW x 16 B, whole 1-KiB DMA instructions
-  const size_t dyn_lds = sizeof(float4) * (size_t)kLLWaves * n_pad + (TAB ? (size_t)kLLWaves * 2 * hot_bytes : 0);
+  size_t dyn_lds = sizeof(float4) * (size_t)kLLWaves * n_pad + (TAB ? (size_t)kLLWaves * 2 * hot_bytes : 0);
   // the log allocation holds log_records (farm slot, source) records: hot part, cold part, side records (wf_device.h)
   size_t log_cold_offset = log_records * WF_LOG_HOT_FLOATS, log_side_offset = log_records * WF_LOG_FLOATS;
   void* args[] = {&cc, &tab, &gidx, &ws, &wd, &wind_stride, &yaw, &power, &o_ws, &o_wd, &load, &B, &ea, &ll_tab,
-                  &group_floats, &cross_tie, &src_log, &log_cold_offset, &log_side_offset, &n_pad, &ga, &gx, &gy};
+                  &group_floats, &cross_tie, &src_log, &log_cold_offset, &log_side_offset, &n_pad, &ga, &gx, &gy, &own_ok};
   const void* fn = (const void*)&wf_step_ll_kernel<G, S, false, TAB, MC1, kLLWaves, VEER>;
   if constexpr (TAB) {
     if (wind_stride == 0) fn = (const void*)&wf_step_ll_kernel<G, S, true, TAB, MC1, kLLWaves, VEER>;
@@ -1270,10 +1502,37 @@ static hipError_t launch_ll(const WfConsts* c, const WfTables* tab, const int* g
       fn = wind_stride == 0 ? (const void*)&wf_step_ll_kernel<G, S, true, TAB, MC1, kLLWaves, VEER, true>
                             : (const void*)&wf_step_ll_kernel<G, S, false, TAB, MC1, kLLWaves, VEER, true>;
   }
+  // The own-source stage keeps the block's V and W in LDS for its fallback: 18 S floats per lane.  Taken only where the kernel
+  // has the stage (table path, no veer, a block's sources within one chunk), the far skip is on (the stage's check is the far
+  // bound) and the room costs no resident block per CU — the three-block one-slot builds: asked of the occupancy API, once per
+  // kernel and LDS size.
+  if (!(TAB && !VEER && G * S <= 64 / (G * S)) || !cc.far_on) own_ok = nullptr;
+  if (own_ok) {
+    const size_t save_wave = sizeof(float) * 18 * S * 64;  // over the wave's two hot buffers: only what exceeds them is new
+    const size_t save_bytes = save_wave > 2 * (size_t)hot_bytes ? (save_wave - 2 * (size_t)hot_bytes) * kLLWaves : 0;
+    struct Occ { const void* fn; size_t lds; int keeps; };
+    static Occ seen[16] = {};
+    static int n_seen = 0;
+    static std::mutex seen_mutex;
+    std::lock_guard<std::mutex> lock(seen_mutex);
+    int keeps = -1;
+    for (int k = 0; k < n_seen; ++k)
+      if (seen[k].fn == fn && seen[k].lds == dyn_lds) keeps = seen[k].keeps;
+    if (keeps < 0) {
+      int without = 0, with = 0;
+      keeps = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&without, fn, 64 * kLLWaves, dyn_lds) == hipSuccess &&
+               hipOccupancyMaxActiveBlocksPerMultiprocessor(&with, fn, 64 * kLLWaves, dyn_lds + save_bytes) == hipSuccess && with >= without && with > 0) ? 1 : 0;
+      if (n_seen < 16) seen[n_seen++] = Occ{fn, dyn_lds, keeps};
+    }
+    if (keeps) dyn_lds += save_bytes; else own_ok = nullptr;
+  }
   return hipLaunchKernel(fn, dim3(grid), dim3(64 * kLLWaves), args, dyn_lds, s);
 }
 
+#if WF_LL_PART != 1
 extern "C" int wfk_ll_farms_per_block(int G) { return kLLWaves * (64 / G); }
+#endif
+#if WF_LL_PART != 2  // (the stamps of the unit that holds the headline kernel)
 #ifdef WF_LL_STAMP
 extern "C" int wfk_ll_stamps(unsigned long long* out, int reset) {
   hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(wf_ll_stamp), sizeof(wf_ll_stamp));
@@ -1285,18 +1544,42 @@ extern "C" int wfk_ll_stamps(unsigned long long* out, int reset) {
 }
 #endif
 
+#endif  // WF_LL_PART != 2
+
 // (G, S) instantiations of the table path: one slot per lane at every width, two slots at G = 4 (eight turbines per block
 // like G = 8, S = 1, with sixteen instead of eight farms per wave sharing the per-source phase).  On the fly (a wind
 // per farm): the two variants the rounds model ever picks, each with and without the mirror-core shortcut.
 #define WF_LL_DISPATCH(G_, S_, CALL) \
   if (G == G_ && S == S_) return CALL(G_, S_)
+#define WF_LL_STEP_ARGS                                                                                                          \
+  int G, int S, const WfConsts *c, const WfTables *tab, const int *gidx, const double *ws, const double *wd, int wind_stride,   \
+      const float *yaw, float *power, float *o_ws, float *o_wd, float *load, int B, const WfEnvArgs *env, const float *ll_tab,    \
+      const int *cross_tie, const int *own_ok, float *src_log, size_t log_records, const WfGroupArgs *grp, hipStream_t s
+#define WF_LL_LAUNCH(G_, S_) launch_ll<G_, S_, true, true>(c, tab, gidx, ws, wd, wind_stride, yaw, power, o_ws, o_wd, load, B, env, ll_tab, cross_tie, src_log, log_records, grp, nullptr, nullptr, own_ok, s)
+#if WF_LL_PART != 2
+// the two-slot shapes without veer (this part's; wfk_launch_step_ll / wfk_ll_func_attributes below ask for them)
+extern "C" hipError_t wfk_launch_step_ll_s2(WF_LL_STEP_ARGS) {
+  WF_LL_DISPATCH(4, 2, WF_LL_LAUNCH);
+  WF_LL_DISPATCH(2, 2, WF_LL_LAUNCH);
+  return hipErrorInvalidValue;
+}
+extern "C" hipError_t wfk_ll_func_attributes_s2(int G, int S, int shared_speed, hipFuncAttributes* a) {
+#define WF_LL_ATTR_S2(G_, S_) hipFuncGetAttributes(a, shared_speed ? (const void*)&wf_step_ll_kernel<G_, S_, true, true, true, kLLWaves> : (const void*)&wf_step_ll_kernel<G_, S_, false, true, true, kLLWaves>)
+  WF_LL_DISPATCH(4, 2, WF_LL_ATTR_S2);
+  WF_LL_DISPATCH(2, 2, WF_LL_ATTR_S2);
+  return hipErrorInvalidValue;
+}
+#endif  // WF_LL_PART != 2
+
+#if WF_LL_PART != 1
+extern "C" hipError_t wfk_launch_step_ll_s2(WF_LL_STEP_ARGS);
+extern "C" hipError_t wfk_ll_func_attributes_s2(int G, int S, int shared_speed, hipFuncAttributes* a);
 extern "C" hipError_t wfk_launch_step_ll(int G, int S, const WfConsts* c, const WfTables* tab, const int* gidx, const double* ws,
                                          const double* wd, int wind_stride, const float* yaw, float* power, float* o_ws,
                                          float* o_wd, float* load, int B, const WfEnvArgs* env, const float* ll_tab,
-                                         const int* cross_tie, float* src_log, size_t log_records,
+                                         const int* cross_tie, const int* own_ok, float* src_log, size_t log_records,
                                          const WfGroupArgs* grp, hipStream_t s) {
-#define WF_LL_LAUNCH(G_, S_) launch_ll<G_, S_, true, true>(c, tab, gidx, ws, wd, wind_stride, yaw, power, o_ws, o_wd, load, B, env, ll_tab, cross_tie, src_log, log_records, grp, nullptr, nullptr, s)
-#define WF_LL_LAUNCH_VEER(G_, S_) launch_ll<G_, S_, true, true, true>(c, tab, gidx, ws, wd, wind_stride, yaw, power, o_ws, o_wd, load, B, env, ll_tab, cross_tie, src_log, log_records, grp, nullptr, nullptr, s)
+#define WF_LL_LAUNCH_VEER(G_, S_) launch_ll<G_, S_, true, true, true>(c, tab, gidx, ws, wd, wind_stride, yaw, power, o_ws, o_wd, load, B, env, ll_tab, cross_tie, src_log, log_records, grp, nullptr, nullptr, nullptr, s)
   if (c->veer_on) {  // wind veer: the throughput families only (wfk_ll_has_veer)
     WF_LL_DISPATCH(4, 1, WF_LL_LAUNCH_VEER);
     WF_LL_DISPATCH(4, 2, WF_LL_LAUNCH_VEER);
@@ -1306,8 +1589,7 @@ extern "C" hipError_t wfk_launch_step_ll(int G, int S, const WfConsts* c, const 
   WF_LL_DISPATCH(4, 1, WF_LL_LAUNCH);
   WF_LL_DISPATCH(8, 1, WF_LL_LAUNCH);
   WF_LL_DISPATCH(16, 1, WF_LL_LAUNCH);
-  WF_LL_DISPATCH(4, 2, WF_LL_LAUNCH);
-  WF_LL_DISPATCH(2, 2, WF_LL_LAUNCH);
+  if (S == 2) return wfk_launch_step_ll_s2(G, S, c, tab, gidx, ws, wd, wind_stride, yaw, power, o_ws, o_wd, load, B, env, ll_tab, cross_tie, own_ok, src_log, log_records, grp, s);
   return hipErrorInvalidValue;
 }
 
@@ -1325,13 +1607,13 @@ extern "C" hipError_t wfk_launch_step_ll_fly(int G, int S, const WfConsts* c, co
 #define WF_LL_LAUNCH_FLY(G_, S_)                                                                                              \
   (c->mirror_core_n <= 1                                                                                                      \
        ? launch_ll<G_, S_, false, true>(c, tab, gidx, ws, wd, 1, yaw, power, o_ws, o_wd, load, B, env, nullptr, farm_tie, src_log, \
-                                        log_records, grp, gx, gy, s)                                                       \
+                                        log_records, grp, gx, gy, nullptr, s)                                                       \
        : launch_ll<G_, S_, false, false>(c, tab, gidx, ws, wd, 1, yaw, power, o_ws, o_wd, load, B, env, nullptr, farm_tie,      \
-                                         src_log, log_records, grp, gx, gy, s))
+                                         src_log, log_records, grp, gx, gy, nullptr, s))
   if (c->veer_on) {
     if (G == 4 && S == 2)
       return launch_ll<4, 2, false, false, true>(c, tab, gidx, ws, wd, 1, yaw, power, o_ws, o_wd, load, B, env, nullptr, farm_tie, src_log,
-                                                 log_records, grp, gx, gy, s);
+                                                 log_records, grp, gx, gy, nullptr, s);
     return hipErrorInvalidValue;
   }
   WF_LL_DISPATCH(4, 2, WF_LL_LAUNCH_FLY);
@@ -1341,30 +1623,33 @@ extern "C" hipError_t wfk_launch_step_ll_fly(int G, int S, const WfConsts* c, co
   return hipErrorInvalidValue;
 }
 
+// the attributes of the on-the-fly kernels (this part's; wfk_ll_func_attributes below asks for them)
+extern "C" hipError_t wfk_ll_func_attributes_fly(int G, int S, int veer, int occ2, hipFuncAttributes* a) {
+  if (veer) return (G == 4 && S == 2) ? hipFuncGetAttributes(a, (const void*)&wf_step_ll_kernel<4, 2, false, false, true, kLLWaves, true>) : hipErrorInvalidValue;
+#define WF_LL_ATTR_FLY(G_, S_) hipFuncGetAttributes(a, (const void*)&wf_step_ll_kernel<G_, S_, false, false, true, kLLWaves>)
+#define WF_LL_ATTR_FLY_OCC2(G_, S_) hipFuncGetAttributes(a, (const void*)&wf_step_ll_kernel<G_, S_, false, false, true, kLLWaves, false, true>)
+  if (occ2) {
+    WF_LL_DISPATCH(4, 1, WF_LL_ATTR_FLY_OCC2);
+    WF_LL_DISPATCH(8, 1, WF_LL_ATTR_FLY_OCC2);
+  }
+  WF_LL_DISPATCH(4, 2, WF_LL_ATTR_FLY);
+  WF_LL_DISPATCH(2, 2, WF_LL_ATTR_FLY);
+  WF_LL_DISPATCH(4, 1, WF_LL_ATTR_FLY);
+  WF_LL_DISPATCH(8, 1, WF_LL_ATTR_FLY);
+  return hipErrorInvalidValue;
+}
+
 // (occ2: the launch reaches no third block per CU — launch_ll then takes the two-wave build of a one-slot family)
 extern "C" hipError_t wfk_ll_func_attributes(int G, int S, int shared_speed, int table, int veer, int occ2, hipFuncAttributes* a) {
+  if (!table) return wfk_ll_func_attributes_fly(G, S, veer, occ2, a);
 #define WF_LL_ATTR_VEER(G_, S_) hipFuncGetAttributes(a, shared_speed ? (const void*)&wf_step_ll_kernel<G_, S_, true, true, true, kLLWaves, true> : (const void*)&wf_step_ll_kernel<G_, S_, false, true, true, kLLWaves, true>)
   if (veer) {
-    if (!table) return (G == 4 && S == 2) ? hipFuncGetAttributes(a, (const void*)&wf_step_ll_kernel<4, 2, false, false, true, kLLWaves, true>) : hipErrorInvalidValue;
     WF_LL_DISPATCH(4, 1, WF_LL_ATTR_VEER);
     WF_LL_DISPATCH(4, 2, WF_LL_ATTR_VEER);
     WF_LL_DISPATCH(2, 2, WF_LL_ATTR_VEER);
     return hipErrorInvalidValue;
   }
 #define WF_LL_ATTR(G_, S_) hipFuncGetAttributes(a, shared_speed ? (const void*)&wf_step_ll_kernel<G_, S_, true, true, true, kLLWaves> : (const void*)&wf_step_ll_kernel<G_, S_, false, true, true, kLLWaves>)
-#define WF_LL_ATTR_FLY(G_, S_) hipFuncGetAttributes(a, (const void*)&wf_step_ll_kernel<G_, S_, false, false, true, kLLWaves>)
-#define WF_LL_ATTR_FLY_OCC2(G_, S_) hipFuncGetAttributes(a, (const void*)&wf_step_ll_kernel<G_, S_, false, false, true, kLLWaves, false, true>)
-  if (!table) {
-    if (occ2) {
-      WF_LL_DISPATCH(4, 1, WF_LL_ATTR_FLY_OCC2);
-      WF_LL_DISPATCH(8, 1, WF_LL_ATTR_FLY_OCC2);
-    }
-    WF_LL_DISPATCH(4, 2, WF_LL_ATTR_FLY);
-    WF_LL_DISPATCH(2, 2, WF_LL_ATTR_FLY);
-    WF_LL_DISPATCH(4, 1, WF_LL_ATTR_FLY);
-    WF_LL_DISPATCH(8, 1, WF_LL_ATTR_FLY);
-    return hipErrorInvalidValue;
-  }
 #define WF_LL_ATTR_OCC2(G_, S_) hipFuncGetAttributes(a, shared_speed ? (const void*)&wf_step_ll_kernel<G_, S_, true, true, true, kLLWaves, false, true> : (const void*)&wf_step_ll_kernel<G_, S_, false, true, true, kLLWaves, false, true>)
   if (occ2) {
     WF_LL_DISPATCH(4, 1, WF_LL_ATTR_OCC2);
@@ -1374,7 +1659,7 @@ extern "C" hipError_t wfk_ll_func_attributes(int G, int S, int shared_speed, int
   WF_LL_DISPATCH(4, 1, WF_LL_ATTR);
   WF_LL_DISPATCH(8, 1, WF_LL_ATTR);
   WF_LL_DISPATCH(16, 1, WF_LL_ATTR);
-  WF_LL_DISPATCH(4, 2, WF_LL_ATTR);
-  WF_LL_DISPATCH(2, 2, WF_LL_ATTR);
+  if (S == 2) return wfk_ll_func_attributes_s2(G, S, shared_speed, a);
   return hipErrorInvalidValue;
 }
+#endif  // WF_LL_PART != 1
