@@ -523,6 +523,50 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the gradient kernels as the runtime reports them."""
         return self._grad().kernel_info()
 
+    # -- per-agent counterfactual rewards: difference rewards, COMA rows (include/wfcredit.h) ----------
+    def _credit(self) -> "_Credit":
+        """The handle's credit object; created on first use, destroyed in close() before the handle."""
+        co = getattr(self, "_credit_obj", None)
+        if co is None:
+            co = self._credit_obj = _Credit(self)
+        return co
+
+    def counterfactual_rewards(self, base=None, alt=None, base_kind="yaw", alt_kind="yaw", farms=None, strict=False,
+                               max_eval_farms=None, want=("reward", "difference"), out=None):
+        """What the farm's reward would have been had ONE turbine done something else, for the handle's current wind
+        (include/wfcredit.h; the project's own definition, PARITY UNPINNED beyond the oracle): R = 1 + N K farm solves per
+        farm in one batched step — row 0 the base, row 1 + i K + k the base with turbine i's entry replaced by alternative
+        (i, k) — and each row's reward  mean_j(P_j [MW] 1e3 / ws^3) - load_coef mean|loads|  in float64.
+          base       (n_farms, N) float32 (row i belongs to farms[i]) — torch CUDA tensor or NumPy — or None: the fused env's
+                     current yaw state
+          alt        (n_farms, N, K) float32, K alternatives per turbine (1 <= K <= 8; (n_farms, N) is K = 1), or None: one
+                     alternative, the hold action (alt_kind "action") or zero yaw ("yaw")
+          base_kind, alt_kind  "yaw": absolute degrees, used as given; "action": the env's encoding under env_config, turned
+                     into a yaw by the fused step's own transition (budget gate, increment, clip) on the env state, which is
+                     only read
+          farms      farm indices (any order), or None: every farm of the batch
+          strict     every row is solved in float64; otherwise the handle's own resolve mode.  A difference of two float32
+                     rows is bounded only by twice the step's tolerance: use strict=True on large farms or where |D| is
+                     small (include/wfcredit.h: WHEN TO USE strict)
+          max_eval_farms  rows the evaluator handle may hold, 1 + N K per farm: longer lists run in chunks (None: 65 536)
+          want       of "reward" (n, R) float64, "farm_power" (n, R) float64 [W], "difference" (n, N, K) float64 =
+                     reward[:, 0] - reward[:, 1 + i K + k]
+          out        dict of tensors / arrays of those names to write into (a torch `out` selects the device path when base
+                     and alt are None)
+        Where an alternative's float32 yaw has the bits of the base entry, difference is exactly 0.0 and the row's reward
+        and farm_power are copies of row 0's.  The reward is normalised by the speed the next env_step would normalise by
+        (env_set_prev_wind is read, not consumed).  Deterministic: fixed summation order, no atomics.  With torch tensors
+        the call only enqueues work on torch's current stream.  The handle is not touched."""
+        return self._credit().run(base, alt, base_kind, alt_kind, farms, strict, max_eval_farms, want, out)
+
+    def credit_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last counterfactual_rewards {"total_ms", "step_ms", "glue_ms"}."""
+        return self._credit().timing(detail)
+
+    def credit_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the credit kernels as the runtime reports them."""
+        return self._credit().kernel_info()
+
     # -- wind-rose expected power and the yaw look-up table (include/wfrose.h) -------------------------
     def _rose(self) -> "_Rose":
         """The handle's rose object; created on first use, destroyed in close() before the handle."""
@@ -827,8 +871,9 @@ class WfStep:
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h)
-            for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rose_obj", "_robust_obj", "_grad_obj"):
+            # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h,
+            # wfcredit.h)
+            for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
                     ext.close()
@@ -844,7 +889,7 @@ class WfStep:
 
 
 class _Ext:
-    """An extension object of a WfStep handle — the `wf_<NAME>` of include/wf<NAME>.h — and what the five wrappers share:
+    """An extension object of a WfStep handle — the `wf_<NAME>` of include/wf<NAME>.h — and what the six wrappers share:
     create / close, timing, kernel_info, evaluator, and the conversion of farm lists, (n, N) float32 rows and output dicts
     into the pointers the C ABI takes.  `_r` is the raw object, `KERNELS` names kernel_info's entries in the library's order."""
 
@@ -1209,3 +1254,56 @@ class _Grad(_Ext):
         grad = torch.empty((B, N), device=yaw.device, dtype=torch.float64)
         self._call("run", yptr, cptr, B, None, None, grad.data_ptr(), None, 1)
         return grad
+
+
+class _Credit(_Ext):
+    """The `wf_credit` object of a WfStep handle (include/wfcredit.h)."""
+
+    NAME = "credit"
+    KERNELS = ("layout", "reduce")
+    KIND = {"yaw": 0, "action": 1}
+    OUTPUTS = ("reward", "farm_power", "difference")
+
+    def run(self, base, alt, base_kind, alt_kind, farms, strict, max_eval_farms, want, out):
+        w = self._w
+        N = w.num_turbines
+        if base_kind not in self.KIND or alt_kind not in self.KIND:
+            raise ValueError("base_kind and alt_kind must be 'yaw' or 'action'")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.OUTPUTS for k in want):
+            raise ValueError("want must name reward, farm_power and / or difference")
+        self._call("config", int(bool(strict)), int(max_eval_farms or 0))
+        fa, n, fptr = self._farms(farms)
+        on_device = _is_torch(base) or _is_torch(alt) or (out is not None and any(_is_torch(v) for v in out.values()))
+        if on_device:
+            w._follow_torch_stream()
+        base, bptr = self._rows(base, n, on_device, "base")
+        K, aptr = 1, None
+        if alt is not None:
+            if not on_device:
+                alt = np.ascontiguousarray(alt, dtype=np.float32)
+            shape = tuple(alt.shape)
+            if len(shape) == 2:
+                shape += (1,)
+            if len(shape) != 3 or shape[:2] != (n, N):
+                raise ValueError("alt must be (n_farms, num_turbines, K): K alternatives per turbine of every listed farm")
+            K = int(shape[2])
+            if on_device:
+                import torch
+
+                assert alt.is_cuda and alt.dtype == torch.float32, "alt"
+                alt = alt.contiguous()
+                aptr = alt.data_ptr()
+            else:
+                aptr = alt.ctypes.data
+        R = 1 + N * K
+        shapes = {"reward": ((n, R), np.float64), "farm_power": ((n, R), np.float64), "difference": ((n, N, K), np.float64)}
+        spec = {k: shapes[k] for k in self.OUTPUTS if k in want}
+        like = base if base is not None else alt
+        if on_device and like is None:
+            like = next(v for v in out.values() if _is_torch(v))
+        out, ptrs = self._outputs(out, spec, on_device, like)
+        p = dict(zip(spec, ptrs))
+        self._call("run", self.KIND[base_kind], bptr, self.KIND[alt_kind], aptr, K, n, fptr, p.get("reward"), p.get("farm_power"),
+                   p.get("difference"), int(on_device))
+        return {k: out[k] for k in spec}

@@ -5,7 +5,8 @@ PettingZoo AEC env; `<Layout>` is one of the named farms (layouts.json) or a pro
 with N = 1..12.  Same name grammar, defaults and 88 registered names as reference
 wfcrl/environments/registration.py:17-117; the `_Floris` suffix is served by the HIP backend, `_Fastfarm` names are
 listed for compatibility but raise (that simulator is out of scope).  Extra keyword of this build: `env_batch=B`
-returns the batched, device-resident `VecWindFarmEnv`.
+returns the batched, device-resident `VecWindFarmEnv`; with a `Dec_` name, `agent_reward="difference"` (and
+`default_action="hold" | "zero"`) pays every turbine-agent its difference reward instead of the cooperative one.
 """
 from __future__ import annotations
 
@@ -80,6 +81,11 @@ def make(env_id: str, controls: Union[dict, list] = ["yaw"], log=True, **env_kwa
     first_control_iter = math.ceil(case.t_init / case.dt)
 
     batch = env_kwargs.pop("env_batch", None)
+    agent_reward = env_kwargs.pop("agent_reward", "shared")
+    default_action = env_kwargs.pop("default_action", "hold")
+    if agent_reward != "shared" and not (decentralised and batch is not None):
+        raise ValueError('agent_reward is an option of the batched decentralised envs: make("Dec_...", env_batch=B, '
+                         'agent_reward="difference")')
     if batch is not None:
         from ..vec_env import VecWindFarmEnv
 
@@ -95,7 +101,7 @@ def make(env_id: str, controls: Union[dict, list] = ["yaw"], log=True, **env_kwa
                 env_kwargs["reuse_buffers"] = False
             inner = VecWindFarmEnv(case, controls, env_batch=batch, start_iter=first_control_iter,
                                    actuation_budget=float("inf"), **env_kwargs)
-            env = VecAECWindFarmEnv(inner)
+            env = VecAECWindFarmEnv(inner, agent_reward=agent_reward, default_action=default_action)
             return VecAECLogWrapper(env) if log else env
         return VecWindFarmEnv(case, controls, env_batch=batch, start_iter=first_control_iter, **env_kwargs)
 

@@ -309,6 +309,27 @@ class HipFlorisInterface(BaseInterface):
         r = self.fi.yaw_gradient(y, c, step=step, bounds=bounds, strict=strict, jacobian=jacobian)
         return {k: v[0].astype(np.float64) for k, v in r.items()}
 
+    def counterfactual_rewards(self, yaw=None, alt=None, load_coef=0.1, strict=False):
+        """What the farm's reward would have been had one turbine stood elsewhere, for the current wind: dict(reward_base,
+        reward_alt [N][K], difference [N][K] = reward_base - reward_alt), float64.  yaw None: the current yaw command; alt
+        [N][K] absolute yaw alternatives per turbine ([N] is K = 1), None: zero yaw.  reward = mean_j(P_j [MW] 1e3 / ws^3) -
+        load_coef mean|loads| (include/wfcredit.h; backend.WfStep.counterfactual_rewards; the project's own definition).  The
+        yaw command of the interface is not changed."""
+        if self._wind_dirty:
+            self.fi.set_wind(self._ws, self._wd)
+            self._wind_dirty = False
+        if float(load_coef) != getattr(self, "_credit_load_coef", 0.1):
+            self.fi.env_config(load_coef=float(load_coef))
+            self._credit_load_coef = float(load_coef)
+        y = self._current_yaw_command if yaw is None else yaw
+        y = np.asarray(y, dtype=np.float64).reshape(1, -1).astype(np.float32)
+        N = y.shape[1]
+        a = None if alt is None else np.asarray(alt, dtype=np.float32).reshape(1, N, -1)
+        r = self.fi.counterfactual_rewards(y, a, strict=strict)
+        K = 1 if a is None else a.shape[2]
+        return {"reward_base": float(r["reward"][0, 0]), "reward_alt": r["reward"][0, 1:].reshape(N, K).copy(),
+                "difference": r["difference"][0].copy()}
+
     def get_farm_AEP(self, wind_directions, wind_speeds, freq, cut_in_wind_speed=0.001, cut_out_wind_speed=None,
                      yaw_angles=None, no_wake=False, turbine_weights=None):
         """Annual energy production [GWh] over a wind rose, with the argument names FLORIS users know:

@@ -9,6 +9,11 @@ per cycle for all B farms.
 `VecWindFarmEnv`: one `step(actions)` call = one joint step of every farm (the AEC env of the reference needs N
 Python calls per joint step, wfcrl/multiagent_env.py:159-254).  Agent naming, per-agent observation keys and
 the cooperative reward follow the reference (multiagent_env.py:51-53, 102-115, 229-238).
+Both take `agent_reward="difference"`: instead of the one cooperative reward, agent `turbine_{i+1}` is paid its DIFFERENCE
+REWARD D_i = r(a) - r(a_-i, c_i) — what the farm's reward owes to its own action, against `default_action` c_i ("hold" or
+"zero" yaw) — from one call of `VecWindFarmEnv.counterfactual_rewards` on the joint action before the joint step
+(include/wfcredit.h; the project's own definition); `info["shared_reward"]` carries the cooperative reward.  The default
+"shared" is the reference's behaviour, unchanged.
 `VecLogWrapper` keeps observation / reward / power / load histories in preallocated ring buffers instead of
 Python lists (wrappers.py:61-88).
 """
@@ -22,10 +27,19 @@ from ._compat import AECEnv, BaseWrapper, agent_selector, spaces
 from .mdp import WindFarmMDP
 
 
+def _check_agent_reward(agent_reward, default_action):
+    if agent_reward not in ("shared", "difference"):
+        raise ValueError('agent_reward must be "shared" (the cooperative reward) or "difference" (difference rewards)')
+    if default_action not in ("hold", "zero"):
+        raise ValueError('default_action must be "hold" or "zero"')
+
+
 class VecParallelWindFarmEnv:
     metadata = {"name": "vectorized-multiagent-windfarm", "is_parallelizable": True}
 
-    def __init__(self, vec_env):
+    def __init__(self, vec_env, agent_reward="shared", default_action="hold"):
+        _check_agent_reward(agent_reward, default_action)
+        self.agent_reward, self.default_action = agent_reward, default_action
         self.env = vec_env
         self.num_envs = vec_env.num_envs
         self.num_turbines = vec_env.num_turbines
@@ -73,12 +87,20 @@ class VecParallelWindFarmEnv:
         missing = [a for a in self.possible_agents if a not in actions]
         if missing:
             raise ValueError(f"Action dict is incomplete. Missing agents: {missing}")
-        obs, reward, term, trunc, info = self.env.step({"yaw": self._join(actions)})
+        joint = self._join(actions)
+        credit = None
+        if self.agent_reward == "difference":  # (before the step: it reads the state the step is about to change)
+            credit = self.env.counterfactual_rewards(joint, self.default_action)["difference"]
+        obs, reward, term, trunc, info = self.env.step({"yaw": joint})
         per_obs = self._split(obs)
         rewards = {a: reward for a in self.possible_agents}  # cooperative: same reward for every turbine
         terms = {a: term for a in self.possible_agents}
         truncs = {a: trunc for a in self.possible_agents}
         infos = {a: {"power": info["power"][:, i], "load": info["load"][:, i]} for a, i in self.agent_name_mapping.items()}
+        if credit is not None:
+            for a, i in self.agent_name_mapping.items():
+                rewards[a] = credit[:, i, 0]
+                infos[a]["shared_reward"] = reward
         if bool(trunc[0]):
             self.agents = []
         return per_obs, rewards, terms, truncs, infos
@@ -101,7 +123,9 @@ class VecAECWindFarmEnv(AECEnv):
 
     metadata = {"name": "vectorized-multiagent-windfarm-aec", "is_parallelizable": True}
 
-    def __init__(self, vec_env):
+    def __init__(self, vec_env, agent_reward="shared", default_action="hold"):
+        _check_agent_reward(agent_reward, default_action)
+        self.agent_reward, self.default_action = agent_reward, default_action
         self.env = vec_env
         self.num_envs, self.num_turbines = vec_env.num_envs, vec_env.num_turbines
         self.continuous_control, self.controls = vec_env.continuous_control, vec_env.controls
@@ -202,6 +226,9 @@ class VecAECWindFarmEnv(AECEnv):
 
         if self._agent_selector.is_last():
             joint = self._stack([self.actions[n] for n in self.possible_agents])
+            credit = None
+            if self.agent_reward == "difference":  # (before the step: it reads the state the step is about to change)
+                credit = self.env.counterfactual_rewards(joint, self.default_action)["difference"]
             obs, reward, term, trunc, info = self.env.step({"yaw": joint})
             self._state = obs
             truncated = bool(trunc[0])
@@ -210,6 +237,9 @@ class VecAECWindFarmEnv(AECEnv):
                     continue
                 self.infos[name]["load"] = info["load"][:, k]
                 self.rewards[name] = reward  # cooperative: one reward for every turbine
+                if credit is not None:  # ... or the agent's own difference reward
+                    self.rewards[name] = credit[:, k, 0]
+                    self.infos[name]["shared_reward"] = reward
                 self.observations[name] = self.observe(name)
                 self.truncations[name], self.terminations[name] = truncated, False
                 self.infos[name]["power"] = info["power"][:, k]

@@ -363,6 +363,60 @@ class VecWindFarmEnv:
             cotangent = self._to_device(cotangent).float().reshape(yaw.shape)
         return self.fi.yaw_gradient(yaw, cotangent, farms=farms, step=step, bounds=(lo, hi), strict=strict)
 
+    def counterfactual_rewards(self, actions, alternatives="hold", farms=None, strict=False):
+        """Per-agent counterfactuals of the joint action the env is ABOUT to take — call it BEFORE `step(actions)`:
+        dict(reward_base (n_farms,), reward_alt (n_farms, N, K), difference (n_farms, N, K) = reward_base - reward_alt),
+        float64, torch CUDA tensors when the env returns torch.  reward_base is the reward `step(actions)` will pay (to the
+        step's tolerance); reward_alt[b, i, k] the one it would pay had turbine i alone taken alternative k:
+          "hold"   the hold action (difference rewards against "did nothing"), K = 1
+          "zero"   absolute zero yaw, K = 1
+          "all"    discrete control: the three actions down / hold / up, K = 3 — the rows of a COMA baseline
+          an action array (num_envs, N, K) in the env's encoding
+        actions is the whole batch's (num_envs, N); farms picks the farms served.  Every action goes through the step's own
+        budget gate, increment and clip on the env's state (include/wfcredit.h; backend.WfStep.counterfactual_rewards; the
+        project's own definition).  Run on a handle of its own: the env's yaw state, accumulators, wind and buffers are
+        read, never changed.  strict=True solves every row in float64: the mode for large farms and small differences."""
+        if self._series is not None:
+            raise NotImplementedError("counterfactual_rewards is not supported on a time-series episode: the series tick "
+                                      "precedes the step, so the wind of the coming step is not the one the env holds")
+        if type(self.reward_shaper).__name__ != "DoNothingReward":
+            raise ValueError("counterfactual_rewards needs the plain reward (DoNothingReward): the effect of a reward shaper "
+                             "is not defined per agent")
+        a = self._to_device(actions["yaw"] if isinstance(actions, dict) else actions)
+        B, N = self.num_envs, self.num_turbines
+        if tuple(a.shape) != (B, N):
+            raise ValueError("actions must be (num_envs, num_turbines): the joint action of the whole batch")
+        idx = None if farms is None else np.ascontiguousarray(farms, dtype=np.int64).reshape(-1)
+        n = B if idx is None else idx.size
+
+        def pick(v):
+            if idx is None:
+                return v
+            if self.return_torch:
+                import torch
+
+                return v[torch.from_numpy(idx).to(v.device)]
+            return v[idx]
+
+        alt, alt_kind = None, "action"
+        if isinstance(alternatives, str):
+            if alternatives == "zero":
+                alt_kind = "yaw"
+            elif alternatives == "all":
+                if self.continuous_control:
+                    raise ValueError('alternatives="all" lists the three discrete actions: the env has continuous control')
+                alt = self._to_device(np.broadcast_to(np.float32([0.0, 1.0, 2.0]), (n, N, 3)).copy())
+            elif alternatives != "hold":
+                raise ValueError('alternatives must be "hold", "zero", "all" or an action array (num_envs, N, K)')
+        else:
+            alt = self._to_device(alternatives)
+            if alt.ndim != 3 or tuple(alt.shape[:2]) != (B, N):
+                raise ValueError("an alternatives array must be (num_envs, num_turbines, K)")
+            alt = pick(alt)
+        r = self.fi.counterfactual_rewards(pick(a), alt, base_kind="action", alt_kind=alt_kind, farms=farms, strict=strict)
+        K = 1 if alt is None else int(alt.shape[2])
+        return {"reward_base": r["reward"][:, 0], "reward_alt": r["reward"][:, 1:].reshape(n, N, K), "difference": r["difference"]}
+
     def lut_target_yaw(self, table_slot: int = 0):
         """The yaw (num_envs, N) the look-up table in `table_slot` (backend.WfStep.set_yaw_table on `self.fi`) holds for
         every farm's CURRENT wind, clipped to the env's yaw bounds — a torch CUDA tensor when the env returns torch.  The
