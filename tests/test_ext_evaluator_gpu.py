@@ -1,15 +1,17 @@
 """GPU: the evaluator follows its parent.
 
 Every extension object that solves farms (yaw optimisation, the robust search and the expected power under uncertainty,
-the rose, the yaw sensitivities) keeps an evaluator handle built from its parent's model, layout, kernel choice and guard
-band on the parent's stream (csrc/ext/wf_ext.h: ensure_evaluator).  Here each of the five calls runs once on a WfStep, the
-parent is changed, and the call runs again: the second answer has to be, bit for bit, what the same call gives on a fresh
-WfStep constructed in the changed configuration — and, where the change moves the physics, not what the first call gave.
+the rose, the yaw sensitivities, the counterfactual rewards) keeps an evaluator handle built from its parent's model,
+layout, kernel choice and guard band on the parent's stream (csrc/ext/wf_ext.h: ensure_evaluator).  Here each of the six
+calls runs once on a WfStep, the parent is changed, and the call runs again: the second answer has to be, bit for bit, what
+the same call gives on a fresh WfStep constructed in the changed configuration — and, where the change moves the physics,
+not what the first call gave.
 
 Shapes are the smallest that reach the code: the three-turbine row of tests/yawopt_ref.py, env_batch = 2 with two
-different winds, one pass of three candidates, three members, 2 directions x 1 speed, R = 2 N + 1 = 7 rows.  Every call is
-strict: every row is solved by the float64 kernel, whose bits depend neither on the batch nor on the kernel family
-(tests/test_grad_gpu.py), so a fresh handle is a bit-exact reference and no tolerance is needed."""
+different winds, one pass of three candidates, three members, 2 directions x 1 speed, R = 2 N + 1 = 7 rows of the
+sensitivities, one alternative per turbine (R = 1 + N = 4 rows).  Every call is strict: every row is solved by the float64
+kernel, whose bits depend neither on the batch nor on the kernel family (tests/test_grad_gpu.py), so a fresh handle is a
+bit-exact reference and no tolerance is needed."""
 import numpy as np
 import pytest
 
@@ -22,6 +24,7 @@ WIND = (np.array([8.0, 9.0]), np.array([270.0, 268.0]))
 YAW = np.array([[10.0, 5.0, 0.0], [-8.0, 12.0, 3.0]], np.float32)
 MEMBERS = {"delta": [-3.0, 0.0, 3.0], "weight": [1.0, 2.0, 1.0]}
 ROSE = (np.array([270.0, 265.0]), np.array([8.0]), np.array([[0.6], [0.4]]))
+ALT = np.array([[[0.0], [-5.0], [10.0]], [[8.0], [0.0], [-3.0]]], np.float32)  # (2, 3, 1): every entry differs from YAW's
 
 
 def _yaw(device):
@@ -60,6 +63,15 @@ def _yaw_gradient(w, strict, device):
     return w.yaw_gradient(_yaw(device), strict=strict, jacobian=True)
 
 
+def _counterfactual_rewards(w, strict, device):
+    alt = ALT
+    if device:
+        import torch
+
+        alt = torch.as_tensor(ALT, device="cuda")
+    return w.counterfactual_rewards(base=_yaw(device), alt=alt, strict=strict)
+
+
 # call -> (the call, the wrapper whose evaluator() is the handle this call steps on, or None where there is no such getter)
 CALLS = {
     "optimize_yaw": (_optimize_yaw, "_yawopt"),
@@ -67,6 +79,7 @@ CALLS = {
     "uncertain_power": (_uncertain_power, None),  # (wf_robust_evaluator names the search's evaluator, not this one)
     "expected_power": (_expected_power, None),    # (include/wfrose.h has no evaluator getter)
     "yaw_gradient": (_yaw_gradient, "_grad"),
+    "counterfactual_rewards": (_counterfactual_rewards, "_credit"),
 }
 
 

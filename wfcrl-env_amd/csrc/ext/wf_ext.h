@@ -1,11 +1,14 @@
-// wf_ext.h — the host layer every extension object (probe/, yawopt/, rose/, robust/, grad/) stands on: the base struct with
-// the parent handle, the error text and the event pool; a grow-only device buffer that frees itself; the evaluator — a
-// further handle that follows the parent, configured through the public ABI of include/wfstep.h only; the checks an
-// extension asks of its parent and of a farm list; event recording and the step / glue split of a timed run; kernel
-// attributes; and the coordinate search over yaw that yawopt/ and robust/ run — its configuration, its buffers and the
-// driver that enqueues it (run_search).  wf_ext.hip holds the non-template parts, wf_ext_kernels.h the device side.
+// wf_ext.h — the host layer every extension object (probe/, yawopt/, rose/, robust/, grad/, credit/) stands on: the base
+// struct with the parent handle, the error text and the event pool; a grow-only device buffer that frees itself; the
+// evaluator — a further handle that follows the parent, configured through the public ABI of include/wfstep.h only; the
+// checks an extension asks of its parent and of a farm list; the staging of a host caller's arrays (staging); event
+// recording and the step / glue split of a timed run; kernel attributes; and the two drivers that enqueue a whole run on the
+// parent's stream: run_rows — R evaluator rows for each of n items, in chunks: lay-out, one step, reduce (grad/, credit/,
+// rose/, robust/'s evaluation) — and run_search, the coordinate search over yaw of yawopt/ and robust/, with its
+// configuration.  wf_ext.hip holds the non-template parts, wf_ext_kernels.h the device side.
 // A new extension starts here: derive its object from ext_base, declare its buffers as dev_buf, and call these.
 #pragma once
+#include <cassert>
 #include <functional>
 
 #include "../wf_handle.h"
@@ -106,22 +109,31 @@ inline WfSlots chunk_slots(const farm_list& fl, const int* farms, int base, int 
   return WfSlots{farms ? fl.d.p : nullptr, base, n_farms - base < C ? n_farms - base : C, C};
 }
 
-// A host caller's n input values go through the staging buffer `buf` (reserved by the caller); *d is where the kernels read
-// them: `src` itself for a device caller or none.
-template <class T>
-int stage_in(ext_base* x, const dev_buf<T>& buf, const T* src, size_t n, int on_device, const T** d) {
-  *d = src;
-  if (!src || on_device) return WF_OK;
-  WFX_HIP(x, hipMemcpyAsync(buf.p, src, sizeof(T) * n, hipMemcpyHostToDevice, x->h->stream));
-  *d = buf.p;
-  return WF_OK;
-}
-// where the kernels write an output: the device caller's array, a host caller's place in the staging buffer, null when not
-// asked for
-template <class T>
-T* out_ptr(T* user, const dev_buf<T>& staging, size_t offset, int on_device) {
-  return user ? (on_device ? user : staging.p + offset) : nullptr;
-}
+// A caller's arrays as the kernels see them.  A device caller's pointers pass through.  A host caller's arrays, of any
+// element type, lie end to end (16-byte aligned) in `buf`, in the order they were named: in() for what the kernels read,
+// out() for what they write; *d is the array's device pointer, null for a null array — a host caller's from begin() on.
+struct staging {
+  ext_base* x;
+  dev_buf<char>& buf;
+  bool host;
+  struct seg { const void* src; void* user; size_t off, bytes; void* d; void (*set)(void* d, char* p); } segs[6];
+  int n_segs = 0;
+  size_t total = 0;
+  staging(ext_base* x, dev_buf<char>& buf, int on_device) : x(x), buf(buf), host(!on_device) {}
+  template <class T>
+  void in(const T* src, size_t n, const T** d) {
+    *d = src;
+    if (host && src) add(seg{src, nullptr, total, sizeof(T) * n, d, [](void* d, char* p) { *(const T**)d = (const T*)p; }});
+  }
+  template <class T>
+  void out(T* user, size_t n, T** d) {
+    *d = user;
+    if (host && user) add(seg{nullptr, user, total, sizeof(T) * n, d, [](void* d, char* p) { *(T**)d = (T*)p; }});
+  }
+  void add(const seg& s) { assert(n_segs < 6); segs[n_segs++] = s; total += (s.bytes + 15) & ~(size_t)15; }
+  int begin();  // reserves the buffer once, gives every array its place in it and enqueues the inputs' copies
+  int end();    // after the run: a host caller's outputs come back, and the stream is drained
+};
 
 // an event on the parent's stream, from the pool
 int record(ext_base* x);
@@ -130,6 +142,35 @@ int record(ext_base* x);
 int last_timing(ext_base* x, const char* not_run, float* total_ms, float* step_ms, float* glue_ms);
 // numRegs, static LDS bytes and private-segment bytes of an extension's n kernels
 int kernel_info(ext_base* x, int n, hipError_t (*attributes)(int, hipFuncAttributes*), int* info);
+
+// ---- a row run: R evaluator rows for each of n items, in chunks (grad/, credit/, rose/, robust/'s evaluation) ----
+// what a row-running object holds (grow-only): the evaluator's input and outputs, the rows' wind and the farm list
+struct row_batch {
+  dev_buf<float> d_yaw, d_pow, d_load;  // [E][N], [E][N], [E][N][4] (reserved for a policy with loads)
+  dev_buf<double> d_wind;               // [2][E] speed, direction
+  farm_list farms;
+};
+// What differs between the row runs.  Every hook returns a WF_* code (and has set the error text).
+struct row_policy {
+  const char *what = "", *name = nullptr;  // check_parent's phrase and the entry point's name (null: the run needs no wind of the parent's)
+  int rows = 1;             // evaluator rows an item takes
+  std::string no_rows;      // ... <= 0 is refused with this, after the parent's checks
+  const char* rows_msg = "";  // max_eval cannot hold one item's rows
+  bool by_farm = true;      // an item is a farm: n_items and farms are check_farms'.  Else: no list, *n_items as it is after check
+  int strict = 0, max_eval = 65536;
+  bool loads = false;         // the step also fills d_load
+  bool split_always = false;  // four events per chunk on every run, not only under detail
+  std::function<int()> check;  // the extension's own checks, after the parent's and the farm list's; may still set rows and *n_items
+  std::function<int(int C, int E)> reserve;  // the extension's own buffers, for chunks of C items; names the caller's arrays to `st`
+  // a chunk's kernels, before the step (yaw and wind of the E rows) and after it; sl.base is the chunk's first item
+  std::function<int(const WfSlots& sl, int E)> layout, reduce;
+  std::function<int()> finish;  // what follows the last chunk, if anything (the rose's copy of its sums)
+};
+// The whole run on the parent's stream.  Chunks of C = max_eval / rows items (at most all *n_items), E = C rows evaluator
+// farms.  Per chunk: layout, then wf_set_wind_counts from b.d_wind and one wf_step from b.d_yaw into b.d_pow (and b.d_load),
+// then reduce.  The caller's arrays go through `st`: begun after reserve, ended last.  Events: the run's first and last, or
+// split per chunk e0 | lay-out e | wind + step e | reduce e (last_timing's per_chunk layout with 4).
+int run_rows(ext_base* x, row_batch& b, evaluator& es, row_policy& k, staging& st, int* n_items, const int* farms);
 
 // ---- the coordinate search over yaw (include/wfyawopt.h; include/wfrobust.h: "with farm power replaced by E") ----
 struct search_config {
@@ -145,13 +186,13 @@ int set_search_config(ext_base* x, search_config& c, double lo, double hi, int n
 int k_max(int P, const int* K);
 void pass_grids(double lo, double hi, int P, const int* K, WfGrid* grid);
 
-// what a searching object holds: the configuration and the device buffers (grow-only) every search needs
-struct yaw_search {
+// what a searching object holds: the configuration, a row run's buffers (the wind is the extension's to fill) and the
+// device buffers (grow-only) every search needs besides
+struct yaw_search : row_batch {
   search_config cfg;
-  dev_buf<float> d_yaw, d_pow, d_best;  // [E][N] the evaluator's input and output, [C][N] best yaw so far
-  dev_buf<int> d_order;                 // [C][N]
-  farm_list farms;
-  dev_buf<float> d_in, d_out;  // staging for host callers: yaw0; yaw_opt, power_opt, power_init
+  dev_buf<float> d_best;    // [C][N] best yaw so far
+  dev_buf<int> d_order;     // [C][N]
+  dev_buf<char> d_stage;    // staging for host callers: yaw0, yaw_opt, power_opt, power_init
 };
 
 // What differs between the searches.  Every hook returns a WF_* code (and has set the error text).

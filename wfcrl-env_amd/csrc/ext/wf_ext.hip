@@ -92,6 +92,25 @@ int upload_farms(ext_base* x, farm_list& fl, const int* farms, int n_farms) {
   return WF_OK;
 }
 
+int staging::begin() {
+  const int rc = reserve(x, buf, total);
+  if (rc != WF_OK) return rc;
+  for (int i = 0; i < n_segs; ++i) {
+    const seg& s = segs[i];
+    s.set(s.d, buf.p + s.off);
+    if (s.src) WFX_HIP(x, hipMemcpyAsync(buf.p + s.off, s.src, s.bytes, hipMemcpyHostToDevice, x->h->stream));
+  }
+  return WF_OK;
+}
+
+int staging::end() {
+  if (!host) return WF_OK;
+  for (int i = 0; i < n_segs; ++i)
+    if (segs[i].user) WFX_HIP(x, hipMemcpyAsync(segs[i].user, buf.p + segs[i].off, segs[i].bytes, hipMemcpyDeviceToHost, x->h->stream));
+  WFX_HIP(x, hipStreamSynchronize(x->h->stream));
+  return WF_OK;
+}
+
 int record(ext_base* x) {
   if (x->n_ev == x->ev_pool.size()) {
     hipEvent_t e = nullptr;
@@ -131,6 +150,48 @@ int kernel_info(ext_base* x, int n, hipError_t (*attributes)(int, hipFuncAttribu
   return WF_OK;
 }
 
+int run_rows(ext_base* x, row_batch& b, evaluator& es, row_policy& k, staging& st, int* n_items, const int* farms) {
+  wf_handle* h = x->h;
+  int rc = check_parent(x, k.what, k.name);
+  if (rc != WF_OK) return rc;
+  if (k.rows <= 0) return ext_fail(x, WF_E_INVALID, k.no_rows);
+  if (k.by_farm && (rc = check_farms(x, n_items, farms)) != WF_OK) return rc;
+  if (k.check && (rc = k.check()) != WF_OK) return rc;
+  const int N = h->N, R = k.rows, n = *n_items;
+  if (k.max_eval < R) return ext_fail(x, WF_E_INVALID, k.rows_msg);
+  WFX_ON_DEVICE(x);
+  int C = k.max_eval / R;
+  if (C > n) C = n;
+  const int E = C * R;
+  if ((rc = ensure_evaluator(x, es, E, k.strict ? 2 : h->resolve_mode)) != WF_OK) return rc;
+  const size_t en = (size_t)E * N;
+  rc = reserve(x, b.d_yaw, en);
+  if (rc == WF_OK) rc = reserve(x, b.d_pow, en);
+  if (rc == WF_OK && k.loads) rc = reserve(x, b.d_load, 4 * en);
+  if (rc == WF_OK) rc = reserve(x, b.d_wind, 2 * (size_t)E);
+  if (rc == WF_OK && farms) rc = reserve(x, b.farms.d, (size_t)n);
+  if (rc != WF_OK) return rc;
+  if (farms && (rc = upload_farms(x, b.farms, farms, n)) != WF_OK) return rc;
+  if ((rc = k.reserve(C, E)) != WF_OK || (rc = st.begin()) != WF_OK) return rc;
+  const bool split = k.split_always || x->detail != 0;
+  x->n_ev = 0; x->timed = false;
+  for (int first = 0; first < n; first += C) {
+    const WfSlots sl = chunk_slots(b.farms, farms, first, n, C);
+    if (first == 0 || split) { rc = record(x); if (rc != WF_OK) return rc; }  // (split: four events per chunk)
+    if ((rc = k.layout(sl, E)) != WF_OK) return rc;
+    if (split) { rc = record(x); if (rc != WF_OK) return rc; }
+    WFX_EV(x, es.ev, wf_set_wind_counts(es.ev, b.d_wind, E, b.d_wind + E, E, 1));
+    WFX_EV(x, es.ev, wf_step(es.ev, b.d_yaw, b.d_pow, nullptr, nullptr, k.loads ? b.d_load.p : nullptr, 1));
+    if (split) { rc = record(x); if (rc != WF_OK) return rc; }
+    if ((rc = k.reduce(sl, E)) != WF_OK) return rc;
+    if (split) { rc = record(x); if (rc != WF_OK) return rc; }
+  }
+  if (!split) { rc = record(x); if (rc != WF_OK) return rc; }
+  x->timed = true; x->per_chunk = split ? 4 : 0;
+  if (k.finish && (rc = k.finish()) != WF_OK) return rc;
+  return st.end();
+}
+
 int set_search_config(ext_base* x, search_config& c, double lo, double hi, int n_passes, const int* K, int strict, int max_eval_farms,
                       int rows_per_candidate, const char* rows_msg) {
   if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) return ext_fail(x, WF_E_INVALID, "yaw bounds must be finite with lo < hi");
@@ -162,7 +223,6 @@ void pass_grids(double lo, double hi, int P, const int* K, WfGrid* grid) {
   }
 }
 
-
 int run_search(ext_base* x, yaw_search& s, evaluator& es, const search_policy& k, const float* yaw0, int n_farms, const int* farms,
                float* yaw_opt, float* power_opt, float* power_init, int on_device) {
   wf_handle* h = x->h;
@@ -185,15 +245,16 @@ int run_search(ext_base* x, yaw_search& s, evaluator& es, const search_policy& k
   if (rc == WF_OK) rc = reserve(x, s.d_best, (size_t)C * N);
   if (rc == WF_OK) rc = reserve(x, s.d_order, (size_t)C * N);
   if (rc == WF_OK && farms) rc = reserve(x, s.farms.d, (size_t)n_farms);
-  if (rc == WF_OK && !on_device && yaw0) rc = reserve(x, s.d_in, fn);
-  if (rc == WF_OK && !on_device) rc = reserve(x, s.d_out, fn + 2 * (size_t)n_farms);
   if (rc != WF_OK) return rc;
   if (farms && (rc = upload_farms(x, s.farms, farms, n_farms)) != WF_OK) return rc;
+  staging st(x, s.d_stage, on_device);
   const float* d_yaw0 = nullptr;
-  if ((rc = stage_in(x, s.d_in, yaw0, fn, on_device, &d_yaw0)) != WF_OK) return rc;
-  float* d_oyaw = out_ptr(yaw_opt, s.d_out, 0, on_device);
-  float* d_opow = out_ptr(power_opt, s.d_out, fn, on_device);
-  float* d_oini = out_ptr(power_init, s.d_out, fn + n_farms, on_device);
+  float *d_oyaw = nullptr, *d_opow = nullptr, *d_oini = nullptr;
+  st.in(yaw0, fn, &d_yaw0);
+  st.out(yaw_opt, fn, &d_oyaw);
+  st.out(power_opt, (size_t)n_farms, &d_opow);
+  st.out(power_init, (size_t)n_farms, &d_oini);
+  if ((rc = st.begin()) != WF_OK) return rc;
 
   WfGrid grid[WF_SEARCH_MAX_PASSES];
   pass_grids(cf.lo, cf.hi, cf.P, cf.K, grid);
@@ -225,13 +286,7 @@ int run_search(ext_base* x, yaw_search& s, evaluator& es, const search_policy& k
   }
   if (!detail) { rc = record(x); if (rc != WF_OK) return rc; }
   x->timed = true; x->per_chunk = detail ? 2 * (size_t)V + 2 : 0;
-  if (!on_device) {
-    WFX_HIP(x, hipMemcpyAsync(yaw_opt, d_oyaw, sizeof(float) * fn, hipMemcpyDeviceToHost, h->stream));
-    WFX_HIP(x, hipMemcpyAsync(power_opt, d_opow, sizeof(float) * n_farms, hipMemcpyDeviceToHost, h->stream));
-    WFX_HIP(x, hipMemcpyAsync(power_init, d_oini, sizeof(float) * n_farms, hipMemcpyDeviceToHost, h->stream));
-    WFX_HIP(x, hipStreamSynchronize(h->stream));
-  }
-  return WF_OK;
+  return st.end();
 }
 
 }  // namespace wfi

@@ -1,10 +1,10 @@
 // wf_robust_abi.hip — the C boundary of the robust extension (include/wfrobust.h): an object that belongs to a parent
 // handle, owns a member set, two evaluator handles and their device buffers, and enqueues a whole expected-power evaluation or
-// a whole robust coordinate search on the parent's stream: per chunk one lay-out kernel, per visit one wf_step on the
-// evaluator, one row-sum kernel and one advance kernel (wf_robust_kernels.hip).  Reads the parent (layout, model, wind,
-// kernel choice, resolve mode); stores nothing in it.  The object's scaffolding — base, buffers, the evaluators that follow
-// the parent, checks, events — and the search's driver (run_search: chunks, the visit loop, staging and copy-back) are the
-// extensions' shared layer (ext/wf_ext.h); for the search this file supplies the rows' wind and the launches.
+// a whole robust coordinate search on the parent's stream.  Both runs are the extensions' shared drivers' (ext/wf_ext.h):
+// the evaluation is a row run of M rows per farm (run_rows), the search a run_search — checks, chunks, the evaluators and
+// their steps, the visit loop, staging and copy-back, events.  This file supplies the rows' wind and the launches
+// (wf_robust_kernels.hip): a lay-out kernel per chunk, a row-sum kernel and an expectation or advance kernel after a step.
+// Reads the parent (layout, model, wind, kernel choice, resolve mode); stores nothing in it.
 #include "../../../include/wfrobust.h"
 #include "../ext/wf_ext.h"
 #include "wf_robust.h"
@@ -19,10 +19,9 @@ struct wf_robust : ext_base {
   int M = 0, frame = WF_ROBUST_FIXED;
   double members[2 * WF_ROBUST_MAX_MEMBERS] = {};
   dev_buf<double> d_members;
-  // configuration and the buffers of every search; wf_robust_evaluate uses its yaw and power blocks, farm list and staging too
+  // configuration and the buffers of every search; wf_robust_evaluate runs its rows in them and stages through them too
   yaw_search s;
-  dev_buf<double> d_rowsum, d_wind;  // [E], [2][E]
-  dev_buf<double> d_outd;            // staging for host callers: wf_robust_evaluate's double outputs
+  dev_buf<double> d_rowsum;  // [E]
   // the evaluators: [0] wf_robust_evaluate (R = 1), [1] wf_robust_optimize
   evaluator eval[2];
 };
@@ -90,69 +89,43 @@ int wf_robust_evaluate(wf_robust* r, const float* yaw, int n_farms, const int* f
                        double* expected_turbine_power, float* member_power, int on_device) {
   if (!r) return WF_E_INVALID;
   wf_handle* h = r->h;
-  int rc = check_parent(r, "expected power under uncertainty serves", "wf_robust_evaluate");
-  if (rc != WF_OK) return rc;
-  if (r->M <= 0) return ext_fail(r, WF_E_INVALID, no_members("wf_robust_evaluate"));
-  if ((rc = check_farms(r, &n_farms, farms)) != WF_OK) return rc;
   yaw_search& s = r->s;
-  const int N = h->N, M = r->M;
-  if (s.cfg.max_eval < M) return ext_fail(r, WF_E_INVALID, kRowsMsg);
-  WFX_ON_DEVICE(r);
-  int C = s.cfg.max_eval / M;
-  if (C > n_farms) C = n_farms;
-  const int E = C * M;
-  evaluator& es = r->eval[0];
-  rc = ensure_evaluator(r, es, E, s.cfg.strict ? 2 : h->resolve_mode);
-  if (rc != WF_OK) return rc;
-  const size_t en = (size_t)E * N, fn = (size_t)n_farms * N, fm = (size_t)n_farms * M;
-  rc = reserve(r, s.d_yaw, en);
-  if (rc == WF_OK) rc = reserve(r, s.d_pow, en);
-  if (rc == WF_OK) rc = reserve(r, r->d_rowsum, (size_t)E);
-  if (rc == WF_OK) rc = reserve(r, r->d_wind, 2 * (size_t)E);
-  if (rc == WF_OK && farms) rc = reserve(r, s.farms.d, (size_t)n_farms);
-  if (rc == WF_OK && !on_device && yaw) rc = reserve(r, s.d_in, fn);
-  if (rc == WF_OK && !on_device) rc = reserve(r, r->d_outd, fn + (size_t)n_farms);
-  if (rc == WF_OK && !on_device) rc = reserve(r, s.d_out, fm);
-  if (rc != WF_OK) return rc;
-  if (farms && (rc = upload_farms(r, s.farms, farms, n_farms)) != WF_OK) return rc;
+  const int N = h->N, M = r->M, wind_stride = h->wind_count == 1 ? 0 : 1;
   const float* d_yaw_in = nullptr;
-  if ((rc = stage_in(r, s.d_in, yaw, fn, on_device, &d_yaw_in)) != WF_OK) return rc;
-  double* d_exp = out_ptr(expected_power, r->d_outd, 0, on_device);
-  double* d_turb = out_ptr(expected_turbine_power, r->d_outd, n_farms, on_device);
-  float* d_mem = out_ptr(member_power, s.d_out, 0, on_device);
-  const int wind_stride = h->wind_count == 1 ? 0 : 1;
-  r->n_ev = 0; r->timed = false;
-  for (int base = 0; base < n_farms; base += C) {
-    const WfSlots sl = chunk_slots(s.farms, farms, base, n_farms, C);
-    if ((rc = record(r)) != WF_OK) return rc;
+  float* d_mem = nullptr;
+  double *d_exp = nullptr, *d_turb = nullptr;
+  staging st(r, s.d_stage, on_device);
+  row_policy k;
+  k.what = "expected power under uncertainty serves"; k.name = "wf_robust_evaluate";
+  k.rows = M; k.no_rows = no_members("wf_robust_evaluate"); k.rows_msg = kRowsMsg;
+  k.strict = s.cfg.strict; k.max_eval = s.cfg.max_eval; k.split_always = true;
+  k.reserve = [&](int, int E) -> int {
+    const size_t fn = (size_t)n_farms * N;
+    st.in(yaw, fn, &d_yaw_in); st.out(expected_power, (size_t)n_farms, &d_exp);
+    st.out(expected_turbine_power, fn, &d_turb); st.out(member_power, (size_t)n_farms * M, &d_mem);
+    return reserve(r, r->d_rowsum, (size_t)E);
+  };
+  k.layout = [&](const WfSlots& sl, int E) -> int {
     WfRobustLayoutArgs la{};
     la.sl = sl; la.mb = device_members(r); la.ws = h->d_ws; la.wd = h->d_wd; la.wind_stride = wind_stride; la.R = 1; la.N = N;
-    la.ews = r->d_wind; la.ewd = r->d_wind + E; la.write_yaw = 1;
-    la.yaw_in = d_yaw_in ? d_yaw_in + (size_t)base * N : nullptr; la.yaw = s.d_yaw;
+    la.ews = s.d_wind; la.ewd = s.d_wind + E; la.write_yaw = 1;
+    la.yaw_in = d_yaw_in ? d_yaw_in + (size_t)sl.base * N : nullptr; la.yaw = s.d_yaw;
     WFX_HIP(r, wfk_launch_robust_layout(&la, h->stream));
-    if ((rc = record(r)) != WF_OK) return rc;
-    WFX_EV(r, es.ev, wf_set_wind_counts(es.ev, la.ews, E, la.ewd, E, 1));
-    WFX_EV(r, es.ev, wf_step(es.ev, s.d_yaw, s.d_pow, nullptr, nullptr, nullptr, 1));
-    if ((rc = record(r)) != WF_OK) return rc;
+    return WF_OK;
+  };
+  k.reduce = [&](const WfSlots& sl, int E) -> int {
+    const size_t base = (size_t)sl.base;
     const WfRobustRowsumArgs sa{E, N, s.d_pow, r->d_rowsum};
     WFX_HIP(r, wfk_launch_robust_rowsum(&sa, h->stream));
     WfRobustExpectArgs xa{};
-    xa.sl = sl; xa.mb = la.mb; xa.N = N; xa.power = s.d_pow; xa.rowsum = r->d_rowsum;
+    xa.sl = sl; xa.mb = device_members(r); xa.N = N; xa.power = s.d_pow; xa.rowsum = r->d_rowsum;
     xa.expected = d_exp ? d_exp + base : nullptr;
-    xa.turbine = d_turb ? d_turb + (size_t)base * N : nullptr;
-    xa.member = d_mem ? d_mem + (size_t)base * M : nullptr;
+    xa.turbine = d_turb ? d_turb + base * N : nullptr;
+    xa.member = d_mem ? d_mem + base * M : nullptr;
     WFX_HIP(r, wfk_launch_robust_expect(&xa, h->stream));
-    if ((rc = record(r)) != WF_OK) return rc;
-  }
-  r->timed = true; r->per_chunk = 4;
-  if (!on_device) {
-    if (expected_power) WFX_HIP(r, hipMemcpyAsync(expected_power, r->d_outd, sizeof(double) * n_farms, hipMemcpyDeviceToHost, h->stream));
-    if (expected_turbine_power)
-      WFX_HIP(r, hipMemcpyAsync(expected_turbine_power, r->d_outd + n_farms, sizeof(double) * fn, hipMemcpyDeviceToHost, h->stream));
-    if (member_power) WFX_HIP(r, hipMemcpyAsync(member_power, s.d_out, sizeof(float) * fm, hipMemcpyDeviceToHost, h->stream));
-    WFX_HIP(r, hipStreamSynchronize(h->stream));
-  }
-  return WF_OK;
+    return WF_OK;
+  };
+  return run_rows(r, s, r->eval[0], k, st, &n_farms, farms);
 }
 
 int wf_robust_optimize(wf_robust* r, const float* yaw0, int n_farms, const int* farms, float* yaw_opt, float* power_opt,
@@ -164,13 +137,13 @@ int wf_robust_optimize(wf_robust* r, const float* yaw0, int n_farms, const int* 
   search_policy k{"robust yaw optimisation serves", "wf_robust_optimize", r->M, no_members("wf_robust_optimize"), kRowsMsg, nullptr, nullptr, nullptr};
   k.reserve = [&](int E) -> int {
     const int rc = reserve(r, r->d_rowsum, (size_t)E);
-    return rc == WF_OK ? reserve(r, r->d_wind, 2 * (size_t)E) : rc;
+    return rc == WF_OK ? reserve(r, r->s.d_wind, 2 * (size_t)E) : rc;
   };
   // every row's wind: its farm's speed and the farm's direction plus the member's offset — a wind per row; then the visit order
   k.begin_chunk = [&](const WfSlots& sl, int R, int E) -> int {
     WfRobustLayoutArgs la{};
     la.sl = sl; la.mb = device_members(r); la.ws = h->d_ws; la.wd = h->d_wd; la.wind_stride = wind_stride; la.R = R; la.N = h->N;
-    la.ews = r->d_wind; la.ewd = r->d_wind + E;
+    la.ews = r->s.d_wind; la.ewd = r->s.d_wind + E;
     WFX_HIP(r, wfk_launch_robust_layout(&la, h->stream));
     WFX_EV(r, es.ev, wf_set_wind_counts(es.ev, la.ews, E, la.ewd, E, 1));
     const WfRobustOrderArgs oa{{sl, h->d_lx, h->d_ly, h->xc, h->yc, h->d_wd, wind_stride, h->N, r->s.d_order}};

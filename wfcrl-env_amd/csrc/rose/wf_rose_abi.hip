@@ -1,9 +1,9 @@
 // wf_rose_abi.hip — the C boundary of the rose extension (include/wfrose.h): an object that belongs to a parent handle,
 // owns yaw tables, a rose, an evaluator handle and its device buffers, and enqueues a whole expected-power evaluation on the
-// parent's stream: per chunk one lay-out kernel, wf_set_wind_counts + wf_step on the evaluator, two reducing kernels
-// (wf_rose_kernels.hip).  Reads the parent (layout, model, wind, env parameters and yaw state, kernel choice, resolve
-// mode); stores nothing in it.  The object's scaffolding — base, buffers, the evaluator that follows the parent, checks,
-// events — is the extensions' shared layer (ext/wf_ext.h).
+// parent's stream.  The run is the extensions' shared row driver's (ext/wf_ext.h: run_rows — chunks, the evaluator and its
+// step, events), an item being one row: a (direction, case, speed); this file supplies the checks of the cases, their
+// upload, a chunk's lay-out kernel and two reducing kernels (wf_rose_kernels.hip) and the copy of the sums.  Reads the
+// parent (layout, model, wind, env parameters and yaw state, kernel choice, resolve mode); stores nothing in it.
 #include "../../../include/wfrose.h"
 #include "../ext/wf_ext.h"
 #include "wf_rose.h"
@@ -23,14 +23,13 @@ struct wf_rose : ext_base {
   double cut_in = 0.001, cut_out = 0.0;
   dev_buf<double> d_wd, d_ws, d_freq;
   // device buffers (grow-only)
-  dev_buf<double> d_ews, d_ewd, d_rowsum;  // [E]
-  dev_buf<float> d_yaw, d_pow;             // [E][N]
-  dev_buf<double> d_acc;                   // [C][N] then [C]
-  dev_buf<int> d_cases;                    // [2][C]
-  dev_buf<float> d_fixed, d_cond;          // staging for host callers
-  dev_buf<float> d_pol;                    // staging of wf_rose_policy: target, action
+  row_batch rows;            // E rows
+  dev_buf<double> d_rowsum;  // [E]
+  dev_buf<double> d_acc;     // [C][N] then [C]
+  dev_buf<int> d_cases;      // [2][C]
+  dev_buf<char> d_stage;     // staging for host callers: fixed_yaw, condition_power; wf_rose_policy's target, action
   std::vector<int> cases;  // host copy the upload reads from: [2][C]
-  evaluator eval;  // E rows; timing: four events per chunk (start | lay-out | wind + step | reduce)
+  evaluator eval;  // timing: four events per chunk (start | lay-out | wind + step | reduce)
 };
 
 namespace {
@@ -122,46 +121,48 @@ int wf_rose_evaluate(wf_rose* r, int n_cases, const int* case_kind, const int* c
                      double* weighted_power, double* weighted_turbine_power, float* condition_power, int on_device) {
   if (!r || !case_kind || !case_arg) return ext_fail(r, WF_E_INVALID, "wf_rose_evaluate: NULL argument");
   wf_handle* h = r->h;
-  int rc = check_parent(r, "a rose evaluation serves", nullptr);
-  if (rc != WF_OK) return rc;
-  if (r->D <= 0) return ext_fail(r, WF_E_INVALID, "no rose: wf_rose_set_rose comes first");
-  if (n_cases < 1 || n_cases > WF_ROSE_MAX_CASES) return ext_fail(r, WF_E_INVALID, "the number of cases must be in 1..64");
   const int N = h->N, C = n_cases, D = r->D, S = r->S;
-  int n_fixed = 0;
-  for (int c = 0; c < C; ++c) {
-    const int kind = case_kind[c], arg = case_arg[c];
-    if (kind == WF_ROSE_CASE_ZERO) continue;
-    if (kind == WF_ROSE_CASE_FIXED) {
-      if (arg < 0 || arg >= 65536) return ext_fail(r, WF_E_INVALID, "a fixed case names a row of fixed_yaw: 0 .. 65535");
-      if (!fixed_yaw) return ext_fail(r, WF_E_INVALID, "a fixed case needs fixed_yaw");
-      n_fixed = arg + 1 > n_fixed ? arg + 1 : n_fixed;
-    } else if (kind == WF_ROSE_CASE_TABLE) {
-      if (arg < 0 || arg >= WF_ROSE_SLOTS) return ext_fail(r, WF_E_INVALID, "table slot out of range (0 .. 3)");
-      if (r->slot[arg].Dt <= 0) return ext_fail(r, WF_E_INVALID, "no yaw table in that slot: wf_rose_set_table comes first");
-      if (r->slot[arg].N != N) return ext_fail(r, WF_E_INVALID, "the yaw table was set for another turbine count: set it again");
-    } else {
-      return ext_fail(r, WF_E_INVALID, "unknown case kind (WF_ROSE_CASE_ZERO / _FIXED / _TABLE)");
+  const size_t cn = (size_t)C * N;
+  row_batch& b = r->rows;
+  int n_fixed = 0, R = 0;  // rows of fixed_yaw the cases name; rows of the run
+  staging st(r, r->d_stage, on_device);
+  WfRoseLayoutArgs la{};
+  WfRoseReduceArgs ra{};
+  row_policy k;
+  k.what = "a rose evaluation serves"; k.name = nullptr;
+  k.by_farm = false; k.split_always = true;
+  k.strict = r->strict; k.max_eval = r->max_eval;
+  k.check = [&]() -> int {
+    if (D <= 0) return ext_fail(r, WF_E_INVALID, "no rose: wf_rose_set_rose comes first");
+    if (C < 1 || C > WF_ROSE_MAX_CASES) return ext_fail(r, WF_E_INVALID, "the number of cases must be in 1..64");
+    for (int c = 0; c < C; ++c) {
+      const int kind = case_kind[c], arg = case_arg[c];
+      if (kind == WF_ROSE_CASE_ZERO) continue;
+      if (kind == WF_ROSE_CASE_FIXED) {
+        if (arg < 0 || arg >= 65536) return ext_fail(r, WF_E_INVALID, "a fixed case names a row of fixed_yaw: 0 .. 65535");
+        if (!fixed_yaw) return ext_fail(r, WF_E_INVALID, "a fixed case needs fixed_yaw");
+        n_fixed = arg + 1 > n_fixed ? arg + 1 : n_fixed;
+      } else if (kind == WF_ROSE_CASE_TABLE) {
+        if (arg < 0 || arg >= WF_ROSE_SLOTS) return ext_fail(r, WF_E_INVALID, "table slot out of range (0 .. 3)");
+        if (r->slot[arg].Dt <= 0) return ext_fail(r, WF_E_INVALID, "no yaw table in that slot: wf_rose_set_table comes first");
+        if (r->slot[arg].N != N) return ext_fail(r, WF_E_INVALID, "the yaw table was set for another turbine count: set it again");
+      } else {
+        return ext_fail(r, WF_E_INVALID, "unknown case kind (WF_ROSE_CASE_ZERO / _FIXED / _TABLE)");
+      }
     }
-  }
-  const long long rows = (long long)D * C * S;
-  if (rows > (1LL << 30) / (N + 1)) return ext_fail(r, WF_E_INVALID, "too many rows: directions x cases x speeds x turbines must stay below 2^30");
-  WFX_ON_DEVICE(r);
-  const int R = (int)rows;
-  const int E = R < r->max_eval ? R : r->max_eval;
-  if ((rc = ensure_evaluator(r, r->eval, E, r->strict ? 2 : h->resolve_mode)) != WF_OK) return rc;
-  wf_handle* ev = r->eval.ev;
-  const size_t en = (size_t)E * N, cn = (size_t)C * N, cds = (size_t)C * D * S;
-  rc = reserve(r, r->d_ews, (size_t)E);
-  if (rc == WF_OK) rc = reserve(r, r->d_ewd, (size_t)E);
-  if (rc == WF_OK) rc = reserve(r, r->d_rowsum, (size_t)E);
-  if (rc == WF_OK) rc = reserve(r, r->d_yaw, en);
-  if (rc == WF_OK) rc = reserve(r, r->d_pow, en);
-  if (rc == WF_OK) rc = reserve(r, r->d_acc, cn + C);
-  if (rc == WF_OK) rc = reserve(r, r->d_cases, 2 * (size_t)C);
-  if (rc == WF_OK && !on_device && n_fixed) rc = reserve(r, r->d_fixed, (size_t)n_fixed * N);
-  if (rc == WF_OK && !on_device && condition_power) rc = reserve(r, r->d_cond, cds);
-  if (rc != WF_OK) return rc;
-  {  // the case list: uploaded when it differs from the one the device holds
+    const long long rows = (long long)D * C * S;
+    if (rows > (1LL << 30) / (N + 1)) return ext_fail(r, WF_E_INVALID, "too many rows: directions x cases x speeds x turbines must stay below 2^30");
+    R = (int)rows;
+    return WF_OK;
+  };
+  k.reserve = [&](int, int E) -> int {
+    st.in(n_fixed ? fixed_yaw : nullptr, (size_t)n_fixed * N, &la.fixed_yaw);
+    st.out(condition_power, (size_t)R, &ra.condition_power);
+    int rc = reserve(r, r->d_rowsum, (size_t)E);
+    if (rc == WF_OK) rc = reserve(r, r->d_acc, cn + C);
+    if (rc == WF_OK) rc = reserve(r, r->d_cases, 2 * (size_t)C);
+    if (rc != WF_OK) return rc;
+    // the case list: uploaded when it differs from the one the device holds
     std::vector<int> cs(2 * (size_t)C);
     for (int c = 0; c < C; ++c) { cs[c] = case_kind[c]; cs[C + c] = case_arg[c]; }
     if (cs != r->cases) {
@@ -169,44 +170,32 @@ int wf_rose_evaluate(wf_rose* r, int n_cases, const int* case_kind, const int* c
       r->cases.swap(cs);
       WFX_HIP(r, hipMemcpyAsync(r->d_cases, r->cases.data(), sizeof(int) * 2 * C, hipMemcpyHostToDevice, h->stream));
     }
-  }
-  const float* d_fixed = fixed_yaw;
-  if (!on_device && n_fixed) {
-    WFX_HIP(r, hipMemcpyAsync(r->d_fixed, fixed_yaw, sizeof(float) * n_fixed * N, hipMemcpyHostToDevice, h->stream));
-    d_fixed = r->d_fixed;
-  }
-  WfRoseLayoutArgs la{};
-  la.wd = r->d_wd; la.ws = r->d_ws; la.cases = r->d_cases; la.fixed_yaw = n_fixed ? d_fixed : nullptr;
-  for (int i = 0; i < WF_ROSE_SLOTS; ++i) la.tab[i] = device_table(r->slot[i]);
-  la.ews = r->d_ews; la.ewd = r->d_ewd; la.yaw = r->d_yaw;
-  WfRoseReduceArgs ra{};
-  ra.ws = r->d_ws; ra.freq = r->d_freq; ra.cut_in = r->cut_in; ra.cut_out = r->cut_out;
-  ra.power = r->d_pow; ra.rowsum = r->d_rowsum;
-  ra.condition_power = out_ptr(condition_power, r->d_cond, 0, on_device);
-  ra.acc_turbine = r->d_acc; ra.acc_farm = r->d_acc + cn;
-  r->n_ev = 0; r->timed = false;
-  for (int row0 = 0; row0 < R; row0 += E) {
-    const WfRoseShape sh{D, C, S, N, row0, R - row0 < E ? R - row0 : E, E};
-    la.sh = sh; ra.sh = sh; ra.first = row0 == 0;
-    if ((rc = record(r)) != WF_OK) return rc;
+    la.wd = r->d_wd; la.ws = r->d_ws; la.cases = r->d_cases;
+    for (int i = 0; i < WF_ROSE_SLOTS; ++i) la.tab[i] = device_table(r->slot[i]);
+    la.ews = b.d_wind; la.ewd = b.d_wind + E; la.yaw = b.d_yaw;
+    ra.ws = r->d_ws; ra.freq = r->d_freq; ra.cut_in = r->cut_in; ra.cut_out = r->cut_out;
+    ra.power = b.d_pow; ra.rowsum = r->d_rowsum;
+    ra.acc_turbine = r->d_acc; ra.acc_farm = r->d_acc + cn;
+    return WF_OK;
+  };
+  k.layout = [&](const WfSlots& sl, int E) -> int {
+    la.sh = WfRoseShape{D, C, S, N, sl.base, sl.n_slots, E};
     WFX_HIP(r, wfk_launch_rose_layout(&la, h->stream));
-    if ((rc = record(r)) != WF_OK) return rc;
-    WFX_EV(r, ev, wf_set_wind_counts(ev, r->d_ews, E, r->d_ewd, E, 1));
-    WFX_EV(r, ev, wf_step(ev, r->d_yaw, r->d_pow, nullptr, nullptr, nullptr, 1));
-    if ((rc = record(r)) != WF_OK) return rc;
+    return WF_OK;
+  };
+  k.reduce = [&](const WfSlots& sl, int) -> int {
+    ra.sh = la.sh; ra.first = sl.base == 0;
     WFX_HIP(r, wfk_launch_rose_rowsum(&ra, h->stream));
     WFX_HIP(r, wfk_launch_rose_accumulate(&ra, h->stream));
-    if ((rc = record(r)) != WF_OK) return rc;
-  }
-  r->timed = true; r->per_chunk = 4;
-  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (weighted_power) WFX_HIP(r, hipMemcpyAsync(weighted_power, r->d_acc + cn, sizeof(double) * C, kind, h->stream));
-  if (weighted_turbine_power) WFX_HIP(r, hipMemcpyAsync(weighted_turbine_power, r->d_acc, sizeof(double) * cn, kind, h->stream));
-  if (!on_device) {
-    if (condition_power) WFX_HIP(r, hipMemcpyAsync(condition_power, r->d_cond, sizeof(float) * cds, hipMemcpyDeviceToHost, h->stream));
-    WFX_HIP(r, hipStreamSynchronize(h->stream));
-  }
-  return WF_OK;
+    return WF_OK;
+  };
+  k.finish = [&]() -> int {
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (weighted_power) WFX_HIP(r, hipMemcpyAsync(weighted_power, r->d_acc + cn, sizeof(double) * C, kind, h->stream));
+    if (weighted_turbine_power) WFX_HIP(r, hipMemcpyAsync(weighted_turbine_power, r->d_acc, sizeof(double) * cn, kind, h->stream));
+    return WF_OK;
+  };
+  return run_rows(r, b, r->eval, k, st, &R, nullptr);
 }
 
 int wf_rose_policy(wf_rose* r, int slot, float* target_yaw, float* action, int on_device) {
@@ -222,21 +211,17 @@ int wf_rose_policy(wf_rose* r, int slot, float* target_yaw, float* action, int o
   if (!h->d_env_yaw) return ext_fail(r, WF_E_INVALID, "no env state: wf_env_config and wf_env_reset come first");
   WFX_ON_DEVICE(r);
   const size_t bn = (size_t)h->B * h->N;
-  if (!on_device && (rc = reserve(r, r->d_pol, 2 * bn)) != WF_OK) return rc;
+  staging st(r, r->d_stage, on_device);
   WfRosePolicyArgs pa{};
+  st.out(target_yaw, bn, &pa.target);
+  st.out(action, bn, &pa.action);
+  if ((rc = st.begin()) != WF_OK) return rc;
   pa.tab = device_table(r->slot[slot]);
   pa.B = h->B; pa.N = h->N; pa.wind_stride = h->wind_count == h->B ? 1 : 0;
   pa.ws = h->d_ws; pa.wd = h->d_wd; pa.yaw_state = h->d_env_yaw;
   pa.lo = h->env.yaw_lo; pa.hi = h->env.yaw_hi; pa.step = h->env.yaw_step; pa.discrete = h->env.discrete;
-  pa.target = out_ptr(target_yaw, r->d_pol, 0, on_device);
-  pa.action = out_ptr(action, r->d_pol, bn, on_device);
   WFX_HIP(r, wfk_launch_rose_policy(&pa, h->stream));
-  if (!on_device) {
-    if (target_yaw) WFX_HIP(r, hipMemcpyAsync(target_yaw, r->d_pol, sizeof(float) * bn, hipMemcpyDeviceToHost, h->stream));
-    if (action) WFX_HIP(r, hipMemcpyAsync(action, r->d_pol + bn, sizeof(float) * bn, hipMemcpyDeviceToHost, h->stream));
-    WFX_HIP(r, hipStreamSynchronize(h->stream));
-  }
-  return WF_OK;
+  return st.end();
 }
 
 // per chunk: e0 | lay-out e1 | wind + step e2 | reduce e3, then the next chunk's e0

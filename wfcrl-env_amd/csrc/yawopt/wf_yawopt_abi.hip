@@ -16,9 +16,8 @@ static_assert(WF_YAWOPT_MAX_PASSES == WF_SEARCH_MAX_PASSES && WF_YAWOPT_MAX_K0 =
 static const char* const kRowsMsg = "max_eval_farms must hold one farm's candidates: at least K_max + 1";
 
 struct wf_yawopt : ext_base {
-  yaw_search s;            // configuration and the buffers of every search
-  dev_buf<double> d_wind;  // [2][C R]
-  evaluator eval;          // C x R farms
+  yaw_search s;    // configuration and the buffers of every search; its wind [2][C R] is filled for per-farm winds only
+  evaluator eval;  // C x R farms
 };
 
 extern "C" {
@@ -44,14 +43,14 @@ int wf_yawopt_run(wf_yawopt* o, const float* yaw0, int n_farms, const int* farms
   wf_handle* h = o->h;
   const bool per_farm = h->wind_count == h->B && h->B > 1;
   search_policy k{"yaw optimisation serves", "wf_yawopt_run", 1, "", kRowsMsg, nullptr, nullptr, nullptr};
-  k.reserve = [&](int E) -> int { return per_farm ? reserve(o, o->d_wind, 2 * (size_t)E) : WF_OK; };
+  k.reserve = [&](int E) -> int { return per_farm ? reserve(o, o->s.d_wind, 2 * (size_t)E) : WF_OK; };
   // the evaluator's wind: the parent's one wind as it is, or each farm's wind repeated over its rows; then the visit order
   k.begin_chunk = [&](const WfSlots& sl, int R, int E) -> int {
     wf_handle* ev = o->eval.ev;
     if (!per_farm) {
       if (sl.base == 0) WFX_EV(o, ev, wf_set_wind_counts(ev, h->d_ws, 1, h->d_wd, 1, 1));
     } else {
-      WfYawoptWindArgs wa{sl, h->d_ws, h->d_wd, R, o->d_wind, o->d_wind + E};
+      WfYawoptWindArgs wa{sl, h->d_ws, h->d_wd, R, o->s.d_wind, o->s.d_wind + E};
       WFX_HIP(o, wfk_launch_yawopt_wind(&wa, h->stream));
       // (a parent whose farms share ONE direction keeps the shared geometry and the pair-table path on the evaluator too)
       if (h->shared_dir) WFX_EV(o, ev, wf_set_wind_counts(ev, wa.ews, E, h->d_wd, 1, 1));
