@@ -1,4 +1,4 @@
-"""What tools/yawopt_timing.py, robust_timing.py, grad_timing.py and credit_timing.py share: the plain wf_step loop on an extension object's own
+"""What tools/yawopt_timing.py, robust_timing.py, grad_timing.py, credit_timing.py and lookahead_timing.py share: the plain wf_step loop on an extension object's own
 evaluator handle — the baseline their totals are divided by."""
 import ctypes as C
 

@@ -567,6 +567,48 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the credit kernels as the runtime reports them."""
         return self._credit().kernel_info()
 
+    # -- multi-step look-ahead returns of action sequences (include/wflookahead.h) ---------------------
+    def _lookahead(self) -> "_Lookahead":
+        """The handle's lookahead object; created on first use, destroyed in close() before the handle."""
+        lo = getattr(self, "_lookahead_obj", None)
+        if lo is None:
+            lo = self._lookahead_obj = _Lookahead(self)
+        return lo
+
+    def lookahead_returns(self, actions, gamma=1.0, wind=None, farms=None, strict=False, max_eval_farms=65536,
+                          want=("returns", "best"), out=None):
+        """The discounted return the fused env would pay over the next H steps for each of K candidate action sequences,
+        from the env state the handle holds, which is read and never changed (include/wflookahead.h; the project's own
+        definition, PARITY UNPINNED beyond the oracle): the step's own transition (budget gate, increment, clip, accumulator,
+        move counter) walks every sequence, the K H yaws of a farm are rows of one batched step, each row's reward is
+        mean_j(P_j [MW] 1e3 / wr^3) - load_coef mean|loads| in float64 with wr the free-stream speed before that step, and
+        ret = sum_h gamma^h r_h added in ascending h.
+          actions    (n_farms, K, H, N) float32 in the env's encoding under env_config (block i belongs to farms[i]) — torch
+                     CUDA tensor or NumPy; 1 <= H <= 64, K H <= 4096
+          gamma      discount in [0, 1]
+          wind       (n_farms, H, 2) float64 (speed, direction) the wind step h is solved under, or None: the handle's
+                     current wind held over the horizon (also in series mode: the series' coming rows are not read)
+          farms      farm indices (any order), or None: every farm of the batch
+          strict     every row is solved in float64; otherwise the handle's own resolve mode.  Returns closer than the sum
+                     of their rows' tolerances are not ordered reliably in the default mode
+          max_eval_farms  rows the evaluator handle may hold, K H per farm: longer lists run in chunks
+          want       of "returns" (n, K) float64, "rewards" (n, K, H) float64, "farm_power" (n, K, H) float64 [W],
+                     "final_yaw" (n, K, N) float32 — the yaw after step H - 1 —, "best" (n,) int32 — the sequence of the
+                     largest return, the lowest index among equal maxima
+          out        dict of tensors / arrays of those names to write into
+        Step 0 is normalised by the speed the next env_step would normalise by (env_set_prev_wind is read, not consumed).
+        Deterministic: fixed summation order, no atomics.  With torch tensors the call only enqueues work on torch's current
+        stream.  HipFlorisInterface has no such method: its MDP state lives in the host-side mdp.py, not in the handle."""
+        return self._lookahead().run(actions, gamma, wind, farms, strict, max_eval_farms, want, out)
+
+    def lookahead_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last lookahead_returns {"total_ms", "step_ms", "glue_ms"}."""
+        return self._lookahead().timing(detail)
+
+    def lookahead_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the lookahead kernels as the runtime reports them."""
+        return self._lookahead().kernel_info()
+
     # -- wind-rose expected power and the yaw look-up table (include/wfrose.h) -------------------------
     def _rose(self) -> "_Rose":
         """The handle's rose object; created on first use, destroyed in close() before the handle."""
@@ -872,8 +914,9 @@ class WfStep:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h,
-            # wfcredit.h)
-            for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj"):
+            # wfcredit.h, wflookahead.h)
+            for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
+                         "_lookahead_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
                     ext.close()
@@ -889,7 +932,7 @@ class WfStep:
 
 
 class _Ext:
-    """An extension object of a WfStep handle — the `wf_<NAME>` of include/wf<NAME>.h — and what the six wrappers share:
+    """An extension object of a WfStep handle — the `wf_<NAME>` of include/wf<NAME>.h — and what the seven wrappers share:
     create / close, timing, kernel_info, evaluator, and the conversion of farm lists, (n, N) float32 rows and output dicts
     into the pointers the C ABI takes.  `_r` is the raw object, `KERNELS` names kernel_info's entries in the library's order."""
 
@@ -1306,4 +1349,54 @@ class _Credit(_Ext):
         p = dict(zip(spec, ptrs))
         self._call("run", self.KIND[base_kind], bptr, self.KIND[alt_kind], aptr, K, n, fptr, p.get("reward"), p.get("farm_power"),
                    p.get("difference"), int(on_device))
+        return {k: out[k] for k in spec}
+
+
+class _Lookahead(_Ext):
+    """The `wf_lookahead` object of a WfStep handle (include/wflookahead.h)."""
+
+    NAME = "lookahead"
+    KERNELS = ("layout", "reduce")
+    OUTPUTS = ("returns", "rewards", "farm_power", "final_yaw", "best")
+
+    def run(self, actions, gamma, wind, farms, strict, max_eval_farms, want, out):
+        w = self._w
+        N = w.num_turbines
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.OUTPUTS for k in want):
+            raise ValueError("want must name returns, rewards, farm_power, final_yaw and / or best")
+        self._call("config", int(bool(strict)), int(max_eval_farms or 0))
+        fa, n, fptr = self._farms(farms)
+        on_device = _is_torch(actions)
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            assert actions.is_cuda and actions.dtype == torch.float32, "actions"
+            actions = actions.contiguous()
+        else:
+            actions = np.ascontiguousarray(actions, dtype=np.float32)
+        shape = tuple(actions.shape)
+        if len(shape) != 4 or shape[0] != n or shape[3] != N:
+            raise ValueError("actions must be (n_farms, K, H, num_turbines): K sequences of H joint actions per listed farm")
+        K, H = int(shape[1]), int(shape[2])
+        wptr = None
+        if wind is not None:
+            if on_device:
+                if not _is_torch(wind):
+                    wind = torch.as_tensor(np.asarray(wind, np.float64), device=actions.device)
+                assert wind.is_cuda and wind.dtype == torch.float64, "wind"
+                wind = wind.contiguous()
+            else:
+                wind = np.ascontiguousarray(wind, dtype=np.float64)
+            if tuple(wind.shape) != (n, H, 2):
+                raise ValueError("wind must be (n_farms, H, 2): the (speed, direction) every step of the horizon is solved under")
+            wptr = wind.data_ptr() if on_device else wind.ctypes.data
+        shapes = {"returns": ((n, K), np.float64), "rewards": ((n, K, H), np.float64), "farm_power": ((n, K, H), np.float64),
+                  "final_yaw": ((n, K, N), np.float32), "best": ((n,), np.int32)}
+        spec = {k: shapes[k] for k in self.OUTPUTS if k in want}
+        out, ptrs = self._outputs(out, spec, on_device, actions)
+        p = dict(zip(spec, ptrs))
+        self._call("run", actions.data_ptr() if on_device else actions.ctypes.data, K, H, wptr, float(gamma), n, fptr,
+                   *[p.get(k) for k in self.OUTPUTS], int(on_device))
         return {k: out[k] for k in spec}

@@ -12,13 +12,8 @@
 #include "../../../include/wfcredit.h"
 #include "../ext/wf_ext_kernels.h"
 
-// the parent's env: parameters by value, state by (read-only) pointer
-struct WfCreditEnv {
-  const float *yaw, *acc;  // [B][N], or null: no env state
-  const int* moves;        // [B]
-  float lo, hi, step, rate, dt, budget;
-  int discrete;
-};
+// the parent's env: parameters by value, state by (read-only) pointer (ext/wf_ext_kernels.h)
+typedef WfEnvView WfCreditEnv;
 
 struct WfCreditLayoutArgs {
   WfSlots sl;

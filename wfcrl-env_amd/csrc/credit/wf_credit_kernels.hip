@@ -18,6 +18,7 @@
 //                            on consecutive doubles; a row whose alternative has the bits of the base entry (read back from the
 //                            evaluator's yaw block) gets row 0's values and a difference of exactly 0.0.
 //
+// The transition and the tile loop are wf_env_transition and wf_staged_row_rewards (ext/wf_ext_kernels.h), shared with lookahead/.
 // T is what 24 KiB of LDS holds (15 rows at N = 80, 4 at N = 256, every row of a farm of 7 with K = 3); with the two [R]
 // arrays a block stays below 57 KiB.  Trip counts are run-time values: no private segment, no spill (tests/test_credit.py
 // reads the metadata); every barrier sits in block-uniform control flow.  The library is built with -ffp-contract=off: the
@@ -25,20 +26,6 @@
 #include <hip/hip_runtime.h>
 
 #include "wf_credit.h"
-
-namespace {
-
-// The fused env step's transition (wf_kernels.hip: "fused MDP transition"), the same float32 operations in the same order;
-// nothing is written back.
-__device__ __forceinline__ float cr_transition(const WfCreditEnv& e, float y, float a, float acc, int moves_new) {
-  const float frac = __fdiv_rn(__fdiv_rn(__fdiv_rn(acc, e.rate), (float)moves_new), e.dt);
-  if (frac >= e.budget) a = 0.0f;  // the gate zeroes the RAW action: "down" in the discrete encoding (the reference's quirk)
-  if (e.discrete) a = (a - 1.0f) * e.step;
-  if (!e.discrete) a = fminf(fmaxf(a, -e.step), e.step);
-  return fminf(fmaxf(y + a, e.lo), e.hi);
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void wf_credit_layout_kernel(const WfCreditLayoutArgs a) {
   extern __shared__ float cr_lay[];  // [N][K + 1]: the base yaw, then the K alternatives, of every turbine
@@ -66,7 +53,8 @@ __global__ __launch_bounds__(256) void wf_credit_layout_kernel(const WfCreditLay
       kind = a.alt_kind;
       v = a.alt ? a.alt[(in0 + t) * K + (k - 1)] : (kind == WF_CREDIT_ACTION && a.env.discrete ? 1.0f : 0.0f);  // hold / zero yaw
     }
-    if (kind == WF_CREDIT_ACTION) v = cr_transition(a.env, a.env.yaw[st0 + t], v, a.env.acc[st0 + t], moves_new);
+    float da;  // (the accumulator is not carried: one step)
+    if (kind == WF_CREDIT_ACTION) v = wf_env_transition(a.env, a.env.yaw[st0 + t], v, a.env.acc[st0 + t], moves_new, da);
     cr_lay[q] = v;
   }
   __syncthreads();
@@ -86,7 +74,7 @@ __global__ __launch_bounds__(256) void wf_credit_layout_kernel(const WfCreditLay
 __global__ __launch_bounds__(256) void wf_credit_reduce_kernel(const WfCreditReduceArgs a, int T, int sp, int sl) {
   extern __shared__ double cr_red[];
   const int tid = threadIdx.x, nth = blockDim.x;
-  const int N = a.N, K = a.K, N4 = 4 * N, R = 1 + N * K;
+  const int N = a.N, K = a.K, R = 1 + N * K;
   double* rw = cr_red;                                // [R] row rewards
   double* ps = cr_red + R;                            // [R] row farm powers
   float* pw = reinterpret_cast<float*>(cr_red + 2 * R);  // [T][sp] a tile's powers
@@ -95,35 +83,9 @@ __global__ __launch_bounds__(256) void wf_credit_reduce_kernel(const WfCreditRed
   const int b = wf_slot_farm(a.sl, slot);
   const double wr = a.ws_prev ? a.ws_prev[b] : a.ws[(size_t)b * a.wind_stride];
   const float* __restrict__ pblk = a.power_ev + (size_t)slot * R * N;
-  const float* __restrict__ lblk = a.load_ev + (size_t)slot * R * N4;
-  for (int r0 = 0; r0 < R; r0 += T) {  // (block-uniform)
-    int nt = R - r0;
-    nt = nt > T ? T : nt;
-    const float* __restrict__ psrc = pblk + (size_t)r0 * N;
-    const int n_p = nt * N;
-    for (int q = tid; q < n_p; q += nth) {
-      const int r = q / N, t = q - r * N;
-      pw[r * sp + t] = psrc[q];
-    }
-    const float* __restrict__ lsrc = lblk + (size_t)r0 * N4;
-    const int n_l = nt * N4;
-    for (int q = tid; q < n_l; q += nth) {
-      const int r = q / N4, t = q - r * N4;
-      ld[r * sl + t] = lsrc[q];
-    }
-    __syncthreads();
-    if (tid < nt) {
-      const float* prow = pw + tid * sp;
-      const float* lrow = ld + tid * sl;
-      double psum = 0.0, lsum = 0.0;
-      for (int t = 0; t < N; ++t) psum += (double)prow[t];
-      for (int t = 0; t < N4; ++t) lsum += fabs((double)lrow[t]);
-      // wf_resolve.hip: res_outputs — psum / n / 1e6 * 1e3 / wr^3 - load_coef lsum / (4 n)
-      rw[r0 + tid] = psum / N / 1.0e6 * 1.0e3 / (wr * wr * wr) - (double)a.load_coef * lsum / (4.0 * N);
-      ps[r0 + tid] = psum;
-    }
-    __syncthreads();  // (the next tile overwrites pw / ld; after the last one rw / ps are complete)
-  }
+  const float* __restrict__ lblk = a.load_ev + (size_t)slot * R * 4 * N;
+  wf_staged_row_rewards(pblk, lblk, R, N, T, sp, sl, a.load_coef, pw, ld, [wr](int) { return wr; },
+                        [rw, ps](int row, double r, double psum) { rw[row] = r; ps[row] = psum; });
   const float* __restrict__ yblk = a.yaw_ev + (size_t)slot * R * N;
   const size_t o_row = (size_t)slot * R, o_dif = (size_t)slot * N * K;
   const double r_base = rw[0], p_base = ps[0];
@@ -147,14 +109,11 @@ extern "C" hipError_t wfk_launch_credit_layout(const WfCreditLayoutArgs* a, hipS
   return hipGetLastError();
 }
 extern "C" hipError_t wfk_launch_credit_reduce(const WfCreditReduceArgs* a, hipStream_t s) {
-  const int N = a->N, R = 1 + N * a->K, sp = N | 1, sl = (4 * N) | 1;
+  const int N = a->N, R = 1 + N * a->K;
   const int threads = R * N <= 512 ? 64 : 256;
-  int T = 6144 / (sp + sl);  // rows per tile: [T][sp] + [T][sl] floats in 24 KiB of LDS, at most a row per thread
-  T = T < 1 ? 1 : T;
-  T = T > R ? R : T;
-  T = T > threads ? threads : T;
-  const size_t lds = sizeof(double) * 2 * (size_t)R + sizeof(float) * (size_t)T * (sp + sl);
-  hipLaunchKernelGGL(wf_credit_reduce_kernel, dim3(a->sl.n_slots), dim3(threads), lds, s, *a, T, sp, sl);
+  const WfRewardTile t = wf_reward_tile(R, N, threads);
+  const size_t lds = sizeof(double) * 2 * (size_t)R + t.lds_bytes;
+  hipLaunchKernelGGL(wf_credit_reduce_kernel, dim3(a->sl.n_slots), dim3(threads), lds, s, *a, t.T, t.sp, t.sl);
   return hipGetLastError();
 }
 extern "C" hipError_t wfk_credit_func_attributes(int kernel, hipFuncAttributes* a) {

@@ -1,6 +1,7 @@
-// wf_ext_kernels.h — the device side the extensions share (yawopt/, robust/, rose/, grad/): which farm a chunk's slot works
-// on, a visit's candidate grid, the visit order of a slot's turbines, the phases the two searches' advance kernels have in
-// common, and the staged row sum of the rose and the robust search.  The per-extension headers build their kernels'
+// wf_ext_kernels.h — the device side the extensions share (yawopt/, robust/, rose/, grad/, credit/, lookahead/): which farm a
+// chunk's slot works on, a visit's candidate grid, the visit order of a slot's turbines, the phases the two searches' advance
+// kernels have in common, the fused env's transition and the staged row rewards of credit and lookahead, and the staged row
+// sum of the rose and the robust search.  The per-extension headers build their kernels'
 // argument structs from these; wf_ext.h is the host side.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -164,6 +165,82 @@ __device__ __forceinline__ int wf_advance_candidates(const WfAdvanceArgs& a, int
 // after the last visit: the slot's best yaw is the answer
 __device__ __forceinline__ void wf_advance_write_best(const WfAdvanceArgs& a, int slot, int lane, const float* brow) {
   for (int t = lane; t < a.N; t += 64) a.out_yaw[(size_t)slot * a.N + t] = brow[t];
+}
+
+// ---- the fused env as the kernels of credit/ and lookahead/ see it: parameters by value, state by (read-only) pointer ----
+struct WfEnvView {
+  const float *yaw, *acc;  // [B][N], or null: no env state
+  const int* moves;        // [B]
+  float lo, hi, step, rate, dt, budget;
+  int discrete;
+};
+
+// The fused env step's transition (wf_kernels.hip: "fused MDP transition"), the same float32 operations in the same order;
+// nothing is written back.  Returns the new yaw; `da` is the increment the accumulator grows by (|da|).
+__device__ __forceinline__ float wf_env_transition(const WfEnvView& e, float y, float a, float acc, int moves_new, float& da) {
+  const float frac = __fdiv_rn(__fdiv_rn(__fdiv_rn(acc, e.rate), (float)moves_new), e.dt);
+  if (frac >= e.budget) a = 0.0f;  // the gate zeroes the RAW action: "down" in the discrete encoding (the reference's quirk)
+  if (e.discrete) a = (a - 1.0f) * e.step;
+  if (!e.discrete) a = fminf(fmaxf(a, -e.step), e.step);
+  da = a;
+  return fminf(fmaxf(y + a, e.lo), e.hi);
+}
+
+// ---- the staged row rewards (wf_credit_reduce_kernel, wf_lookahead_reduce_kernel): ONE WORKGROUP PER SLOT, every thread of
+// the block calls it.  The slot's R rows go by in TILES of T rows: a tile's [T][N] powers and [T][4 N] load values are
+// contiguous at pblk / lblk and are staged in pw [T][sp] / ld [T][sl] with coalesced loads (odd row strides: no bank conflict
+// when a lane walks a row, as wf_staged_rowsum below).  Then thread k < T adds row k in float64 — the powers in caller order,
+// the absolute load values in memory order — and hands the row's reward and farm power to keep(row, reward, psum), which
+// leaves them in the kernel's [R] doubles in LDS (or, consecutive threads being on consecutive rows, in the caller's array).
+// wr_of(row) is the speed the row's reward is normalised by.  After the last tile's barrier what `keep` stored is visible
+// to the block.  Every barrier sits in block-uniform control flow. ----
+template <class WR, class KEEP>
+__device__ __forceinline__ void wf_staged_row_rewards(const float* __restrict__ pblk, const float* __restrict__ lblk, int R, int N, int T,
+                                                      int sp, int sl, float load_coef, float* pw, float* ld, WR wr_of, KEEP keep) {
+  const int tid = threadIdx.x, nth = blockDim.x, N4 = 4 * N;
+  for (int r0 = 0; r0 < R; r0 += T) {  // (block-uniform)
+    int nt = R - r0;
+    nt = nt > T ? T : nt;
+    const float* __restrict__ psrc = pblk + (size_t)r0 * N;
+    const int n_p = nt * N;
+    for (int q = tid; q < n_p; q += nth) {
+      const int r = q / N, t = q - r * N;
+      pw[r * sp + t] = psrc[q];
+    }
+    const float* __restrict__ lsrc = lblk + (size_t)r0 * N4;
+    const int n_l = nt * N4;
+    for (int q = tid; q < n_l; q += nth) {
+      const int r = q / N4, t = q - r * N4;
+      ld[r * sl + t] = lsrc[q];
+    }
+    __syncthreads();
+    if (tid < nt) {
+      const float* prow = pw + tid * sp;
+      const float* lrow = ld + tid * sl;
+      double psum = 0.0, lsum = 0.0;
+      for (int t = 0; t < N; ++t) psum += (double)prow[t];
+      for (int t = 0; t < N4; ++t) lsum += fabs((double)lrow[t]);
+      const double wr = wr_of(r0 + tid);
+      // wf_resolve.hip: res_outputs — psum / n / 1e6 * 1e3 / wr^3 - load_coef lsum / (4 n)
+      keep(r0 + tid, psum / N / 1.0e6 * 1.0e3 / (wr * wr * wr) - (double)load_coef * lsum / (4.0 * N), psum);
+    }
+    __syncthreads();  // (the next tile overwrites pw / ld; after the last one what `keep` left in LDS is complete)
+  }
+}
+
+// its launch: the odd row strides and T, the rows per tile — [T][sp] + [T][sl] floats in 24 KiB of LDS, at most a row per
+// thread —, and the tile's LDS bytes (the kernel's [R] arrays of doubles come first and are the kernel's to add)
+struct WfRewardTile {
+  int T, sp, sl;
+  size_t lds_bytes;
+};
+inline WfRewardTile wf_reward_tile(int R, int N, int threads) {
+  const int sp = N | 1, sl = (4 * N) | 1;
+  int T = 6144 / (sp + sl);
+  T = T < 1 ? 1 : T;
+  T = T > R ? R : T;
+  T = T > threads ? threads : T;
+  return WfRewardTile{T, sp, sl, sizeof(float) * (size_t)T * (sp + sl)};
 }
 
 // ---- the staged row sum (wf_rose_rowsum_kernel, wf_robust_rowsum_kernel): a block of ONE wave stages the N float32 powers of

@@ -417,6 +417,37 @@ class VecWindFarmEnv:
         K = 1 if alt is None else int(alt.shape[2])
         return {"reward_base": r["reward"][:, 0], "reward_alt": r["reward"][:, 1:].reshape(n, N, K), "difference": r["difference"]}
 
+    def lookahead_returns(self, action_sequences, gamma=1.0, farms=None, strict=False):
+        """The discounted return the env would pay over the next H steps for each of K candidate action sequences, from
+        the state it is in — call it BEFORE `step`: dict(returns (n_farms, K) float64, rewards (n_farms, K, H) float64,
+        final_yaw (n_farms, K, N) float32, best (n_farms,) int32 — the sequence of the largest return, the lowest index among
+        equal ones), torch CUDA tensors when the env returns torch.  action_sequences is {"yaw": (num_envs, K, H, N)} or
+        the array itself, in the env's action encoding; farms picks the farms served.  rewards[:, k, 0] is the reward
+        `step(action_sequences[:, k, 0])` will pay (to the step's tolerance).  Every action goes through the step's own budget
+        gate, increment and clip, and the accumulators and the move counter advance along each sequence; the wind the env
+        holds is held over the horizon (include/wflookahead.h; backend.WfStep.lookahead_returns; the project's own
+        definition).  Run on a handle of its own: the env's yaw state, accumulators, wind and buffers are read, never
+        changed.  strict=True solves every row in float64: the mode for near-equal candidates."""
+        if self._series is not None:
+            raise NotImplementedError("lookahead_returns is not supported on a time-series episode: the series tick precedes "
+                                      "the step, so the wind of the coming steps is not the one the env holds")
+        if type(self.reward_shaper).__name__ != "DoNothingReward":
+            raise ValueError("lookahead_returns needs the plain reward (DoNothingReward): the return of a shaped reward is "
+                             "not defined here")
+        a = self._to_device(action_sequences["yaw"] if isinstance(action_sequences, dict) else action_sequences)
+        B, N = self.num_envs, self.num_turbines
+        if a.ndim != 4 or a.shape[0] != B or a.shape[3] != N:
+            raise ValueError("action_sequences must be (num_envs, K, H, num_turbines): K sequences of H joint actions per farm")
+        if farms is not None:
+            idx = np.ascontiguousarray(farms, dtype=np.int64).reshape(-1)
+            if self.return_torch:
+                import torch
+
+                a = a[torch.from_numpy(idx).to(a.device)]
+            else:
+                a = a[idx]
+        return self.fi.lookahead_returns(a, gamma=gamma, farms=farms, strict=strict, want=("returns", "rewards", "final_yaw", "best"))
+
     def lut_target_yaw(self, table_slot: int = 0):
         """The yaw (num_envs, N) the look-up table in `table_slot` (backend.WfStep.set_yaw_table on `self.fi`) holds for
         every farm's CURRENT wind, clipped to the env's yaw bounds — a torch CUDA tensor when the env returns torch.  The
