@@ -609,6 +609,51 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the lookahead kernels as the runtime reports them."""
         return self._lookahead().kernel_info()
 
+    # -- receding-horizon planner: CEM over action sequences (include/wfplan.h) ------------------------
+    def _plan(self) -> "_Plan":
+        """The handle's plan object; created on first use, destroyed in close() before the handle."""
+        po = getattr(self, "_plan_obj", None)
+        if po is None:
+            po = self._plan_obj = _Plan(self)
+        return po
+
+    def plan_actions(self, horizon, candidates=64, elites=8, sigma=None, seed=0, gamma=1.0, wind=None, mean=None, farms=None,
+                     strict=False, max_eval_farms=65536, want=("first_action", "plan_return"), out=None):
+        """A receding-horizon plan for every farm, from the env state the handle holds, which is read and never changed
+        (include/wfplan.h; the project's own definition, PARITY UNPINNED beyond the oracle): the cross-entropy method over
+        (horizon, N) raw actions, continuous control only.  Each of len(sigma) iterations scores `candidates` sequences as
+        lookahead_returns scores them — candidate 0 the best sequence so far (at first the hold: the plan is never worse
+        than doing nothing), candidate 1 the mean, the others the mean plus sigma[i] times a unit-variance deviate of a
+        counter-based generator, clipped to +-yaw_step — and moves the mean to the average of the `elites` best.  One glue
+        kernel stands between two evaluator steps; nothing is read back in between.
+          horizon    H, 1 <= H <= 64
+          candidates K >= 3, K H <= 4096;  elites  1 <= E <= K
+          sigma      one width per iteration, degrees, non-negative; None: (1, 1/2, 1/4) yaw_step
+          seed       of the draws; a farm's draws depend on (seed, its index in the batch, iteration, element) alone
+          gamma      discount in [0, 1]
+          wind       (n_farms, H, 2) float64 (speed, direction) the wind step h is solved under, or None: the handle's
+                     current wind held over the horizon
+          mean       (n_farms, H, N) float32 the warm start, or None: zeros (receding horizon: the previous call's "mean"
+                     shifted by one step)
+          farms      farm indices (any order), or None: every farm of the batch
+          strict     every row is solved in float64; otherwise the handle's own resolve mode
+          max_eval_farms  rows the evaluator handle may hold, K H per farm: longer lists run in chunks
+          want       of "plan" (n, H, N) float32 — the best sequence seen —, "plan_return" (n,) float64, "hold_return" (n,)
+                     float64 — the return of doing nothing —, "first_action" (n, N) float32 — plan[:, 0], what to execute —,
+                     "final_yaw" (n, N) float32 — the yaw after walking the plan —, "mean" (n, H, N) float32
+          out        dict of tensors / arrays of those names to write into
+        Deterministic: fixed summation order, no atomics.  With torch tensors (wind, mean or out) the call only enqueues
+        work on torch's current stream and returns torch CUDA tensors."""
+        return self._plan().run(horizon, candidates, elites, sigma, seed, gamma, wind, mean, farms, strict, max_eval_farms, want, out)
+
+    def plan_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last plan_actions {"total_ms", "step_ms", "glue_ms"}."""
+        return self._plan().timing(detail)
+
+    def plan_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the plan kernel as the runtime reports them."""
+        return self._plan().kernel_info()
+
     # -- wind-rose expected power and the yaw look-up table (include/wfrose.h) -------------------------
     def _rose(self) -> "_Rose":
         """The handle's rose object; created on first use, destroyed in close() before the handle."""
@@ -689,6 +734,7 @@ class WfStep:
         p = EnvParams(yaw_lo, yaw_hi, yaw_step, actuator_rate, dt, budget, load_coef, int(bool(discrete)))
         check(self._lib.wf_env_config(self._h, C.byref(p)), self._h)
         check(self._lib.wf_env_set_power_unit(self._h, int(bool(power_mw))), self._h)
+        self._env_yaw_step = float(np.float32(yaw_step))  # (plan_actions' default widths are fractions of it)
 
     def env_reset(self):
         check(self._lib.wf_env_reset(self._h), self._h)
@@ -914,9 +960,9 @@ class WfStep:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h,
-            # wfcredit.h, wflookahead.h)
+            # wfcredit.h, wflookahead.h, wfplan.h)
             for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
-                         "_lookahead_obj"):
+                         "_lookahead_obj", "_plan_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
                     ext.close()
@@ -932,7 +978,7 @@ class WfStep:
 
 
 class _Ext:
-    """An extension object of a WfStep handle — the `wf_<NAME>` of include/wf<NAME>.h — and what the seven wrappers share:
+    """An extension object of a WfStep handle — the `wf_<NAME>` of include/wf<NAME>.h — and what the eight wrappers share:
     create / close, timing, kernel_info, evaluator, and the conversion of farm lists, (n, N) float32 rows and output dicts
     into the pointers the C ABI takes.  `_r` is the raw object, `KERNELS` names kernel_info's entries in the library's order."""
 
@@ -1398,5 +1444,65 @@ class _Lookahead(_Ext):
         out, ptrs = self._outputs(out, spec, on_device, actions)
         p = dict(zip(spec, ptrs))
         self._call("run", actions.data_ptr() if on_device else actions.ctypes.data, K, H, wptr, float(gamma), n, fptr,
+                   *[p.get(k) for k in self.OUTPUTS], int(on_device))
+        return {k: out[k] for k in spec}
+
+
+class _Plan(_Ext):
+    """The `wf_plan` object of a WfStep handle (include/wfplan.h)."""
+
+    NAME = "plan"
+    KERNELS = ("advance",)
+    OUTPUTS = ("plan", "plan_return", "hold_return", "first_action", "final_yaw", "mean")
+
+    def run(self, horizon, candidates, elites, sigma, seed, gamma, wind, mean, farms, strict, max_eval_farms, want, out):
+        w = self._w
+        N = w.num_turbines
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.OUTPUTS for k in want):
+            raise ValueError("want must name plan, plan_return, hold_return, first_action, final_yaw and / or mean")
+        H, K, E = int(horizon), int(candidates), int(elites)
+        if sigma is None:
+            step = getattr(w, "_env_yaw_step", 5.0)
+            sigma = (step, 0.5 * step, 0.25 * step)
+        sg = np.ascontiguousarray(np.atleast_1d(sigma), dtype=np.float64).reshape(-1)
+        self._call("config", int(bool(strict)), int(max_eval_farms or 0))
+        fa, n, fptr = self._farms(farms)
+        on_device = _is_torch(wind) or _is_torch(mean) or (out is not None and any(_is_torch(v) for v in out.values()))
+        like = None
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            like = next(v for v in [wind, mean] + list((out or {}).values()) if _is_torch(v))
+        wptr = mptr = None
+        if wind is not None:
+            if on_device:
+                if not _is_torch(wind):
+                    wind = torch.as_tensor(np.asarray(wind, np.float64), device=like.device)
+                assert wind.is_cuda and wind.dtype == torch.float64, "wind"
+                wind = wind.contiguous()
+            else:
+                wind = np.ascontiguousarray(wind, dtype=np.float64)
+            if tuple(wind.shape) != (n, H, 2):
+                raise ValueError("wind must be (n_farms, H, 2): the (speed, direction) every step of the horizon is solved under")
+            wptr = wind.data_ptr() if on_device else wind.ctypes.data
+        if mean is not None:
+            if on_device:
+                if not _is_torch(mean):
+                    mean = torch.as_tensor(np.asarray(mean, np.float32), device=like.device)
+                assert mean.is_cuda and mean.dtype == torch.float32, "mean"
+                mean = mean.contiguous()
+            else:
+                mean = np.ascontiguousarray(mean, dtype=np.float32)
+            if tuple(mean.shape) != (n, H, N):
+                raise ValueError("mean must be (n_farms, H, num_turbines): the warm start of every listed farm")
+            mptr = mean.data_ptr() if on_device else mean.ctypes.data
+        shapes = {"plan": ((n, H, N), np.float32), "plan_return": ((n,), np.float64), "hold_return": ((n,), np.float64),
+                  "first_action": ((n, N), np.float32), "final_yaw": ((n, N), np.float32), "mean": ((n, H, N), np.float32)}
+        spec = {k: shapes[k] for k in self.OUTPUTS if k in want}
+        out, ptrs = self._outputs(out, spec, on_device, like)
+        p = dict(zip(spec, ptrs))
+        self._call("run", H, K, E, int(sg.size), sg.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF, float(gamma), wptr, mptr, n, fptr,
                    *[p.get(k) for k in self.OUTPUTS], int(on_device))
         return {k: out[k] for k in spec}

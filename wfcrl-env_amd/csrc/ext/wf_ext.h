@@ -1,4 +1,4 @@
-// wf_ext.h — the host layer every extension object (probe/, yawopt/, rose/, robust/, grad/, credit/, lookahead/) stands on: the base
+// wf_ext.h — the host layer every extension object (probe/, yawopt/, rose/, robust/, grad/, credit/, lookahead/, plan/) stands on: the base
 // struct with the parent handle, the error text and the event pool; a grow-only device buffer that frees itself; the
 // evaluator — a further handle that follows the parent, configured through the public ABI of include/wfstep.h only; the
 // checks an extension asks of its parent and of a farm list; the staging of a host caller's arrays (staging); event
@@ -113,7 +113,7 @@ inline WfSlots chunk_slots(const farm_list& fl, const int* farms, int base, int 
 // element type, lie end to end (16-byte aligned) in `buf`, in the order they were named: in() for what the kernels read,
 // out() for what they write; *d is the array's device pointer, null for a null array — a host caller's from begin() on.
 struct staging {
-  static constexpr int kMaxSegs = 8;  // the most arrays one call names (wf_lookahead_run: two inputs, five outputs)
+  static constexpr int kMaxSegs = 8;  // the most arrays one call names (wf_plan_run: two inputs, six outputs)
   ext_base* x;
   dev_buf<char>& buf;
   bool host;
@@ -165,12 +165,18 @@ struct row_policy {
   std::function<int(int C, int E)> reserve;  // the extension's own buffers, for chunks of C items; names the caller's arrays to `st`
   // a chunk's kernels, before the step (yaw and wind of the E rows) and after it; sl.base is the chunk's first item
   std::function<int(const WfSlots& sl, int E)> layout, reduce;
+  // A chunk may take several ROUNDS: rounds steps of the evaluator under the wind the lay-out wrote, with advance(sl, E, r),
+  // r = 1 .. rounds - 1, between step r - 1 and step r: it reads the step's outputs and writes the next yaw block (plan/)
+  int rounds = 1;
+  std::function<int(const WfSlots& sl, int E, int round)> advance;
   std::function<int()> finish;  // what follows the last chunk, if anything (the rose's copy of its sums)
 };
 // The whole run on the parent's stream.  Chunks of C = max_eval / rows items (at most all *n_items), E = C rows evaluator
 // farms.  Per chunk: layout, then wf_set_wind_counts from b.d_wind and one wf_step from b.d_yaw into b.d_pow (and b.d_load),
+// then — under a policy of several rounds — advance and one more wf_step per further round, the wind set ONCE per chunk;
 // then reduce.  The caller's arrays go through `st`: begun after reserve, ended last.  Events: the run's first and last, or
-// split per chunk e0 | lay-out e | wind + step e | reduce e (last_timing's per_chunk layout with 4).
+// split per chunk e0 | lay-out e | wind + step e | advance e | step e | ... | reduce e (last_timing's per_chunk layout with
+// 2 rounds + 2: 4 for one round).
 int run_rows(ext_base* x, row_batch& b, evaluator& es, row_policy& k, staging& st, int* n_items, const int* farms);
 
 // ---- the coordinate search over yaw (include/wfyawopt.h; include/wfrobust.h: "with farm power replaced by E") ----

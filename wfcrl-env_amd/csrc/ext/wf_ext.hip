@@ -183,11 +183,17 @@ int run_rows(ext_base* x, row_batch& b, evaluator& es, row_policy& k, staging& s
     WFX_EV(x, es.ev, wf_set_wind_counts(es.ev, b.d_wind, E, b.d_wind + E, E, 1));
     WFX_EV(x, es.ev, wf_step(es.ev, b.d_yaw, b.d_pow, nullptr, nullptr, k.loads ? b.d_load.p : nullptr, 1));
     if (split) { rc = record(x); if (rc != WF_OK) return rc; }
+    for (int r = 1; r < k.rounds; ++r) {  // (the rows' wind stays what the lay-out wrote: set once per chunk)
+      if ((rc = k.advance(sl, E, r)) != WF_OK) return rc;
+      if (split) { rc = record(x); if (rc != WF_OK) return rc; }
+      WFX_EV(x, es.ev, wf_step(es.ev, b.d_yaw, b.d_pow, nullptr, nullptr, k.loads ? b.d_load.p : nullptr, 1));
+      if (split) { rc = record(x); if (rc != WF_OK) return rc; }
+    }
     if ((rc = k.reduce(sl, E)) != WF_OK) return rc;
     if (split) { rc = record(x); if (rc != WF_OK) return rc; }
   }
   if (!split) { rc = record(x); if (rc != WF_OK) return rc; }
-  x->timed = true; x->per_chunk = split ? 4 : 0;
+  x->timed = true; x->per_chunk = split ? 2 * (size_t)k.rounds + 2 : 0;
   if (k.finish && (rc = k.finish()) != WF_OK) return rc;
   return st.end();
 }

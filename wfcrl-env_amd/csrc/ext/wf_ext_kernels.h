@@ -1,4 +1,4 @@
-// wf_ext_kernels.h — the device side the extensions share (yawopt/, robust/, rose/, grad/, credit/, lookahead/): which farm a
+// wf_ext_kernels.h — the device side the extensions share (yawopt/, robust/, rose/, grad/, credit/, lookahead/, plan/): which farm a
 // chunk's slot works on, a visit's candidate grid, the visit order of a slot's turbines, the phases the two searches' advance
 // kernels have in common, the fused env's transition and the staged row rewards of credit and lookahead, and the staged row
 // sum of the rose and the robust search.  The per-extension headers build their kernels'
@@ -229,14 +229,15 @@ __device__ __forceinline__ void wf_staged_row_rewards(const float* __restrict__ 
 }
 
 // its launch: the odd row strides and T, the rows per tile — [T][sp] + [T][sl] floats in 24 KiB of LDS, at most a row per
-// thread —, and the tile's LDS bytes (the kernel's [R] arrays of doubles come first and are the kernel's to add)
+// thread —, and the tile's LDS bytes (the kernel's [R] arrays of doubles come first and are the kernel's to add).  A kernel
+// that keeps more in LDS beside the tile gives it fewer `floats` (wf_plan_advance_kernel: its elite flags come out of these)
 struct WfRewardTile {
   int T, sp, sl;
   size_t lds_bytes;
 };
-inline WfRewardTile wf_reward_tile(int R, int N, int threads) {
+inline WfRewardTile wf_reward_tile(int R, int N, int threads, int floats = 6144) {
   const int sp = N | 1, sl = (4 * N) | 1;
-  int T = 6144 / (sp + sl);
+  int T = floats / (sp + sl);
   T = T < 1 ? 1 : T;
   T = T > R ? R : T;
   T = T > threads ? threads : T;

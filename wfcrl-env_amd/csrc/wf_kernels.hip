@@ -38,6 +38,7 @@
 #include <cstring>
 
 #include "wf_device.h"
+#include "wf_philox.h"
 
 #define WF_TAB_WAVES 4  // waves per block on the pair-table path (two-wave blocks: +8 %, twice the row staging per farm; eight: slower)
 // The library is built from this file twice (csrc/Makefile): WF_KSET=1 carries the step-kernel variants with one, two,
@@ -127,37 +128,11 @@ __global__ void wf_geometry_kernel(int N, const double* __restrict__ lx, const d
 // ---------------------------------------------------------------------------------------------
 // On-device wind process
 //   reset sampling  ws = clip(scale * Weibull(shape), lo, hi), wd = clip(Normal(mean, std) mod 360, lo, hi)
-//                   (reference wfcrl/mdp.py:237-258; NumPy draws there, a counter-based Philox4x32-10 here:
+//                   (reference wfcrl/mdp.py:237-258; NumPy draws there, a counter-based Philox4x32-10 here (wf_philox.h):
 //                   same distributions, different stream)
 //   series playback per-farm position in a shared (ws, wd) series, rolled to a per-farm start
 //                   (reference wfcrl/interface.py:512-524)
 // ---------------------------------------------------------------------------------------------
-namespace {
-__device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3, unsigned k0,
-                                             unsigned k1) {
-  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-  const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-  const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-  const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-  c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
-__device__ __forceinline__ void philox4x32_10(unsigned long long seed, unsigned long long ctr, unsigned stream,
-                                              unsigned out[4]) {
-  unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = stream, c3 = 0;
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c0, c1, c2, c3, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ double u01(unsigned hi, unsigned lo) {  // (0, 1), 53 bits
-  const unsigned long long v = (((unsigned long long)hi << 32) | lo) >> 11;
-  return ((double)v + 0.5) * (1.0 / 9007199254740992.0);
-}
-}  // namespace
 
 __global__ void wf_wind_sample_kernel(int B, unsigned long long seed, double ws_scale, double ws_shape, double ws_lo,
                                       double ws_hi, double wd_mean, double wd_std, double wd_lo, double wd_hi,

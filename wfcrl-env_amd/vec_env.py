@@ -448,6 +448,39 @@ class VecWindFarmEnv:
                 a = a[idx]
         return self.fi.lookahead_returns(a, gamma=gamma, farms=farms, strict=strict, want=("returns", "rewards", "final_yaw", "best"))
 
+    def plan_actions(self, horizon, candidates=64, elites=8, sigma=None, seed=0, gamma=1.0, wind=None, mean=None, farms=None,
+                     strict=False, max_eval_farms=65536, want=("first_action", "plan_return")):
+        """A receding-horizon plan for every farm from the state the env is in — call it BEFORE `step`, execute
+        {"yaw": first_action}, shift "mean" by one step and pass it back as `mean`: the cross-entropy method over (horizon, N)
+        action sequences on the device, one glue kernel between two evaluator steps (include/wfplan.h;
+        backend.WfStep.plan_actions has the arguments; the project's own definition).  Returns the outputs `want` names —
+        "plan", "plan_return", "hold_return", "first_action", "final_yaw", "mean" —, torch CUDA tensors when the env returns
+        torch.  Continuous control only.  Run on a handle of its own: the env's yaw state, accumulators, wind and buffers
+        are read, never changed.  On a time-series episode the wind of the coming steps is not the one the env holds: the
+        caller passes it as wind=(n_farms, horizon, 2)."""
+        if self._series is not None and wind is None:
+            raise NotImplementedError("plan_actions on a time-series episode needs wind=(n_farms, horizon, 2): the series tick "
+                                      "precedes the step, so the wind of the coming steps is not the one the env holds")
+        if type(self.reward_shaper).__name__ != "DoNothingReward":
+            raise ValueError("plan_actions needs the plain reward (DoNothingReward): the return of a shaped reward is not "
+                             "defined here")
+        out = None
+        if self.return_torch:
+            import torch
+
+            wind = None if wind is None else self._to_device(wind).double()
+            mean = None if mean is None else self._to_device(mean).float()
+            want = (want,) if isinstance(want, str) else tuple(want)
+            n = self.num_envs if farms is None else int(np.asarray(farms).size)
+            H, N = int(horizon), self.num_turbines
+            shapes = {"plan": ((n, H, N), torch.float32), "plan_return": ((n,), torch.float64), "hold_return": ((n,), torch.float64),
+                      "first_action": ((n, N), torch.float32), "final_yaw": ((n, N), torch.float32), "mean": ((n, H, N), torch.float32)}
+            if any(k not in shapes for k in want):
+                raise ValueError("want must name plan, plan_return, hold_return, first_action, final_yaw and / or mean")
+            out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=f"cuda:{self.fi.device_id}") for k in want}
+        return self.fi.plan_actions(horizon, candidates=candidates, elites=elites, sigma=sigma, seed=seed, gamma=gamma, wind=wind,
+                                    mean=mean, farms=farms, strict=strict, max_eval_farms=max_eval_farms, want=want, out=out)
+
     def lut_target_yaw(self, table_slot: int = 0):
         """The yaw (num_envs, N) the look-up table in `table_slot` (backend.WfStep.set_yaw_table on `self.fi`) holds for
         every farm's CURRENT wind, clipped to the env's yaw bounds — a torch CUDA tensor when the env returns torch.  The
