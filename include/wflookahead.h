@@ -16,8 +16,8 @@
  *   actions [n_farms][K][H][N] float32, the env's action encoding (continuous or discrete as configured), caller's turbine
  *           order; 1 <= H <= WF_LOOKAHEAD_MAX_H, K >= 1, K H <= WF_LOOKAHEAD_MAX_ROWS
  *   wind    [n_farms][H][2] double (speed, direction), the wind step h is solved under; NULL = the parent's current wind of
- *           the farm, held over the horizon — also under a parent in series mode: version 1 does not read the series'
- *           coming rows; a caller who wants them passes them here
+ *           the farm, held over the horizon — also under a parent in series mode, unless wf_lookahead_set_series
+ *           (include/wfseries.h) asks for the series' coming rows, which are then read on the device
  *   gamma   double, finite, in [0, 1]
  *
  * TRAJECTORY of sequence k: start from (y, acc, moves) of the farm; for h = 0 .. H-1 the fused env step's transition, in the

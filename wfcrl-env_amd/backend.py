@@ -17,6 +17,11 @@ def _is_torch(a) -> bool:
     return type(a).__module__.startswith("torch")
 
 
+def _is_series(wind) -> bool:
+    """wind="series": the series-ahead mode of lookahead, plan and credit (include/wfseries.h)."""
+    return isinstance(wind, str) and wind == "series"
+
+
 def default_model() -> dict:
     """Reference defaults (case.yaml + nrel_5MW) as a plain dict incl. the power/thrust table."""
     p = ModelParams()
@@ -294,6 +299,55 @@ class WfStep:
     def wind_series_step(self):
         check(self._lib.wf_wind_series_step(self._h), self._h)
 
+    # -- time-series episodes beyond reset / step (include/wfseries.h) ---------------------------------
+    def wind_preview(self, H: int, first: int = 1, farms=None, as_torch: bool = False, out=None):
+        """The window (first, H) of the wind series' coming rows (include/wfseries.h; a handle in series mode): entry h is
+        the wind of tick min(t + first + h, T - 1).  first=1 starts at the wind of the coming env step (the env ticks before
+        it steps), first=0 at the wind the handle holds.  Returns ((n, H, 2) float64 [speed, direction], available):
+        `available` = clamp(T - t - first, 0, H) entries are real, the rest hold the last tick's wind.  as_torch (or a torch
+        `out`): a CUDA tensor written by one kernel launch on torch's current stream, nothing read back; else NumPy.
+          farms   farm indices (any order), or None: every farm of the batch"""
+        H, first = int(H), int(first)
+        fa = None if farms is None else np.ascontiguousarray(farms, dtype=np.int32).reshape(-1)
+        n = self.env_batch if fa is None else int(fa.size)
+        on_device = bool(as_torch) or _is_torch(out)
+        if on_device:
+            import torch
+
+            self._follow_torch_stream()
+            if out is None:
+                out = torch.empty((n, max(H, 0), 2), dtype=torch.float64, device=f"cuda:{self.device_id}")
+            assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (n, H, 2), "out"
+            ptr = out.data_ptr()
+        else:
+            if out is None:
+                out = np.empty((n, max(H, 0), 2), np.float64)
+            assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (n, H, 2), "out"
+            ptr = out.ctypes.data
+        avail = C.c_int(0)
+        check(self._lib.wf_series_window(self._h, first, H, n, None if fa is None else fa.ctypes.data, ptr, C.byref(avail),
+                                         int(on_device)), self._h)
+        return out, int(avail.value)
+
+    def series_state(self) -> dict:
+        """The series cursor (include/wfseries.h: wf_series_get): {"T", "t" — ticks made since set_wind_series —, "start" (B,)
+        int32, "prev_pending" — the speed of tick t - 1 waits for the next env step's reward}."""
+        T, t, pending = C.c_int(), C.c_int(), C.c_int()
+        start = np.empty(self.env_batch, np.int32)
+        check(self._lib.wf_series_get(self._h, C.byref(T), C.byref(t), start.ctypes.data, C.byref(pending)), self._h)
+        return {"T": int(T.value), "t": int(t.value), "start": start, "prev_pending": bool(pending.value)}
+
+    def series_seek(self, t: int, prev_pending: bool = False):
+        """Puts the handle in the state `t` ticks after set_wind_series would have left (include/wfseries.h: wf_series_seek);
+        the series and the start rows stay."""
+        check(self._lib.wf_series_seek(self._h, int(t), int(bool(prev_pending))), self._h)
+
+    def series_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the series kernel as the runtime reports them."""
+        v = (C.c_int * 3)()
+        check(self._lib.wf_series_kernel_info(self._h, v), self._h)
+        return {"window": dict(zip(("vgprs", "lds_bytes", "scratch_bytes"), v))}
+
     def get_wind(self, as_torch: bool = False):
         """Current (ws, wd) of every farm: two float64 arrays of length B."""
         B = self.env_batch
@@ -532,7 +586,7 @@ class WfStep:
         return co
 
     def counterfactual_rewards(self, base=None, alt=None, base_kind="yaw", alt_kind="yaw", farms=None, strict=False,
-                               max_eval_farms=None, want=("reward", "difference"), out=None):
+                               max_eval_farms=None, want=("reward", "difference"), out=None, wind=None):
         """What the farm's reward would have been had ONE turbine done something else, for the handle's current wind
         (include/wfcredit.h; the project's own definition, PARITY UNPINNED beyond the oracle): R = 1 + N K farm solves per
         farm in one batched step — row 0 the base, row 1 + i K + k the base with turbine i's entry replaced by alternative
@@ -553,11 +607,14 @@ class WfStep:
                      reward[:, 0] - reward[:, 1 + i K + k]
           out        dict of tensors / arrays of those names to write into (a torch `out` selects the device path when base
                      and alt are None)
+          wind       None: the handle's current wind; "series" (a handle in series mode): the wind of the coming env step —
+                     the series' next row, read on the device (include/wfseries.h) —, the reward normalised by the current
+                     speed, as that step will
         Where an alternative's float32 yaw has the bits of the base entry, difference is exactly 0.0 and the row's reward
         and farm_power are copies of row 0's.  The reward is normalised by the speed the next env_step would normalise by
         (env_set_prev_wind is read, not consumed).  Deterministic: fixed summation order, no atomics.  With torch tensors
         the call only enqueues work on torch's current stream.  The handle is not touched."""
-        return self._credit().run(base, alt, base_kind, alt_kind, farms, strict, max_eval_farms, want, out)
+        return self._credit().run(base, alt, base_kind, alt_kind, farms, strict, max_eval_farms, want, out, wind)
 
     def credit_timing(self, detail=None) -> dict:
         """As yawopt_timing, for the last counterfactual_rewards {"total_ms", "step_ms", "glue_ms"}."""
@@ -586,8 +643,10 @@ class WfStep:
           actions    (n_farms, K, H, N) float32 in the env's encoding under env_config (block i belongs to farms[i]) — torch
                      CUDA tensor or NumPy; 1 <= H <= 64, K H <= 4096
           gamma      discount in [0, 1]
-          wind       (n_farms, H, 2) float64 (speed, direction) the wind step h is solved under, or None: the handle's
-                     current wind held over the horizon (also in series mode: the series' coming rows are not read)
+          wind       (n_farms, H, 2) float64 (speed, direction) the wind step h is solved under; None: the handle's
+                     current wind held over the horizon (also in series mode); "series" (a handle in series mode): the
+                     series' coming rows, read on the device — step h under the wind of tick t + 1 + h, the last row held
+                     past the end, step 0 normalised by the current speed (include/wfseries.h)
           farms      farm indices (any order), or None: every farm of the batch
           strict     every row is solved in float64; otherwise the handle's own resolve mode.  Returns closer than the sum
                      of their rows' tolerances are not ordered reliably in the default mode
@@ -631,8 +690,8 @@ class WfStep:
           sigma      one width per iteration, degrees, non-negative; None: (1, 1/2, 1/4) yaw_step
           seed       of the draws; a farm's draws depend on (seed, its index in the batch, iteration, element) alone
           gamma      discount in [0, 1]
-          wind       (n_farms, H, 2) float64 (speed, direction) the wind step h is solved under, or None: the handle's
-                     current wind held over the horizon
+          wind       (n_farms, H, 2) float64 (speed, direction) the wind step h is solved under; None: the handle's
+                     current wind held over the horizon; "series": the series' coming rows, as lookahead_returns reads them
           mean       (n_farms, H, N) float32 the warm start, or None: zeros (receding horizon: the previous call's "mean"
                      shifted by one step)
           farms      farm indices (any order), or None: every farm of the batch
@@ -1353,9 +1412,12 @@ class _Credit(_Ext):
     KIND = {"yaw": 0, "action": 1}
     OUTPUTS = ("reward", "farm_power", "difference")
 
-    def run(self, base, alt, base_kind, alt_kind, farms, strict, max_eval_farms, want, out):
+    def run(self, base, alt, base_kind, alt_kind, farms, strict, max_eval_farms, want, out, wind=None):
         w = self._w
         N = w.num_turbines
+        if wind is not None and not _is_series(wind):
+            raise ValueError('wind must be None (the current wind) or "series" (the series\' coming row)')
+        self._call("set_series", int(wind is not None))
         if base_kind not in self.KIND or alt_kind not in self.KIND:
             raise ValueError("base_kind and alt_kind must be 'yaw' or 'action'")
         want = (want,) if isinstance(want, str) else tuple(want)
@@ -1427,6 +1489,9 @@ class _Lookahead(_Ext):
             raise ValueError("actions must be (n_farms, K, H, num_turbines): K sequences of H joint actions per listed farm")
         K, H = int(shape[1]), int(shape[2])
         wptr = None
+        self._call("set_series", int(_is_series(wind)))
+        if _is_series(wind):
+            wind = None
         if wind is not None:
             if on_device:
                 if not _is_torch(wind):
@@ -1467,6 +1532,9 @@ class _Plan(_Ext):
             sigma = (step, 0.5 * step, 0.25 * step)
         sg = np.ascontiguousarray(np.atleast_1d(sigma), dtype=np.float64).reshape(-1)
         self._call("config", int(bool(strict)), int(max_eval_farms or 0))
+        self._call("set_series", int(_is_series(wind)))
+        if _is_series(wind):
+            wind = None
         fa, n, fptr = self._farms(farms)
         on_device = _is_torch(wind) or _is_torch(mean) or (out is not None and any(_is_torch(v) for v in out.values()))
         like = None

@@ -19,6 +19,7 @@ struct WfCreditLayoutArgs {
   WfSlots sl;
   const double *ws, *wd;  // the parent's wind
   int wind_stride;        // 0 shared, 1 per farm
+  const double* wind;     // [n_slots][2] (speed, direction) rows of this chunk that replace it (include/wfseries.h), or null
   int N, K;
   WfCreditEnv env;
   int base_kind, alt_kind;  // WF_CREDIT_YAW / WF_CREDIT_ACTION

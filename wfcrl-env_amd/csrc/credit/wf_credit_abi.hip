@@ -7,6 +7,7 @@
 // the next env step stays for that step.
 #include "../../../include/wfcredit.h"
 #include "../ext/wf_ext.h"
+#include "../series/wf_series.h"
 #include "wf_credit.h"
 
 using namespace wfi;
@@ -14,8 +15,10 @@ using namespace wfi;
 struct wf_credit : ext_base {
   // configuration
   int strict = 0, max_eval = 65536;
+  int series_ahead = 0;   // wf_credit_set_series (include/wfseries.h): the rows' wind is the series' coming row
   // device buffers (grow-only)
   row_batch rows;         // E = C (1 + N K) farms, with loads
+  dev_buf<double> d_window;  // [n_farms][2] that row of every listed farm
   dev_buf<char> d_stage;  // staging for host callers: base and alt rows; reward, farm_power, difference
   evaluator eval;
 };
@@ -49,11 +52,18 @@ int wf_credit_set_timing(wf_credit* c, int detail) {
   return WF_OK;
 }
 
+int wf_credit_set_series(wf_credit* c, int ahead) {
+  if (!c) return WF_E_INVALID;
+  c->series_ahead = ahead != 0;
+  return WF_OK;
+}
+
 int wf_credit_run(wf_credit* c, int base_kind, const float* base, int alt_kind, const float* alt, int K, int n_farms,
                   const int* farms, double* reward, double* farm_power, double* difference, int on_device) {
   if (!c) return WF_E_INVALID;
   wf_handle* h = c->h;
   const int N = h->N, wind_stride = h->wind_count == 1 ? 0 : 1;
+  const bool ahead = c->series_ahead != 0;
   row_batch& b = c->rows;
   const float *d_base = nullptr, *d_alt = nullptr;
   double *d_rew = nullptr, *d_fp = nullptr, *d_dif = nullptr;
@@ -72,6 +82,10 @@ int wf_credit_run(wf_credit* c, int base_kind, const float* base, int alt_kind, 
     if (!alt && K != 1) return ext_fail(c, WF_E_INVALID, "alt == NULL (hold / zero yaw) is one alternative: K must be 1");
     const bool needs_env = !base || base_kind == WF_CREDIT_ACTION || alt_kind == WF_CREDIT_ACTION;
     if (needs_env && !h->d_env_yaw) return ext_fail(c, WF_E_INVALID, kNoEnv);
+    if (ahead) {
+      const int rc = series_ahead_check(c, false, 1);
+      if (rc != WF_OK) return rc;
+    }
     k.rows = 1 + N * K;
     return WF_OK;
   };
@@ -79,6 +93,8 @@ int wf_credit_run(wf_credit* c, int base_kind, const float* base, int alt_kind, 
     const size_t fn = (size_t)n_farms * N, fr = (size_t)n_farms * k.rows;
     st.in(base, fn, &d_base); st.in(alt, fn * K, &d_alt);
     st.out(reward, fr, &d_rew); st.out(farm_power, fr, &d_fp); st.out(difference, fn * K, &d_dif);
+    if (ahead)  // (the farm list is on the device by now: run_rows uploads it before this hook)
+      return series_ahead_window(c, c->d_window, 1, n_farms, farms ? b.farms.d.p : nullptr);
     return WF_OK;
   };
   k.layout = [&](const WfSlots& sl, int E) -> int {
@@ -89,6 +105,7 @@ int wf_credit_run(wf_credit* c, int base_kind, const float* base, int alt_kind, 
     la.env = env; la.base_kind = base_kind; la.alt_kind = alt_kind;
     la.base = d_base ? d_base + off : nullptr;
     la.alt = d_alt ? d_alt + off * K : nullptr;
+    la.wind = ahead ? c->d_window + (size_t)sl.base * 2 : nullptr;
     la.yaw = b.d_yaw; la.ews = b.d_wind; la.ewd = b.d_wind + E;
     WFX_HIP(c, wfk_launch_credit_layout(&la, h->stream));
     return WF_OK;
@@ -98,7 +115,7 @@ int wf_credit_run(wf_credit* c, int base_kind, const float* base, int alt_kind, 
     WfCreditReduceArgs ra{};
     ra.sl = sl; ra.N = N; ra.K = K;
     ra.ws = h->d_ws; ra.wind_stride = wind_stride;
-    ra.ws_prev = (h->ws_prev_valid && h->d_ws_prev) ? h->d_ws_prev : nullptr;  // read, not consumed
+    ra.ws_prev = (!ahead && h->ws_prev_valid && h->d_ws_prev) ? h->d_ws_prev : nullptr;  // read, not consumed; series-ahead: the current speed
     ra.load_coef = h->env.load_coef;
     ra.yaw_ev = b.d_yaw; ra.power_ev = b.d_pow; ra.load_ev = b.d_load;
     ra.reward = d_rew ? d_rew + first * k.rows : nullptr;

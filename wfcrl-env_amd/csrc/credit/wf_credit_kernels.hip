@@ -7,7 +7,8 @@
 //                            alternative) where the value is an action; consecutive threads read consecutive inputs.  A
 //                            barrier.  Phase 2: the slot's [R][N] yaw block in one pass, consecutive threads on consecutive
 //                            floats: every store is a whole line; element (row, t) is the base entry unless t is the row's own
-//                            turbine.  Every row's wind from the parent's device wind.
+//                            turbine.  Every row's wind from the parent's device wind, or from the
+//                            chunk's override rows (the series-ahead mode, include/wfseries.h).
 //   wf_credit_reduce_kernel  once per chunk, after the step, ONE WORKGROUP PER SLOT.  The slot's R rows go by in TILES of T
 //                            rows: a tile's [T][N] powers and [T][4 N] load values are contiguous in the evaluator's outputs
 //                            and are staged in LDS with coalesced loads, two arrays of odd row stride (the pattern of
@@ -36,7 +37,9 @@ __global__ __launch_bounds__(256) void wf_credit_layout_kernel(const WfCreditLay
   const size_t in0 = (size_t)(slot < a.sl.n_slots ? slot : 0) * N;  // the slot's input rows
   const size_t st0 = (size_t)b * N;                                 // ... and its farm's env state
   const int moves_new = a.env.moves ? a.env.moves[b] + 1 : 1;
-  const double ws = a.ws[(size_t)b * a.wind_stride], wd = a.wd[(size_t)b * a.wind_stride];
+  const size_t in_slot = slot < a.sl.n_slots ? slot : 0;
+  const double ws = a.wind ? a.wind[2 * in_slot] : a.ws[(size_t)b * a.wind_stride];
+  const double wd = a.wind ? a.wind[2 * in_slot + 1] : a.wd[(size_t)b * a.wind_stride];
   for (int r = tid; r < R; r += nth) {
     a.ews[(size_t)slot * R + r] = ws;
     a.ewd[(size_t)slot * R + r] = wd;

@@ -9,6 +9,7 @@
 
 #include "../../../include/wflookahead.h"
 #include "../ext/wf_ext.h"
+#include "../series/wf_series.h"
 #include "wf_lookahead.h"
 
 using namespace wfi;
@@ -16,8 +17,10 @@ using namespace wfi;
 struct wf_lookahead : ext_base {
   // configuration
   int strict = 0, max_eval = 65536;
+  int series_ahead = 0;   // wf_lookahead_set_series (include/wfseries.h): the rows' wind is the window of the series' coming rows
   // device buffers (grow-only)
   row_batch rows;         // E = C K H farms, with loads
+  dev_buf<double> d_window;  // [n_farms][H][2] that window, laid out like a caller's wind
   dev_buf<char> d_stage;  // staging for host callers: actions, wind; returns, rewards, farm_power, final_yaw, best
   evaluator eval;
 };
@@ -48,12 +51,19 @@ int wf_lookahead_set_timing(wf_lookahead* l, int detail) {
   return WF_OK;
 }
 
+int wf_lookahead_set_series(wf_lookahead* l, int ahead) {
+  if (!l) return WF_E_INVALID;
+  l->series_ahead = ahead != 0;
+  return WF_OK;
+}
+
 int wf_lookahead_run(wf_lookahead* l, const float* actions, int K, int H, const double* wind, double gamma, int n_farms,
                      const int* farms, double* returns, double* rewards, double* farm_power, float* final_yaw, int* best,
                      int on_device) {
   if (!l) return WF_E_INVALID;
   wf_handle* h = l->h;
   const int N = h->N, wind_stride = h->wind_count == 1 ? 0 : 1;
+  const bool ahead = l->series_ahead != 0;
   row_batch& b = l->rows;
   const float* d_act = nullptr;
   const double* d_wind = nullptr;
@@ -75,12 +85,21 @@ int wf_lookahead_run(wf_lookahead* l, const float* actions, int K, int H, const 
     if (!std::isfinite(gamma) || gamma < 0.0 || gamma > 1.0) return ext_fail(l, WF_E_INVALID, "gamma must be finite and in [0, 1]");
     if (!actions) return ext_fail(l, WF_E_INVALID, "wf_lookahead_run: actions is NULL");
     if (!h->d_env_yaw || !h->d_env_acc || !h->d_env_moves) return ext_fail(l, WF_E_INVALID, kNoEnv);
+    if (ahead) {
+      const int rc = series_ahead_check(l, wind != nullptr, H);
+      if (rc != WF_OK) return rc;
+    }
     k.rows = K * H;
     return WF_OK;
   };
   k.reserve = [&](int, int) -> int {
     const size_t fk = (size_t)n_farms * K, fr = fk * H;
     st.in(actions, fr * N, &d_act); st.in(wind, (size_t)n_farms * H * 2, &d_wind);
+    if (ahead) {  // (the farm list is on the device by now: run_rows uploads it before this hook)
+      const int rc = series_ahead_window(l, l->d_window, H, n_farms, farms ? b.farms.d.p : nullptr);
+      if (rc != WF_OK) return rc;
+      d_wind = l->d_window;
+    }
     st.out(returns, fk, &d_ret); st.out(rewards, fr, &d_rew); st.out(farm_power, fr, &d_fp);
     st.out(final_yaw, fk * N, &d_fy); st.out(best, (size_t)n_farms, &d_best);
     return WF_OK;
@@ -103,7 +122,7 @@ int wf_lookahead_run(wf_lookahead* l, const float* actions, int K, int H, const 
     WfLookaheadReduceArgs ra{};
     ra.sl = sl; ra.N = N; ra.K = K; ra.H = H;
     ra.ws = h->d_ws; ra.wind_stride = wind_stride;
-    ra.ws_prev = (h->ws_prev_valid && h->d_ws_prev) ? h->d_ws_prev : nullptr;  // read, not consumed
+    ra.ws_prev = (!ahead && h->ws_prev_valid && h->d_ws_prev) ? h->d_ws_prev : nullptr;  // read, not consumed; series-ahead: the current speed
     ra.ews = b.d_wind;
     ra.load_coef = h->env.load_coef; ra.gamma = gamma;
     ra.power_ev = b.d_pow; ra.load_ev = b.d_load;

@@ -10,6 +10,7 @@
 
 #include "../../../include/wfplan.h"
 #include "../ext/wf_ext.h"
+#include "../series/wf_series.h"
 #include "wf_plan.h"
 
 using namespace wfi;
@@ -17,8 +18,10 @@ using namespace wfi;
 struct wf_plan : ext_base {
   // configuration
   int strict = 0, max_eval = 65536;
+  int series_ahead = 0;    // wf_plan_set_series (include/wfseries.h): the rows' wind is the window of the series' coming rows
   // device buffers (grow-only)
   row_batch rows;          // E = C K H farms, with loads
+  dev_buf<double> d_window;  // [n_farms][H][2] that window, laid out like a caller's wind
   dev_buf<float> d_cand;   // [E][N] the candidates of an iteration, kept from its lay-out to its reduce
   dev_buf<float> d_best;   // [C][H][N] best sequence so far
   dev_buf<float> d_mu;     // [C][H][N] the mean
@@ -56,12 +59,19 @@ int wf_plan_set_timing(wf_plan* p, int detail) {
   return WF_OK;
 }
 
+int wf_plan_set_series(wf_plan* p, int ahead) {
+  if (!p) return WF_E_INVALID;
+  p->series_ahead = ahead != 0;
+  return WF_OK;
+}
+
 int wf_plan_run(wf_plan* p, int H, int K, int E, int I, const double* sigma, unsigned long long seed, double gamma,
                 const double* wind, const float* mean0, int n_farms, const int* farms, float* plan, double* plan_return,
                 double* hold_return, float* first_action, float* final_yaw, float* mean, int on_device) {
   if (!p) return WF_E_INVALID;
   wf_handle* h = p->h;
   const int N = h->N;
+  const bool ahead = p->series_ahead != 0;
   row_batch& b = p->rows;
   const double* d_wind = nullptr;
   const float* d_mean0 = nullptr;
@@ -87,6 +97,10 @@ int wf_plan_run(wf_plan* p, int H, int K, int E, int I, const double* sigma, uns
     if (!h->d_env_yaw || !h->d_env_acc || !h->d_env_moves) return ext_fail(p, WF_E_INVALID, kNoEnv);
     if (h->env.discrete)
       return ext_fail(p, WF_E_UNSUPPORTED, "planning serves the continuous action encoding: this handle is configured discrete (wf_env_config)");
+    if (ahead) {
+      const int rc = series_ahead_check(p, wind != nullptr, H);
+      if (rc != WF_OK) return rc;
+    }
     sg.assign(sigma, sigma + I);
     k.rows = K * H; k.rounds = I;
     return WF_OK;
@@ -99,6 +113,11 @@ int wf_plan_run(wf_plan* p, int H, int K, int E, int I, const double* sigma, uns
     if (rc != WF_OK) return rc;
     const size_t fh = (size_t)n_farms * H;
     st.in(wind, fh * 2, &d_wind); st.in(mean0, fh * N, &d_mean0);
+    if (ahead) {  // (the farm list is on the device by now: run_rows uploads it before this hook)
+      rc = series_ahead_window(p, p->d_window, H, n_farms, farms ? b.farms.d.p : nullptr);
+      if (rc != WF_OK) return rc;
+      d_wind = p->d_window;
+    }
     st.out(plan, fh * N, &d_plan); st.out(plan_return, (size_t)n_farms, &d_pr); st.out(hold_return, (size_t)n_farms, &d_hr);
     st.out(first_action, (size_t)n_farms * N, &d_fa); st.out(final_yaw, (size_t)n_farms * N, &d_fy); st.out(mean, fh * N, &d_mean);
     return WF_OK;
@@ -113,7 +132,7 @@ int wf_plan_run(wf_plan* p, int H, int K, int E, int I, const double* sigma, uns
     r.wind_stride = h->wind_count == 1 ? 0 : 1;
     r.load_coef = h->env.load_coef; r.gamma = gamma; r.seed = seed;
     r.ws = h->d_ws; r.wd = h->d_wd;
-    r.ws_prev = (h->ws_prev_valid && h->d_ws_prev) ? h->d_ws_prev : nullptr;  // read, not consumed
+    r.ws_prev = (!ahead && h->ws_prev_valid && h->d_ws_prev) ? h->d_ws_prev : nullptr;  // read, not consumed; series-ahead: the current speed
     r.env.yaw = h->d_env_yaw; r.env.acc = h->d_env_acc; r.env.moves = h->d_env_moves;
     r.env.lo = h->env.yaw_lo; r.env.hi = h->env.yaw_hi; r.env.step = h->env.yaw_step;
     r.env.rate = h->env.actuator_rate; r.env.dt = h->env.dt; r.env.budget = h->env.budget; r.env.discrete = 0;

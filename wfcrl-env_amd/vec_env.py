@@ -363,7 +363,7 @@ class VecWindFarmEnv:
             cotangent = self._to_device(cotangent).float().reshape(yaw.shape)
         return self.fi.yaw_gradient(yaw, cotangent, farms=farms, step=step, bounds=(lo, hi), strict=strict)
 
-    def counterfactual_rewards(self, actions, alternatives="hold", farms=None, strict=False):
+    def counterfactual_rewards(self, actions, alternatives="hold", farms=None, strict=False, wind=None):
         """Per-agent counterfactuals of the joint action the env is ABOUT to take — call it BEFORE `step(actions)`:
         dict(reward_base (n_farms,), reward_alt (n_farms, N, K), difference (n_farms, N, K) = reward_base - reward_alt),
         float64, torch CUDA tensors when the env returns torch.  reward_base is the reward `step(actions)` will pay (to the
@@ -375,10 +375,10 @@ class VecWindFarmEnv:
         actions is the whole batch's (num_envs, N); farms picks the farms served.  Every action goes through the step's own
         budget gate, increment and clip on the env's state (include/wfcredit.h; backend.WfStep.counterfactual_rewards; the
         project's own definition).  Run on a handle of its own: the env's yaw state, accumulators, wind and buffers are
-        read, never changed.  strict=True solves every row in float64: the mode for large farms and small differences."""
-        if self._series is not None:
-            raise NotImplementedError("counterfactual_rewards is not supported on a time-series episode: the series tick "
-                                      "precedes the step, so the wind of the coming step is not the one the env holds")
+        read, never changed.  strict=True solves every row in float64: the mode for large farms and small differences.
+        On a time-series episode pass wind="series": every row is solved under the series' coming row, the wind `step` will
+        tick to (include/wfseries.h)."""
+        self._series_keyword("counterfactual_rewards", wind, "step")
         if type(self.reward_shaper).__name__ != "DoNothingReward":
             raise ValueError("counterfactual_rewards needs the plain reward (DoNothingReward): the effect of a reward shaper "
                              "is not defined per agent")
@@ -413,11 +413,11 @@ class VecWindFarmEnv:
             if alt.ndim != 3 or tuple(alt.shape[:2]) != (B, N):
                 raise ValueError("an alternatives array must be (num_envs, num_turbines, K)")
             alt = pick(alt)
-        r = self.fi.counterfactual_rewards(pick(a), alt, base_kind="action", alt_kind=alt_kind, farms=farms, strict=strict)
+        r = self.fi.counterfactual_rewards(pick(a), alt, base_kind="action", alt_kind=alt_kind, farms=farms, strict=strict, wind=wind)
         K = 1 if alt is None else int(alt.shape[2])
         return {"reward_base": r["reward"][:, 0], "reward_alt": r["reward"][:, 1:].reshape(n, N, K), "difference": r["difference"]}
 
-    def lookahead_returns(self, action_sequences, gamma=1.0, farms=None, strict=False):
+    def lookahead_returns(self, action_sequences, gamma=1.0, farms=None, strict=False, wind=None):
         """The discounted return the env would pay over the next H steps for each of K candidate action sequences, from
         the state it is in — call it BEFORE `step`: dict(returns (n_farms, K) float64, rewards (n_farms, K, H) float64,
         final_yaw (n_farms, K, N) float32, best (n_farms,) int32 — the sequence of the largest return, the lowest index among
@@ -427,10 +427,10 @@ class VecWindFarmEnv:
         gate, increment and clip, and the accumulators and the move counter advance along each sequence; the wind the env
         holds is held over the horizon (include/wflookahead.h; backend.WfStep.lookahead_returns; the project's own
         definition).  Run on a handle of its own: the env's yaw state, accumulators, wind and buffers are read, never
-        changed.  strict=True solves every row in float64: the mode for near-equal candidates."""
-        if self._series is not None:
-            raise NotImplementedError("lookahead_returns is not supported on a time-series episode: the series tick precedes "
-                                      "the step, so the wind of the coming steps is not the one the env holds")
+        changed.  strict=True solves every row in float64: the mode for near-equal candidates.  On a time-series episode
+        pass wind="series": step h is solved under the series' row of tick t + 1 + h, the last row held past the end of the
+        series (include/wfseries.h)."""
+        self._series_keyword("lookahead_returns", wind, "steps")
         if type(self.reward_shaper).__name__ != "DoNothingReward":
             raise ValueError("lookahead_returns needs the plain reward (DoNothingReward): the return of a shaped reward is "
                              "not defined here")
@@ -446,7 +446,8 @@ class VecWindFarmEnv:
                 a = a[torch.from_numpy(idx).to(a.device)]
             else:
                 a = a[idx]
-        return self.fi.lookahead_returns(a, gamma=gamma, farms=farms, strict=strict, want=("returns", "rewards", "final_yaw", "best"))
+        return self.fi.lookahead_returns(a, gamma=gamma, wind=wind, farms=farms, strict=strict,
+                                         want=("returns", "rewards", "final_yaw", "best"))
 
     def plan_actions(self, horizon, candidates=64, elites=8, sigma=None, seed=0, gamma=1.0, wind=None, mean=None, farms=None,
                      strict=False, max_eval_farms=65536, want=("first_action", "plan_return")):
@@ -456,11 +457,16 @@ class VecWindFarmEnv:
         backend.WfStep.plan_actions has the arguments; the project's own definition).  Returns the outputs `want` names —
         "plan", "plan_return", "hold_return", "first_action", "final_yaw", "mean" —, torch CUDA tensors when the env returns
         torch.  Continuous control only.  Run on a handle of its own: the env's yaw state, accumulators, wind and buffers
-        are read, never changed.  On a time-series episode the wind of the coming steps is not the one the env holds: the
-        caller passes it as wind=(n_farms, horizon, 2)."""
+        are read, never changed.  On a time-series episode the wind of the coming steps is not the one the env holds:
+        wind="series" reads the series' coming rows on the device (include/wfseries.h), or the caller passes them as
+        wind=(n_farms, horizon, 2)."""
+        series = isinstance(wind, str) and wind == "series"
+        if series and self._series is None:
+            raise ValueError('wind="series" needs a time-series episode: this env has no wind_time_series')
         if self._series is not None and wind is None:
             raise NotImplementedError("plan_actions on a time-series episode needs wind=(n_farms, horizon, 2): the series tick "
-                                      "precedes the step, so the wind of the coming steps is not the one the env holds")
+                                      "precedes the step, so the wind of the coming steps is not the one the env holds "
+                                      '(or wind="series": the series\' coming rows, read on the device)')
         if type(self.reward_shaper).__name__ != "DoNothingReward":
             raise ValueError("plan_actions needs the plain reward (DoNothingReward): the return of a shaped reward is not "
                              "defined here")
@@ -468,7 +474,7 @@ class VecWindFarmEnv:
         if self.return_torch:
             import torch
 
-            wind = None if wind is None else self._to_device(wind).double()
+            wind = wind if wind is None or series else self._to_device(wind).double()
             mean = None if mean is None else self._to_device(mean).float()
             want = (want,) if isinstance(want, str) else tuple(want)
             n = self.num_envs if farms is None else int(np.asarray(farms).size)
@@ -480,6 +486,28 @@ class VecWindFarmEnv:
             out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=f"cuda:{self.fi.device_id}") for k in want}
         return self.fi.plan_actions(horizon, candidates=candidates, elites=elites, sigma=sigma, seed=seed, gamma=gamma, wind=wind,
                                     mean=mean, farms=farms, strict=strict, max_eval_farms=max_eval_farms, want=want, out=out)
+
+    def _series_keyword(self, name, wind, steps):
+        """The wind keyword of counterfactual_rewards / lookahead_returns: None or "series"; a time-series episode needs
+        "series", any other episode None."""
+        if wind is not None and not (isinstance(wind, str) and wind == "series"):
+            raise ValueError(f'{name}: wind must be None or "series"')
+        if self._series is not None and wind is None:
+            raise NotImplementedError(f"{name} is not supported on a time-series episode: the series tick precedes the step, so "
+                                      f"the wind of the coming {steps} is not the one the env holds (pass wind=\"series\": the "
+                                      "series' coming rows, read on the device)")
+        if self._series is None and wind is not None:
+            raise ValueError(f'{name}: wind="series" needs a time-series episode: this env has no wind_time_series')
+
+    def wind_preview(self, H: int):
+        """The free wind the env will observe over its next H steps, on a time-series episode: ((num_envs, H, 2) float64
+        [speed, direction], available) — entry h is what `freewind_measurements` will hold after step h + 1 from here; only
+        the first `available` entries are real, the rest hold the series' last wind (the step that would follow it fails
+        with "exhausted").  A torch CUDA tensor when the env returns torch: one kernel launch, nothing read back
+        (include/wfseries.h; backend.WfStep.wind_preview).  What a feed-forward or preview controller observes."""
+        if self._series is None:
+            raise ValueError("wind_preview needs a time-series episode: this env has no wind_time_series")
+        return self.fi.wind_preview(H, first=1, as_torch=self.return_torch)
 
     def lut_target_yaw(self, table_slot: int = 0):
         """The yaw (num_envs, N) the look-up table in `table_slot` (backend.WfStep.set_yaw_table on `self.fi`) holds for
@@ -497,15 +525,25 @@ class VecWindFarmEnv:
     # -- checkpoint / resume (the env state is tiny; FLORIS itself is stateless between steps) ------
     def get_state(self) -> dict:
         """Everything needed to resume the batch: device env state, the per-farm wind, the step counter."""
-        if self._series is not None:
-            raise NotImplementedError("checkpointing a time-series episode is not supported")
         ws, wd = self.fi.get_wind()
-        return {**self.fi.env_get_state(), "wind_speed": ws, "wind_direction": wd, "num_iter": self._num_iter,
-                "shaper_ref": None if self._shaper_ref is None else np.asarray(
-                    self._shaper_ref.cpu() if hasattr(self._shaper_ref, "cpu") else self._shaper_ref).copy()}
+        st = {**self.fi.env_get_state(), "wind_speed": ws, "wind_direction": wd, "num_iter": self._num_iter,
+              "shaper_ref": None if self._shaper_ref is None else np.asarray(
+                  self._shaper_ref.cpu() if hasattr(self._shaper_ref, "cpu") else self._shaper_ref).copy()}
+        if self._series is not None:  # a time-series episode: one cursor per farm (include/wfseries.h)
+            cur = self.fi.series_state()
+            st.update(series_t=cur["t"], series_start=cur["start"], series_prev_pending=cur["prev_pending"])
+        return st
 
     def set_state(self, state: dict):
-        self.fi.set_wind(state["wind_speed"], state["wind_direction"])
+        if ("series_t" in state) != (self._series is not None):
+            raise ValueError("the state of a time-series episode resumes on an env with that wind_time_series, and only there: "
+                             + ("this env has none" if self._series is None else "this state holds no series cursor"))
+        if self._series is not None:
+            # the env's own series with the state's start rows, then the cursor: the wind is the series' row again
+            self.fi.set_wind_series(self._series, start=state["series_start"])
+            self.fi.series_seek(state["series_t"], state["series_prev_pending"])
+        else:
+            self.fi.set_wind(state["wind_speed"], state["wind_direction"])
         self.fi.env_set_state(state)
         self._num_iter = int(state["num_iter"])
         ref = state.get("shaper_ref")
