@@ -1,7 +1,13 @@
 // wf_f64_math.h — lean float64 arithmetic of the float64 re-solve (wf_resolve.hip): square root, reciprocal, exp, log, pow and
 // the trigonometric functions of the per-source chain without the device library's range scaling and special cases, plus
-// inline general-range versions for the rare arguments outside the model's normal ranges.  Checked on the device against the
-// library by tools/ubench/lean_f64_check.hip (profiles/r05_lean_f64_check.txt).
+// inline general-range versions for the rare arguments outside the model's normal ranges.
+// Checked on the device against mpmath at 50 digits by tests/test_f64_math_gpu.py (through check/wf_math_check.hip, built
+// under the product's flags; arguments aimed at every interval end, reduction tie and special branch, and the bounds' origin:
+// tests/f64_math_cases.py).  Bounds held there, in ulp of the exact value: rcp64, sqrt_pos, sqrt_nn 1; sincos_small,
+// atan_small, cbrt_pos, cbrt_any 2; exp_lean 3 (subnormal results: 2 * 2^-1074 absolute); log_lean, log_any, tan_small,
+// asin_small, atan_01 4; tan_any (1e-3 away from its poles), atan2_any, asin_any 5; pow_lean, pow_any 3 + 2 |y ln x| (the
+// error of y log x enters the result undamped); sincos_any 3.3e-16 absolute.  tools/ubench/lean_f64_check.hip compares with
+// the device library on one uniform grid (profiles/r05_lean_f64_check.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,7 +21,8 @@ constexpr double kTwoPi = 2.0 * 3.14159265358979323846;
 // exp / log / division are general-range IEEE routines — 17-25, ~50, ~60 and 11+ instructions with range scaling, special-case
 // selects and (exp, log) table lookups; round 4's kernels issued ~3 000 instructions per source stage, three quarters of them
 // inside those routines.  Every operand of this model is a positive, finite, NORMAL double of moderate size, so the routines
-// below drop the scaling and the special cases and keep the accuracy (<= ~2 ulp): the stage is ~800 instructions now.
+// below drop the scaling and the special cases and keep the accuracy (1 to 5 ulp, per routine at the top of this file): the
+// stage is ~800 instructions now.
 // 1 / x from the hardware estimate and two Newton steps (6 instructions; the compiler's IEEE division sequence is 11)
 __device__ __forceinline__ double rcp64(double x) {
   double r = __builtin_amdgcn_rcp(x);
@@ -164,8 +171,11 @@ __device__ __forceinline__ double cbrt_any(double x) {
 // sin / cos of any moderate angle: x = k pi/2 + r (three-part pi/2), |r| <= pi/4, then the series above
 __device__ __forceinline__ void sincos_any(double x, double& s_out, double& c_out) {
   const double k = rint(x * 0.63661977236758134);
+  // (33 + 33 + 53 bits of pi/2: the first two products are exact, the three parts sum to pi/2 within 1e-37.  The middle
+  // part was once the 53-bit tail 6.07710050650619224932e-11 of the FIRST part, which with the third part on top put r off
+  // by k 2e-21: 1e8 ulp of tan_any next to its zeros at k = 200 — tests/test_f64_math_gpu.py)
   double r = fma(k, -1.57079632673412561417e+00, x);
-  r = fma(k, -6.07710050650619224932e-11, r);
+  r = fma(k, -6.07710050630396597660e-11, r);
   r = fma(k, -2.02226624879595063154e-21, r);
   double sr, cr;
   sincos_small(r, sr, cr);
@@ -200,6 +210,8 @@ __device__ __forceinline__ double atan2_any(double y, double x) {
   return copysign(a, y);
 }
 // asin(x), |x| <= 1
-__device__ __forceinline__ double asin_any(double x) { return atan2_any(x, sqrt_nn(fmax(1.0 - x * x, 0.0))); }
+// (the radicand as ONE fma: the product rounded on its own cancels against 1 and costs ~1000 ulp near |x| = 1, and the
+// product's -ffp-contract=off would not fuse `1.0 - x * x`)
+__device__ __forceinline__ double asin_any(double x) { return atan2_any(x, sqrt_nn(fmax(fma(-x, x, 1.0), 0.0))); }
 
 }  // namespace
