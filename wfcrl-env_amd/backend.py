@@ -786,6 +786,65 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the rose kernels as the runtime reports them."""
         return self._rose().kernel_info()
 
+    # -- closed-loop rollouts of yaw-table controllers (include/wfrollout.h) ---------------------------
+    def _rollout(self) -> "_Rollout":
+        """The handle's rollout object, created on its rose object on first use; destroyed in close() before it."""
+        ro = getattr(self, "_rollout_obj", None)
+        if ro is None:
+            ro = self._rollout_obj = _Rollout(self)
+        return ro
+
+    @staticmethod
+    def controller_grid(alphas, deadbands, leads, slot=0):
+        """The full grid of look-up-table controllers over filter gains, deadbands [deg] and previews [steps] on table
+        `slot`: (controllers, params) — the dict controller_returns takes and, index for index, the list of
+        dict(slot, alpha, deadband, lead) each controller stands for (alpha slowest, lead fastest)."""
+        params = [{"slot": int(slot), "alpha": float(a), "deadband": float(d), "lead": int(l)}
+                  for a in np.atleast_1d(alphas) for d in np.atleast_1d(deadbands) for l in np.atleast_1d(leads)]
+        controllers = {"slot": np.array([p["slot"] for p in params], np.int32), "alpha": np.array([p["alpha"] for p in params], np.float64),
+                       "deadband": np.array([p["deadband"] for p in params], np.float32), "lead": np.array([p["lead"] for p in params], np.int32)}
+        return controllers, params
+
+    def controller_returns(self, controllers, horizon, gamma=1.0, wind=None, filter0=None, farms=None, strict=False,
+                           max_eval_farms=65536, want=("returns", "best"), out=None):
+        """What each of K look-up-table controllers earns over the next `horizon` steps of the fused env, in closed loop,
+        from the env state the handle holds, which is read and never changed (include/wfrollout.h; the project's own
+        definition, PARITY UNPINNED beyond the oracle).  At step h controller k observes the wind (obs[min(h + lead, H)],
+        obs[0] the current wind, obs[j] the wind of step j - 1), filters it in float64 (fs += alpha (o_s - fs),
+        fd += alpha wrap(o_d - fd); alpha 1 copies), looks the table of `slot` up at the filtered wind (set_yaw_table's
+        tables, the look-up of lut_policy), clips the target to the env's yaw bounds, holds inside `deadband` degrees and
+        else issues lut_policy's action; the action goes through the step's own budget gate, increment and clip.  The K H
+        yaws of a farm are rows of one batched step; rewards and returns are those of lookahead_returns.
+          controllers  dict of "slot" (default 0), "alpha" in (0, 1] (default 1), "deadband" >= 0 [deg] (default 0), "lead"
+                       0..16 steps (default 0): scalars or sequences, broadcast to a common length K <= 64 — the same K
+                       controllers for every farm.  alpha 1, deadband 0, lead 0 is what lut_policy's action does every step
+          horizon      H, 1 <= H <= 1024, K H <= 4096
+          gamma        discount in [0, 1]
+          wind         (n_farms, H, 2) float64 (speed, direction) the wind step h is solved under; None: the handle's
+                       current wind held; "series" (a handle in series mode): the series' coming rows, read on the device
+          filter0      (n_farms, K, 2) float64 the filter states to start from — a previous call's "filter_final" —; None:
+                       the farm's current wind
+          farms        farm indices (any order), or None: every farm of the batch
+          strict       every row is solved in float64; otherwise the handle's own resolve mode
+          max_eval_farms  rows the evaluator handle may hold, K H per farm: longer lists run in chunks
+          want         of "returns" (n, K) float64, "rewards" (n, K, H) float64, "farm_power" (n, K, H) float64 [W],
+                       "actions" (n, K, H, N) float32 — the RAW actions: what env_step or lookahead_returns would be given —,
+                       "final_yaw" (n, K, N) float32, "gated" (n, K) int32 — (step, turbine) pairs with a closed budget gate —,
+                       "filter_final" (n, K, 2) float64, "best" (n,) int32 — the lowest index among equal maxima
+          out          dict of tensors / arrays of those names to write into
+        actions, final_yaw, gated and filter_final do not depend on the solver: the same bits in every mode.  Deterministic:
+        fixed summation order, no floating-point atomics.  With torch tensors (wind, filter0 or out) the call only enqueues
+        work on torch's current stream and returns torch CUDA tensors."""
+        return self._rollout().run(controllers, horizon, gamma, wind, filter0, farms, strict, max_eval_farms, want, out)
+
+    def rollout_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last controller_returns {"total_ms", "step_ms", "glue_ms"}."""
+        return self._rollout().timing(detail)
+
+    def rollout_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the rollout kernels as the runtime reports them."""
+        return self._rollout().kernel_info()
+
     # -- fused env step (SURVEY f1) ---------------------------------------------------------------
     def env_config(self, yaw_lo=-40.0, yaw_hi=40.0, yaw_step=5.0, actuator_rate=0.3, dt=60.0, budget=0.1,
                    load_coef=0.1, discrete=False, power_mw=False):
@@ -1019,8 +1078,8 @@ class WfStep:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h,
-            # wfcredit.h, wflookahead.h, wfplan.h)
-            for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
+            # wfcredit.h, wflookahead.h, wfplan.h, wfrollout.h — the rollout object, created on the rose object, before it)
+            for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rollout_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
                          "_lookahead_obj", "_plan_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
@@ -1510,6 +1569,85 @@ class _Lookahead(_Ext):
         p = dict(zip(spec, ptrs))
         self._call("run", actions.data_ptr() if on_device else actions.ctypes.data, K, H, wptr, float(gamma), n, fptr,
                    *[p.get(k) for k in self.OUTPUTS], int(on_device))
+        return {k: out[k] for k in spec}
+
+
+class _Rollout(_Ext):
+    """The `wf_rollout` object of a WfStep handle (include/wfrollout.h), created on the handle's rose object."""
+
+    NAME = "rollout"
+    KERNELS = ("layout", "reduce")
+    OUTPUTS = ("returns", "rewards", "farm_power", "actions", "final_yaw", "gated", "filter_final", "best")
+    FIELDS = {"slot": (np.int32, 0), "alpha": (np.float64, 1.0), "deadband": (np.float32, 0.0), "lead": (np.int32, 0)}
+
+    def __init__(self, owner: WfStep):
+        self._w, self._lib = owner, owner._lib
+        self._r = C.c_void_p()
+        check(self._fn("create")(owner._h, owner._rose()._r, C.byref(self._r)), owner._h)
+
+    def _controllers(self, controllers):
+        if not isinstance(controllers, dict) or any(k not in self.FIELDS for k in controllers):
+            raise ValueError("controllers must be a dict of slot, alpha, deadband and / or lead")
+        cols = {}
+        for k, (dtype, default) in self.FIELDS.items():
+            v = controllers.get(k, default)
+            v = np.asarray(v.detach().cpu() if _is_torch(v) else v)
+            if k in ("slot", "lead") and not np.array_equal(v, np.round(v)):
+                raise ValueError(f"controllers[{k!r}] must hold integers")
+            cols[k] = np.atleast_1d(v.astype(dtype)).reshape(-1)
+        K = max(c.size for c in cols.values())
+        if any(c.size not in (1, K) for c in cols.values()):
+            raise ValueError("the controllers' fields must broadcast to a common length K")
+        return {k: np.ascontiguousarray(np.broadcast_to(c, (K,))) for k, c in cols.items()}, K
+
+    def run(self, controllers, horizon, gamma, wind, filter0, farms, strict, max_eval_farms, want, out):
+        w = self._w
+        N = w.num_turbines
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.OUTPUTS for k in want):
+            raise ValueError("want must name returns, rewards, farm_power, actions, final_yaw, gated, filter_final and / or best")
+        ctl, K = self._controllers(controllers)
+        H = int(horizon)
+        self._call("config", int(bool(strict)), int(max_eval_farms or 0))
+        self._call("set_series", int(_is_series(wind)))
+        if _is_series(wind):
+            wind = None
+        fa, n, fptr = self._farms(farms)
+        on_device = _is_torch(wind) or _is_torch(filter0) or (out is not None and any(_is_torch(v) for v in out.values()))
+        like = None
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            like = next(v for v in [wind, filter0] + list((out or {}).values()) if _is_torch(v))
+
+        def f64(a, shape, name, what):
+            if a is None:
+                return None, None
+            if on_device:
+                if not _is_torch(a):
+                    a = torch.as_tensor(np.asarray(a, np.float64), device=like.device)
+                assert a.is_cuda and a.dtype == torch.float64, name
+                a = a.contiguous()
+            else:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+            if tuple(a.shape) != shape:
+                raise ValueError(f"{name} must be {what}")
+            return a, (a.data_ptr() if on_device else a.ctypes.data)
+
+        wind, wptr = f64(wind, (n, H, 2), "wind", "(n_farms, H, 2): the (speed, direction) every step of the horizon is solved under")
+        filter0, f0ptr = f64(filter0, (n, K, 2), "filter0", "(n_farms, K, 2): the (speed, direction) every controller's filter starts from")
+        shapes = {"returns": ((n, K), np.float64), "rewards": ((n, K, H), np.float64), "farm_power": ((n, K, H), np.float64),
+                  "actions": ((n, K, H, N), np.float32), "final_yaw": ((n, K, N), np.float32), "gated": ((n, K), np.int32),
+                  "filter_final": ((n, K, 2), np.float64), "best": ((n,), np.int32)}
+        if H < 1 or K < 1 or K * H > 4096:  # (the library names the limit; no output is sized from a refused shape)
+            shapes = {k: ((0,), d) for k, (_, d) in shapes.items()}
+            out = None
+        spec = {k: shapes[k] for k in self.OUTPUTS if k in want}
+        out, ptrs = self._outputs(out, spec, on_device, like)
+        p = dict(zip(spec, ptrs))
+        self._call("run", K, ctl["slot"].ctypes.data, ctl["alpha"].ctypes.data, ctl["deadband"].ctypes.data, ctl["lead"].ctypes.data,
+                   H, wptr, f0ptr, float(gamma), n, fptr, *[p.get(k) for k in self.OUTPUTS], int(on_device))
         return {k: out[k] for k in spec}
 
 

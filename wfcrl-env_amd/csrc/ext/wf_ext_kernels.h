@@ -1,10 +1,12 @@
-// wf_ext_kernels.h — the device side the extensions share (yawopt/, robust/, rose/, grad/, credit/, lookahead/, plan/): which farm a
+// wf_ext_kernels.h — the device side the extensions share (yawopt/, robust/, rose/, grad/, credit/, lookahead/, plan/, rollout/): which farm a
 // chunk's slot works on, a visit's candidate grid, the visit order of a slot's turbines, the phases the two searches' advance
-// kernels have in common, the fused env's transition and the staged row rewards of credit and lookahead, and the staged row
-// sum of the rose and the robust search.  The per-extension headers build their kernels'
+// kernels have in common, the fused env's transition, the staged row rewards of credit, lookahead and rollout, the returns of K sequences
+// (lookahead, rollout), and the staged row sum of the rose and the robust search.  The per-extension headers build their kernels'
 // argument structs from these; wf_ext.h is the host side.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <climits>
 
 #include "../wf_f64_math.h"
 
@@ -177,9 +179,13 @@ struct WfEnvView {
 
 // The fused env step's transition (wf_kernels.hip: "fused MDP transition"), the same float32 operations in the same order;
 // nothing is written back.  Returns the new yaw; `da` is the increment the accumulator grows by (|da|).
-__device__ __forceinline__ float wf_env_transition(const WfEnvView& e, float y, float a, float acc, int moves_new, float& da) {
+// the budget gate of that transition: closed when the accumulated actuation per move and second has reached the budget
+__device__ __forceinline__ bool wf_env_gate_closed(const WfEnvView& e, float acc, int moves_new) {
   const float frac = __fdiv_rn(__fdiv_rn(__fdiv_rn(acc, e.rate), (float)moves_new), e.dt);
-  if (frac >= e.budget) a = 0.0f;  // the gate zeroes the RAW action: "down" in the discrete encoding (the reference's quirk)
+  return frac >= e.budget;
+}
+__device__ __forceinline__ float wf_env_transition(const WfEnvView& e, float y, float a, float acc, int moves_new, float& da) {
+  if (wf_env_gate_closed(e, acc, moves_new)) a = 0.0f;  // the gate zeroes the RAW action: "down" in the discrete encoding (the reference's quirk)
   if (e.discrete) a = (a - 1.0f) * e.step;
   if (!e.discrete) a = fminf(fmaxf(a, -e.step), e.step);
   da = a;
@@ -242,6 +248,98 @@ inline WfRewardTile wf_reward_tile(int R, int N, int threads, int floats = 6144)
   T = T > R ? R : T;
   T = T > threads ? threads : T;
   return WfRewardTile{T, sp, sl, sizeof(float) * (size_t)T * (sp + sl)};
+}
+
+// ---- the returns of K sequences of H rows (wf_lookahead_reduce_kernel, wf_rollout_reduce_kernel: both are this body, and
+// WfLookaheadReduceArgs / WfRolloutReduceArgs derive from these arguments): ONE WORKGROUP PER SLOT.  The slot's R = K H rows
+// go by in the tiles above; the thread of a tile's row leaves the row's reward in LDS ([K][Hs] doubles, Hs = H | 1 where that
+// fits: no bank conflict when thread k walks sequence k) and writes rewards / farm_power, consecutive threads on consecutive
+// doubles.  After the last tile's barrier thread k forms sequence k's discounted return in ascending h; the argmax is a
+// fixed-order reduction: every thread over its own k ascending, then a tree over the threads in LDS, the larger return and
+// among equal ones the lower index.  The row normalisers: step 0's is the parent's (the pending prev-wind speed, else the
+// current speed), step h >= 1's the speed of row (k, h - 1), read from the evaluator's wind block. ----
+struct WfReturnsReduceArgs {
+  WfSlots sl;
+  int N, K, H;
+  const double* ws;       // the parent's wind speed ...
+  int wind_stride;
+  const double* ws_prev;  // ... or [B] the speed the next env step normalises by (null: the current one): step 0's
+  const double* ews;      // [C R] every row's wind speed: row (k, h - 1)'s normalises step h >= 1
+  float load_coef;
+  double gamma;
+  const float* power_ev;  // [C][R][N] the evaluator's outputs
+  const float* load_ev;   // [C][R][N][4]
+  double* returns;        // rows of this chunk [n_slots][K], or null
+  double* rewards;        // [n_slots][R], or null
+  double* farm_power;     // [n_slots][R], or null
+  int* best;              // [n_slots], or null
+};
+
+// `red` is the block's dynamic LDS: [K][Hs] + [nth] doubles, [nth] ints, then the tile's [T][sp] + [T][sl] floats
+__device__ __forceinline__ void wf_sequence_returns(const WfReturnsReduceArgs& a, int T, int sp, int sl, int Hs, double* red) {
+  const int tid = threadIdx.x, nth = blockDim.x;
+  const int N = a.N, K = a.K, H = a.H, R = K * H;
+  double* rw = red;                                 // [K][Hs] row rewards
+  double* bv = rw + K * Hs;                         // [nth] the argmax tree: returns ...
+  int* bi = reinterpret_cast<int*>(bv + nth);       // [nth] ... and their sequences
+  float* pw = reinterpret_cast<float*>(bi + nth);   // [T][sp] a tile's powers
+  float* ld = pw + T * sp;                          // [T][sl] ... and load values
+  const int slot = blockIdx.x;
+  const int b = wf_slot_farm(a.sl, slot);
+  const double wr0 = a.ws_prev ? a.ws_prev[b] : a.ws[(size_t)b * a.wind_stride];
+  const double* __restrict__ ews = a.ews + (size_t)slot * R;
+  const float* __restrict__ pblk = a.power_ev + (size_t)slot * R * N;
+  const float* __restrict__ lblk = a.load_ev + (size_t)slot * R * 4 * N;
+  double* const rewards = a.rewards ? a.rewards + (size_t)slot * R : nullptr;
+  double* const farm_power = a.farm_power ? a.farm_power + (size_t)slot * R : nullptr;
+  wf_staged_row_rewards(
+      pblk, lblk, R, N, T, sp, sl, a.load_coef, pw, ld,
+      [H, wr0, ews](int row) { return row % H == 0 ? wr0 : ews[row - 1]; },  // the speed BEFORE the step
+      [H, Hs, rw, rewards, farm_power](int row, double r, double psum) {
+        const int k = row / H, h = row - k * H;
+        rw[k * Hs + h] = r;
+        if (rewards) rewards[row] = r;
+        if (farm_power) farm_power[row] = psum;
+      });
+  const double gamma = a.gamma;
+  double best_v = -HUGE_VAL;
+  int best_k = INT_MAX;
+  for (int k = tid; k < K; k += nth) {
+    const double* r = rw + k * Hs;
+    double g = 1.0, ret = 0.0;
+    for (int h = 0; h < H; ++h) {
+      ret += g * r[h];
+      g = g * gamma;
+    }
+    if (a.returns) a.returns[(size_t)slot * K + k] = ret;
+    if (ret > best_v || (ret == best_v && k < best_k)) { best_v = ret; best_k = k; }
+  }
+  bv[tid] = best_v;
+  bi[tid] = best_k;
+  __syncthreads();
+  for (int s = nth >> 1; s > 0; s >>= 1) {  // (block-uniform)
+    if (tid < s) {
+      const double v = bv[tid + s];
+      const int k = bi[tid + s];
+      if (v > bv[tid] || (v == bv[tid] && k < bi[tid])) { bv[tid] = v; bi[tid] = k; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0 && a.best) a.best[slot] = bi[0] == INT_MAX ? 0 : bi[0];
+}
+
+// its launch: one wave for a few short rows, the odd stride where [K][H | 1] doubles fit in 36 KiB, the tile, the LDS bytes
+struct WfReturnsLaunch {
+  int threads, Hs;
+  WfRewardTile t;
+  size_t lds_bytes;
+};
+inline WfReturnsLaunch wf_returns_launch(int N, int K, int H) {
+  const int R = K * H;
+  const int threads = R * N <= 512 ? 64 : 256;
+  const int Hs = K * (H | 1) <= 4608 ? (H | 1) : H;
+  const WfRewardTile t = wf_reward_tile(R, N, threads);
+  return WfReturnsLaunch{threads, Hs, t, sizeof(double) * ((size_t)K * Hs + threads) + sizeof(int) * threads + t.lds_bytes};
 }
 
 // ---- the staged row sum (wf_rose_rowsum_kernel, wf_robust_rowsum_kernel): a block of ONE wave stages the N float32 powers of

@@ -24,22 +24,8 @@ struct WfLookaheadLayoutArgs {
   float* final_yaw;       // [n_slots][K][N] of this chunk, or null
 };
 
-struct WfLookaheadReduceArgs {
-  WfSlots sl;
-  int N, K, H;
-  const double* ws;       // the parent's wind speed ...
-  int wind_stride;
-  const double* ws_prev;  // ... or [B] the speed the next env step normalises by (null: the current one): step 0's
-  const double* ews;      // [C R] every row's wind speed: row (k, h - 1)'s normalises step h >= 1
-  float load_coef;
-  double gamma;
-  const float* power_ev;  // [C][R][N] the evaluator's outputs
-  const float* load_ev;   // [C][R][N][4]
-  double* returns;        // rows of this chunk [n_slots][K], or null
-  double* rewards;        // [n_slots][R], or null
-  double* farm_power;     // [n_slots][R], or null
-  int* best;              // [n_slots], or null
-};
+// the reduce kernel is the shared returns body (ext/wf_ext_kernels.h: wf_sequence_returns) and takes its arguments
+struct WfLookaheadReduceArgs : WfReturnsReduceArgs {};
 
 extern "C" hipError_t wfk_launch_lookahead_layout(const WfLookaheadLayoutArgs* a, hipStream_t s);
 extern "C" hipError_t wfk_launch_lookahead_reduce(const WfLookaheadReduceArgs* a, hipStream_t s);

@@ -25,8 +25,6 @@
 // kernels and the NumPy restatement.
 #include <hip/hip_runtime.h>
 
-#include <climits>
-
 #include "wf_lookahead.h"
 
 __global__ __launch_bounds__(256) void wf_lookahead_layout_kernel(const WfLookaheadLayoutArgs a) {
@@ -64,55 +62,7 @@ __global__ __launch_bounds__(256) void wf_lookahead_layout_kernel(const WfLookah
 
 __global__ __launch_bounds__(256) void wf_lookahead_reduce_kernel(const WfLookaheadReduceArgs a, int T, int sp, int sl, int Hs) {
   extern __shared__ double la_red[];
-  const int tid = threadIdx.x, nth = blockDim.x;
-  const int N = a.N, K = a.K, H = a.H, R = K * H;
-  double* rw = la_red;                              // [K][Hs] row rewards
-  double* bv = rw + K * Hs;                         // [nth] the argmax tree: returns ...
-  int* bi = reinterpret_cast<int*>(bv + nth);       // [nth] ... and their sequences
-  float* pw = reinterpret_cast<float*>(bi + nth);   // [T][sp] a tile's powers
-  float* ld = pw + T * sp;                          // [T][sl] ... and load values
-  const int slot = blockIdx.x;
-  const int b = wf_slot_farm(a.sl, slot);
-  const double wr0 = a.ws_prev ? a.ws_prev[b] : a.ws[(size_t)b * a.wind_stride];
-  const double* __restrict__ ews = a.ews + (size_t)slot * R;
-  const float* __restrict__ pblk = a.power_ev + (size_t)slot * R * N;
-  const float* __restrict__ lblk = a.load_ev + (size_t)slot * R * 4 * N;
-  double* const rewards = a.rewards ? a.rewards + (size_t)slot * R : nullptr;
-  double* const farm_power = a.farm_power ? a.farm_power + (size_t)slot * R : nullptr;
-  wf_staged_row_rewards(
-      pblk, lblk, R, N, T, sp, sl, a.load_coef, pw, ld,
-      [H, wr0, ews](int row) { return row % H == 0 ? wr0 : ews[row - 1]; },  // the speed BEFORE the step
-      [H, Hs, rw, rewards, farm_power](int row, double r, double psum) {
-        const int k = row / H, h = row - k * H;
-        rw[k * Hs + h] = r;
-        if (rewards) rewards[row] = r;
-        if (farm_power) farm_power[row] = psum;
-      });
-  const double gamma = a.gamma;
-  double best_v = -HUGE_VAL;
-  int best_k = INT_MAX;
-  for (int k = tid; k < K; k += nth) {
-    const double* r = rw + k * Hs;
-    double g = 1.0, ret = 0.0;
-    for (int h = 0; h < H; ++h) {
-      ret += g * r[h];
-      g = g * gamma;
-    }
-    if (a.returns) a.returns[(size_t)slot * K + k] = ret;
-    if (ret > best_v || (ret == best_v && k < best_k)) { best_v = ret; best_k = k; }
-  }
-  bv[tid] = best_v;
-  bi[tid] = best_k;
-  __syncthreads();
-  for (int s = nth >> 1; s > 0; s >>= 1) {  // (block-uniform)
-    if (tid < s) {
-      const double v = bv[tid + s];
-      const int k = bi[tid + s];
-      if (v > bv[tid] || (v == bv[tid] && k < bi[tid])) { bv[tid] = v; bi[tid] = k; }
-    }
-    __syncthreads();
-  }
-  if (tid == 0 && a.best) a.best[slot] = bi[0] == INT_MAX ? 0 : bi[0];
+  wf_sequence_returns(a, T, sp, sl, Hs, la_red);
 }
 
 extern "C" hipError_t wfk_launch_lookahead_layout(const WfLookaheadLayoutArgs* a, hipStream_t s) {
@@ -121,12 +71,8 @@ extern "C" hipError_t wfk_launch_lookahead_layout(const WfLookaheadLayoutArgs* a
   return hipGetLastError();
 }
 extern "C" hipError_t wfk_launch_lookahead_reduce(const WfLookaheadReduceArgs* a, hipStream_t s) {
-  const int N = a->N, K = a->K, H = a->H, R = K * H;
-  const int threads = R * N <= 512 ? 64 : 256;
-  const int Hs = K * (H | 1) <= 4608 ? (H | 1) : H;  // the odd stride where [K][H | 1] doubles fit in 36 KiB
-  const WfRewardTile t = wf_reward_tile(R, N, threads);
-  const size_t lds = sizeof(double) * ((size_t)K * Hs + threads) + sizeof(int) * threads + t.lds_bytes;
-  hipLaunchKernelGGL(wf_lookahead_reduce_kernel, dim3(a->sl.n_slots), dim3(threads), lds, s, *a, t.T, t.sp, t.sl, Hs);
+  const WfReturnsLaunch l = wf_returns_launch(a->N, a->K, a->H);
+  hipLaunchKernelGGL(wf_lookahead_reduce_kernel, dim3(a->sl.n_slots), dim3(l.threads), l.lds_bytes, s, *a, l.t.T, l.t.sp, l.t.sl, l.Hs);
   return hipGetLastError();
 }
 extern "C" hipError_t wfk_lookahead_func_attributes(int kernel, hipFuncAttributes* a) {

@@ -16,6 +16,16 @@ struct WfRoseTable {
   int Dt, St, interp;
 };
 
+// Read access to a rose object's tables for an object created on it (rollout/): slot's device table as the kernels take it
+// (T == null: empty) and the turbine count it was set for.  The pointers stay valid until the slot is set again or the rose
+// object is destroyed; the work that reads them is enqueued on the same stream as wf_rose_set_table's copies.
+struct wf_rose;
+struct wf_handle;
+namespace wfi {
+WfRoseTable rose_device_table(const wf_rose* r, int slot, int* N);
+wf_handle* rose_parent(const wf_rose* r);
+}  // namespace wfi
+
 struct WfRoseShape {
   int D, C, S, N;
   int row0, n_rows, E;  // this chunk

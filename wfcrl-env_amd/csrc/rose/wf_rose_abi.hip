@@ -40,6 +40,18 @@ WfRoseTable device_table(const wf_rose::Slot& s) {
 
 }  // namespace
 
+namespace wfi {
+
+WfRoseTable rose_device_table(const wf_rose* r, int slot, int* N) {
+  const wf_rose::Slot& s = r->slot[slot];
+  if (N) *N = s.N;
+  return device_table(s);
+}
+
+wf_handle* rose_parent(const wf_rose* r) { return r->h; }
+
+}  // namespace wfi
+
 extern "C" {
 
 int wf_rose_create(wf_handle* h, wf_rose** out) { return ext_create(h, out); }

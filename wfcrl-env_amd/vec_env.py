@@ -487,6 +487,48 @@ class VecWindFarmEnv:
         return self.fi.plan_actions(horizon, candidates=candidates, elites=elites, sigma=sigma, seed=seed, gamma=gamma, wind=wind,
                                     mean=mean, farms=farms, strict=strict, max_eval_farms=max_eval_farms, want=want, out=out)
 
+    def controller_returns(self, controllers, horizon, gamma=1.0, wind=None, filter0=None, farms=None, strict=False,
+                           max_eval_farms=65536, want=("returns", "best")):
+        """What each of K look-up-table controllers — table slot, filter gain alpha, deadband, preview `lead` — earns over
+        the next `horizon` steps under the env's own actuator, in closed loop, from the state the env is in: call it BEFORE
+        `step`; the env state is read and never changed (include/wfrollout.h; backend.WfStep.controller_returns has the
+        arguments and WfStep.controller_grid builds a tuning grid; the project's own definition).  Returns the outputs
+        `want` names — "returns", "rewards", "farm_power", "actions", "final_yaw", "gated", "filter_final", "best" —, torch
+        CUDA tensors when the env returns torch.  controllers alpha 1, deadband 0, lead 0 is what stepping with
+        `lut_action()` does; {"yaw": actions[:, k, h]} is what to give `step` to replay controller k.  The tables are those
+        of `self.fi.set_yaw_table`.  Run on a handle of its own: the env's yaw state, accumulators, wind and buffers are
+        read, never changed.  On a time-series episode the wind of the coming steps is not the one the env holds:
+        wind="series" reads the series' coming rows on the device (include/wfseries.h), or the caller passes them as
+        wind=(n_farms, horizon, 2)."""
+        series = isinstance(wind, str) and wind == "series"
+        if series and self._series is None:
+            raise ValueError('wind="series" needs a time-series episode: this env has no wind_time_series')
+        if self._series is not None and wind is None:
+            raise NotImplementedError("controller_returns on a time-series episode needs wind=(n_farms, horizon, 2): the series "
+                                      "tick precedes the step, so the wind of the coming steps is not the one the env holds "
+                                      '(or wind="series": the series\' coming rows, read on the device)')
+        if type(self.reward_shaper).__name__ != "DoNothingReward":
+            raise ValueError("controller_returns needs the plain reward (DoNothingReward): the return of a shaped reward is "
+                             "not defined here")
+        out = None
+        if self.return_torch:
+            import torch
+
+            wind = wind if wind is None or series else self._to_device(wind).double()
+            filter0 = None if filter0 is None else self._to_device(filter0).double()
+            want = (want,) if isinstance(want, str) else tuple(want)
+            n = self.num_envs if farms is None else int(np.asarray(farms).size)
+            K, H, N = self.fi._rollout()._controllers(controllers)[1], int(horizon), self.num_turbines
+            shapes = {"returns": ((n, K), torch.float64), "rewards": ((n, K, H), torch.float64), "farm_power": ((n, K, H), torch.float64),
+                      "actions": ((n, K, H, N), torch.float32), "final_yaw": ((n, K, N), torch.float32), "gated": ((n, K), torch.int32),
+                      "filter_final": ((n, K, 2), torch.float64), "best": ((n,), torch.int32)}
+            if any(k not in shapes for k in want):
+                raise ValueError("want must name returns, rewards, farm_power, actions, final_yaw, gated, filter_final and / or best")
+            if 1 <= H and 1 <= K and K * H <= 4096:  # (a refused shape sizes nothing: the library names the limit)
+                out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=f"cuda:{self.fi.device_id}") for k in want}
+        return self.fi.controller_returns(controllers, horizon, gamma=gamma, wind=wind, filter0=filter0, farms=farms, strict=strict,
+                                          max_eval_farms=max_eval_farms, want=want, out=out)
+
     def _series_keyword(self, name, wind, steps):
         """The wind keyword of counterfactual_rewards / lookahead_returns: None or "series"; a time-series episode needs
         "series", any other episode None."""
