@@ -9,7 +9,9 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/fuzz_head.txt
 : > $O
-leg() { echo "## $*" >> $O; timeout ${LEG_TIMEOUT:-2400} env "$@" 2>&1 | grep -v amdgpu.ids | grep -E "^BAD|^fuzz|^api|^env|^family" | cut -c1-1500 >> $O; }
+# (a leg that ran into its time limit, aborted or faulted ends the campaign: nothing more is started on that card)
+leg() { echo "## $*" >> $O; timeout -k 10 ${LEG_TIMEOUT:-2400} env "$@" 2>&1 | grep -v amdgpu.ids | grep -E "^BAD|^fuzz|^api|^env|^family" | cut -c1-1500 >> $O
+        rc=${PIPESTATUS[0]}; case $rc in 124|134|137|139) echo "leg ended with status $rc: campaign stopped" | tee -a $O; exit $rc;; esac; }
 S=${FUZZ_SCALE:-5}  # (round 6: the default is the scale that found round 5's only real defect; FUZZ_SCALE=1 for an interim record)
 leg python tests/tools/fuzz_parity.py $((500 * S)) 5011
 leg WF_FUZZ_RESOLVE=1 python tests/tools/fuzz_parity.py $((400 * S)) 5021

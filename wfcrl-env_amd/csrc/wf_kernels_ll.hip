@@ -65,6 +65,39 @@
 #ifndef WF_LL_PART
 #define WF_LL_PART 0
 #endif
+// Three switches of the replay of logged sources (table path); none changes an operation or the order of a sum, only where
+// loads are issued and waited for.  The defaults are what ships: the two-slot unit (part 1) with the chunk wait stated and
+// one wait per slot, every other kernel as it was.  A/B builds: tools/build_alt.sh; figures: profiles/replay_waits_ab.txt.
+//
+// WF_LL_CHUNK_VMCNT — the chunk's closing wait (wf_dma_wait(): vmcnt(0) in inline assembly, which the compiler does not
+// read) stated to the compiler as well: 0 = no, 1 = yes.  The deficit pass's LAST step fetches a cold record nobody reads
+// (near_step: the load is unconditional); the compiler keeps those three loads on its books as in flight across the chunk's
+// end, and when the next chunk's near test and transverse pass reuse their twelve registers it guards the test's LDS read
+// with s_waitcnt vmcnt(2) and the loop's first three LDS reads with vmcnt(5) / (4) / (3), in EVERY iteration.  The counter is
+// in order and the hardware's count includes the LDS-DMA transfers of the following chunk, issued by hand a few
+// instructions earlier: "all but the newest two or three" waits for exactly those transfers — the wait at the top of the
+// chunk that issued them which the hand-issued transfers were introduced to get rid of (wf_kernel_common.h: lds_dma16).
+// With the wait on the compiler's books nothing is in flight at a chunk's start and the loop carries no vmcnt wait:
+// HornsRev1 x 65 536 -2.5 %.
+#ifndef WF_LL_CHUNK_VMCNT
+#define WF_LL_CHUNK_VMCNT (WF_LL_PART == 1)
+#endif
+// WF_LL_TRANS_WAIT — where the transverse pass waits for a source's pair records, 18 ds_read_b128 at two slots:
+// 0 = where the compiler puts its counted waits — without machine LICM in front of nearly every grid point's five
+// instructions, 33 s_waitcnt per two sources; 1 = once per source, lgkmcnt(0) in front of the first slot's arithmetic
+// (slower: +1.6 %, a source's whole LDS latency stands open); 2 = once per slot, lgkmcnt(9 (S - 1 - p)) in front of slot
+// p's: the later slots' reads land under the earlier slots' arithmetic (another -0.9 %).  The waits are hints between
+// scheduling barriers: the compiler's own bookkeeping stays on, so no setting can read a register early.
+#ifndef WF_LL_TRANS_WAIT
+#define WF_LL_TRANS_WAIT (WF_LL_PART == 1 ? 2 : 0)
+#endif
+// WF_LL_COLD_DEPTH — how many near steps ahead the deficit pass fetches a cold record: 1 = the next near source's, into the
+// other of two register sets; 2 = the one after that, into the third of three sets (12 more VGPRs, a three times unrolled
+// loop; measured equal within the spread: not shipped).
+#ifndef WF_LL_COLD_DEPTH
+#define WF_LL_COLD_DEPTH 1
+#endif
+static_assert(WF_LL_TRANS_WAIT >= 0 && WF_LL_TRANS_WAIT <= 2 && (WF_LL_COLD_DEPTH == 1 || WF_LL_COLD_DEPTH == 2), "replay A/B switches");
 
 namespace {
 
@@ -77,6 +110,17 @@ __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int
 template <int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// wait until at most LGKM of the wave's LDS reads are outstanding, where it stands: nothing is scheduled across it.
+// (s_waitcnt of gfx9: vmcnt 63 and expcnt 7 = not waited for — the hand-issued LDS-DMA transfers count on vmcnt and stay
+// wf_dma_wait()'s business — lgkmcnt in bits 11:8)
+template <int LGKM>
+__device__ __forceinline__ void lds_wait_here() {
+  static_assert(LGKM >= 0 && LGKM <= 15, "lgkmcnt has four bits");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt(0xC07F | (LGKM << 8));
+  __builtin_amdgcn_sched_barrier(0);
 }
 
 // sin / cos of the commanded yaw from the angle in radians: |yaw| <= 45 deg for every admissible command, where the
@@ -1218,6 +1262,11 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
           // the first near source's cold record is fetched now and lands while the transverse pass runs
           ColdRec cold_nx = {};
           if (near_bits) cold_nx = load_cold(i0 + (__builtin_ctzll(near_bits) / GS));
+#if WF_LL_COLD_DEPTH == 2
+          // (the second near source's beside it: the deficit pass fetches two steps ahead, into the third of three sets)
+          ColdRec cold_b = {}, cold_c = {};
+          if (near_bits & (near_bits - 1ull)) cold_b = load_cold(i0 + (__builtin_ctzll(near_bits & (near_bits - 1ull)) / GS));
+#endif
           // -- transverse pass: every logged source of the chunk, two per iteration (their hot records are one float4,
           // staged into wave-private LDS by hand-issued LDS-DMA a chunk ahead: the loop holds no global load at all).  Two
           // sources per iteration, ~230 instructions.  No lane mask: every real turbine of this block is at or downstream of an earlier block's
@@ -1227,6 +1276,7 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
           for (int k = 0; k < k_log; k += 2) {
             const float4 hot2 = hotL[(q & 1) * HOT_F4 + (k >> 1) * EPW + eiw];  // {rho, Gwt} of sources i0 + k, i0 + k + 1
             float4 cf[S][9];
+#if WF_LL_TRANS_WAIT == 0
 #pragma unroll
             for (int p = 0; p < S; ++p)
 #pragma unroll
@@ -1239,6 +1289,27 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
               for (int qq = 0; qq < 9; ++qq)
                 cf[p][qq] = *reinterpret_cast<const float4*>(buf + ((k + 1) * GS + p * G + sub) * WF_PAIR_STRIDE + 4 * qq);
             static_for<S>([&](auto PP) { apply_tab_ratio(PP, cf[decltype(PP)::value], hot2.z, hot2.w); });
+#else
+            // (WF_LL_TRANS_WAIT at the top: all of a source's reads are issued, then waited for once per source or once per
+            // slot — LDS reads return in the order of issue, which the barrier between the slots' reads pins)
+            auto one_source = [&](int kk, float rho, float Gwt) {
+              static_for<S>([&](auto PP) {
+                constexpr int p = decltype(PP)::value;
+#pragma unroll
+                for (int qq = 0; qq < 9; ++qq)
+                  cf[p][qq] = *reinterpret_cast<const float4*>(buf + (kk * GS + p * G + sub) * WF_PAIR_STRIDE + 4 * qq);
+                if constexpr (WF_LL_TRANS_WAIT == 2 && p + 1 < S) __builtin_amdgcn_sched_barrier(0);
+              });
+              static_for<S>([&](auto PP) {
+                constexpr int p = decltype(PP)::value;
+                if constexpr (WF_LL_TRANS_WAIT == 2) lds_wait_here<9 * (S - 1 - p)>();
+                else if constexpr (p == 0) lds_wait_here<0>();
+                apply_tab_ratio(PP, cf[p], rho, Gwt);
+              });
+            };
+            one_source(k, hot2.x, hot2.y);
+            one_source(k + 1, hot2.z, hot2.w);
+#endif
           }
           WF_T(st_ab);
           WF_ACC(11, st_a, st_ab);  // (the transverse pass's share of the replay)
@@ -1258,6 +1329,13 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
             // with the hand-issued transfers the position no longer matters: measured equal either way, profiles/r05_hotlds_ablation.txt.)
 #ifdef WF_EXP_NOCOLD  // timing experiment only (wrong results): the deficit pass without its cold-record loads
             nxt = cold;
+#elif WF_LL_COLD_DEPTH == 2
+            // (two steps ahead: near_bits holds the sources behind this one; the record of the SECOND of them — the first's is
+            // in flight or landed — or, with fewer than two left, this step's own, as above.  Like every logged source it
+            // belongs to an earlier block: this wave wrote it earlier in program order, in whole lines of its own — the cache-line
+            // discipline of the log, see stage_hot, is the same at any depth.)
+            const unsigned long long ahead2 = near_bits & (near_bits - 1ull);
+            nxt = load_cold(ahead2 ? i0 + (__builtin_ctzll(ahead2) / GS) : i);
 #else
             nxt = load_cold(near_bits ? i0 + (__builtin_ctzll(near_bits) / GS) : i);
 #endif
@@ -1271,10 +1349,30 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
               if ((pair_bits >> (k * GS + p * G)) & ((1ull << G) - 1ull)) pass2(PP, Sl, side, true, exs[p], tvalid[p]);
             });
           };
+#if WF_LL_COLD_DEPTH == 1
           ColdRec cold_b = {};
+#endif
           // (the deficit pass waits for its cold records: ahead of the other wave's transverse pass and outputs, behind its
           // own-source chain — HornsRev1 x 65 536 another -2.4 %, profiles/r05_setprio_ab.txt)
           __builtin_amdgcn_s_setprio(1);
+#if WF_LL_COLD_DEPTH == 2
+          // (three sets in rotation: step m reads set m mod 3 and fetches the record of step m + 2 into set (m + 2) mod 3, which
+          // step m - 1 has finished with)
+#pragma unroll 1
+          while (near_bits) {
+            const int k0 = __builtin_ctzll(near_bits) / GS;
+            near_bits &= near_bits - 1ull;
+            near_step(k0, cold_nx, cold_c);
+            if (!near_bits) break;
+            const int k1 = __builtin_ctzll(near_bits) / GS;
+            near_bits &= near_bits - 1ull;
+            near_step(k1, cold_b, cold_nx);
+            if (!near_bits) break;
+            const int k2 = __builtin_ctzll(near_bits) / GS;
+            near_bits &= near_bits - 1ull;
+            near_step(k2, cold_c, cold_b);
+          }
+#else
 #pragma unroll 1
           while (near_bits) {
             const int k0 = __builtin_ctzll(near_bits) / GS;
@@ -1285,6 +1383,7 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
             near_bits &= near_bits - 1ull;
             near_step(k1, cold_b, cold_nx);
           }
+#endif
           __builtin_amdgcn_s_setprio(0);
         }
       } else {
@@ -1339,6 +1438,10 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
       WF_ACC(1, st_b, st_c);
       if constexpr (TAB) {
         wf_dma_wait();    // this wave's transfers for the next chunk (pair records, hot records) have landed ...
+#if WF_LL_CHUNK_VMCNT
+        // ... and the compiler is told so (see WF_LL_CHUNK_VMCNT at the top): the same wait once more, in its own bookkeeping
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt 0, expcnt 7, lgkmcnt 15
+#endif
         __syncthreads();  // ... and so have everyone else's; everyone is done with this chunk
       }
       WF_T(st_d);
