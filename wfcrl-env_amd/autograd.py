@@ -1,4 +1,5 @@
-"""torch autograd through the farm step: `differentiable_power` (include/wfgrad.h).
+"""torch autograd through the farm step: `differentiable_power` (include/wfgrad.h) and, through H steps of the fused env,
+`differentiable_return` (include/wfretgrad.h; its docstring below).
 
     power = differentiable_power(wfstep, yaw)          # (B, N) float32, W
     (power * credit).sum().backward()                  # yaw.grad: (B, N) float32, W/deg
@@ -48,3 +49,45 @@ def differentiable_power(wfstep, yaw, step=1.0, bounds=(-45.0, 45.0), strict=Fal
     if tuple(yaw.shape) != (wfstep.env_batch, wfstep.num_turbines):
         raise ValueError("yaw must be (env_batch, num_turbines)")
     return _DifferentiablePower.apply(yaw, wfstep, float(step), (float(bounds[0]), float(bounds[1])), bool(strict))
+
+
+class _DifferentiableReturn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, actions, wfstep, gamma, wind, delta, strict):
+        a = actions.detach().contiguous()
+        r = wfstep.return_gradient(a, gamma=gamma, wind=wind, delta=delta, strict=strict, want=("returns", "action_gradient"))
+        ctx.save_for_backward(r["action_gradient"])
+        ctx.dtype = actions.dtype
+        return r["returns"]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (g,) = ctx.saved_tensors
+        return (grad_output[..., None, None] * g).to(ctx.dtype), None, None, None, None, None
+
+
+def differentiable_return(wfstep, actions, gamma=1.0, wind=None, delta=1.0, strict=False):
+    """(B, K) float64 discounted H-step returns of `wfstep` (a backend.WfStep with an env state) for actions — a
+    (B, K, H, N) float32 CUDA tensor in the continuous encoding — with a backward pass (include/wfretgrad.h).
+
+        ret = differentiable_return(wfstep, actions, gamma=0.95)      # (B, K) float64
+        ret.sum().backward()                                          # actions.grad: (B, K, H, N) float32, reward / deg
+
+    Forward is ONE run of the return-gradient extension, which also keeps action_gradient; backward is
+    grad_output[..., None, None] * action_gradient cast to the dtype of `actions`: no second run.
+
+    What the derivative is.  As differentiable_power's, a DIFFERENCE QUOTIENT at a finite step: per step of the horizon
+    turbine i of the yaw the transition reaches is moved to y+ = float32(min(y + delta, hi)) and y- = float32(max(y - delta, lo))
+    — hi, lo the env's yaw bounds —, q = (r(y+) - r(y-)) / (y+ - y-), one-sided at a bound and exactly 0 where y+ <= y-.  It is
+    chained to the actions through a 0/1 TRANSITION JACOBIAN: 1 where the budget gate, the clip to +-yaw_step and the clip to
+    the yaw bounds returned their input unchanged, else 0; the dependence of later gates on the accumulated actuation is
+    piecewise constant and contributes 0.  It is not an analytic or adjoint derivative of the step kernels: the model has
+    kinks and `delta` sets the scale at which they are seen.
+
+    The env state and the wind are those of the FORWARD (wind: as WfStep.lookahead_returns — None, (B, H, 2) or "series");
+    nothing is read at backward time.  strict solves every row in float64."""
+    if not (torch.is_tensor(actions) and actions.is_cuda and actions.dtype == torch.float32):
+        raise ValueError("differentiable_return needs a float32 CUDA tensor (env_batch, K, H, num_turbines)")
+    if actions.ndim != 4 or actions.shape[0] != wfstep.env_batch or actions.shape[3] != wfstep.num_turbines:
+        raise ValueError("actions must be (env_batch, K, H, num_turbines)")
+    return _DifferentiableReturn.apply(actions, wfstep, float(gamma), wind, float(delta), bool(strict))

@@ -668,6 +668,50 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the lookahead kernels as the runtime reports them."""
         return self._lookahead().kernel_info()
 
+    # -- the gradient of look-ahead returns w.r.t. the action sequences (include/wfretgrad.h) ------------
+    def _retgrad(self) -> "_RetGrad":
+        """The handle's retgrad object; created on first use, destroyed in close() before the handle."""
+        ro = getattr(self, "_retgrad_obj", None)
+        if ro is None:
+            ro = self._retgrad_obj = _RetGrad(self)
+        return ro
+
+    def return_gradient(self, actions, gamma=1.0, wind=None, terminal=None, delta=1.0, farms=None, strict=False,
+                        max_eval_farms=65536, want=("returns", "action_gradient"), out=None):
+        """The derivative of lookahead_returns' H-step return with respect to the action sequences that produce it, from the
+        env state the handle holds, which is read and never changed — call it before env_step (include/wfretgrad.h; the
+        project's own definition, PARITY UNPINNED beyond the oracle).  The step's own transition walks every sequence and
+        records where the gate and the two clips returned their input unchanged (the 0/1 transition Jacobian); per step the
+        base yaw and a +- delta row per turbine are rows of one batched step — K H (2 N + 1) per farm —, q = (r+ - r-) / d is
+        the reward's difference quotient (include/wfgrad.h's perturbation, one-sided at a yaw bound), and a backward sweep
+        over the horizon, lam = gamma^h q + lam, in float64, carries it to every action.  Later gates' dependence on the
+        accumulated actuation is piecewise constant: its derivative is taken as 0.  Continuous encoding only.
+          actions    (n_farms, K, H, N) float32 (block i belongs to farms[i]) — torch CUDA tensor or NumPy; 1 <= H <= 64,
+                     K H (2 N + 1) <= max_eval_farms
+          gamma      discount in [0, 1]
+          wind       as lookahead_returns: (n_farms, H, 2) float64, None (the current wind held) or "series"
+          terminal   (n_farms, K, N) float64 or None (zeros): the derivative of a terminal value w.r.t. the final yaw
+          delta      the perturbation in degrees
+          farms, strict, max_eval_farms   as lookahead_returns; a quotient carries (bound+ + bound-) / d of the step's
+                     tolerance, so strict=True is the mode for validation
+          want       of "returns", "rewards", "farm_power", "final_yaw", "best" (lookahead_returns' base outputs),
+                     "action_gradient" (n, K, H, N) float64 [reward / deg], "reward_gradient" (n, K, H, N) float64 — the
+                     undiscounted q —, "state_gradient" (n, K, N) float64 — w.r.t. the yaw the env holds now —,
+                     "yaw" (n, K, H, N) float32 — the trajectory —, "pass_mask" (n, K, H, N) uint8: bit 0 the action
+                     passes, bit 1 the state passes
+          out        dict of tensors / arrays of those names to write into
+        Deterministic: fixed summation order, no atomics.  With torch tensors the call only enqueues work on torch's current
+        stream."""
+        return self._retgrad().run(actions, gamma, wind, terminal, delta, farms, strict, max_eval_farms, want, out)
+
+    def return_gradient_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last return_gradient {"total_ms", "step_ms", "glue_ms"}."""
+        return self._retgrad().timing(detail)
+
+    def return_gradient_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the retgrad kernels as the runtime reports them."""
+        return self._retgrad().kernel_info()
+
     # -- receding-horizon planner: CEM over action sequences (include/wfplan.h) ------------------------
     def _plan(self) -> "_Plan":
         """The handle's plan object; created on first use, destroyed in close() before the handle."""
@@ -1078,9 +1122,9 @@ class WfStep:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h,
-            # wfcredit.h, wflookahead.h, wfplan.h, wfrollout.h — the rollout object, created on the rose object, before it)
+            # wfcredit.h, wflookahead.h, wfplan.h, wfretgrad.h, wfrollout.h — the rollout object, created on the rose object, before it)
             for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rollout_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
-                         "_lookahead_obj", "_plan_obj"):
+                         "_lookahead_obj", "_plan_obj", "_retgrad_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
                     ext.close()
@@ -1096,7 +1140,7 @@ class WfStep:
 
 
 class _Ext:
-    """An extension object of a WfStep handle — the `wf_<NAME>` of include/wf<NAME>.h — and what the eight wrappers share:
+    """An extension object of a WfStep handle — the `wf_<NAME>` of include/wf<NAME>.h — and what the wrappers share:
     create / close, timing, kernel_info, evaluator, and the conversion of farm lists, (n, N) float32 rows and output dicts
     into the pointers the C ABI takes.  `_r` is the raw object, `KERNELS` names kernel_info's entries in the library's order."""
 
@@ -1569,6 +1613,67 @@ class _Lookahead(_Ext):
         p = dict(zip(spec, ptrs))
         self._call("run", actions.data_ptr() if on_device else actions.ctypes.data, K, H, wptr, float(gamma), n, fptr,
                    *[p.get(k) for k in self.OUTPUTS], int(on_device))
+        return {k: out[k] for k in spec}
+
+
+class _RetGrad(_Ext):
+    """The `wf_retgrad` object of a WfStep handle (include/wfretgrad.h)."""
+
+    NAME = "retgrad"
+    KERNELS = ("layout", "reduce", "best")
+    OUTPUTS = ("returns", "rewards", "farm_power", "final_yaw", "best", "action_gradient", "reward_gradient", "state_gradient",
+               "yaw", "pass_mask")
+
+    def run(self, actions, gamma, wind, terminal, delta, farms, strict, max_eval_farms, want, out):
+        w = self._w
+        N = w.num_turbines
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.OUTPUTS for k in want):
+            raise ValueError("want must name " + ", ".join(self.OUTPUTS[:-1]) + " and / or " + self.OUTPUTS[-1])
+        self._call("config", int(bool(strict)), int(max_eval_farms or 0))
+        fa, n, fptr = self._farms(farms)
+        on_device = _is_torch(actions)
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            assert actions.is_cuda and actions.dtype == torch.float32, "actions"
+            actions = actions.contiguous()
+        else:
+            actions = np.ascontiguousarray(actions, dtype=np.float32)
+        shape = tuple(actions.shape)
+        if len(shape) != 4 or shape[0] != n or shape[3] != N:
+            raise ValueError("actions must be (n_farms, K, H, num_turbines): K sequences of H joint actions per listed farm")
+        K, H = int(shape[1]), int(shape[2])
+        self._call("set_series", int(_is_series(wind)))
+        if _is_series(wind):
+            wind = None
+
+        def f64(a, shape, name, what):
+            if a is None:
+                return None, None
+            if on_device:
+                if not _is_torch(a):
+                    a = torch.as_tensor(np.asarray(a, np.float64), device=actions.device)
+                assert a.is_cuda and a.dtype == torch.float64, name
+                a = a.contiguous()
+            else:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+            if tuple(a.shape) != shape:
+                raise ValueError(f"{name} must be {what}")
+            return a, (a.data_ptr() if on_device else a.ctypes.data)
+
+        wind, wptr = f64(wind, (n, H, 2), "wind", "(n_farms, H, 2): the (speed, direction) every step of the horizon is solved under")
+        terminal, tptr = f64(terminal, (n, K, N), "terminal", "(n_farms, K, num_turbines): the terminal value's derivative w.r.t. the final yaw")
+        seq = ((n, K, H, N), np.float64)
+        shapes = {"returns": ((n, K), np.float64), "rewards": ((n, K, H), np.float64), "farm_power": ((n, K, H), np.float64),
+                  "final_yaw": ((n, K, N), np.float32), "best": ((n,), np.int32), "action_gradient": seq, "reward_gradient": seq,
+                  "state_gradient": ((n, K, N), np.float64), "yaw": ((n, K, H, N), np.float32), "pass_mask": ((n, K, H, N), np.uint8)}
+        spec = {k: shapes[k] for k in self.OUTPUTS if k in want}
+        out, ptrs = self._outputs(out, spec, on_device, actions)
+        p = dict(zip(spec, ptrs))
+        self._call("run", actions.data_ptr() if on_device else actions.ctypes.data, K, H, wptr, float(gamma), float(delta), tptr,
+                   n, fptr, *[p.get(k) for k in self.OUTPUTS], int(on_device))
         return {k: out[k] for k in spec}
 
 

@@ -1,10 +1,10 @@
-// wf_ext.h — the host layer every extension object (probe/, yawopt/, rose/, robust/, grad/, credit/, lookahead/, plan/, rollout/) stands on: the base
+// wf_ext.h — the host layer every extension object (probe/, yawopt/, rose/, robust/, grad/, credit/, lookahead/, plan/, rollout/, retgrad/) stands on: the base
 // struct with the parent handle, the error text and the event pool; a grow-only device buffer that frees itself; the
 // evaluator — a further handle that follows the parent, configured through the public ABI of include/wfstep.h only; the
 // checks an extension asks of its parent and of a farm list; the staging of a host caller's arrays (staging); event
 // recording and the step / glue split of a timed run; kernel attributes; and the two drivers that enqueue a whole run on the
 // parent's stream: run_rows — R evaluator rows for each of n items, in chunks: lay-out, one step, reduce (grad/, credit/,
-// lookahead/, rollout/, rose/, robust/'s evaluation) — and run_search, the coordinate search over yaw of yawopt/ and robust/, with its
+// lookahead/, rollout/, retgrad/, rose/, robust/'s evaluation) — and run_search, the coordinate search over yaw of yawopt/ and robust/, with its
 // configuration.  wf_ext.hip holds the non-template parts, wf_ext_kernels.h the device side.
 // A new extension starts here: derive its object from ext_base, declare its buffers as dev_buf, and call these.
 #pragma once
@@ -113,7 +113,7 @@ inline WfSlots chunk_slots(const farm_list& fl, const int* farms, int base, int 
 // element type, lie end to end (16-byte aligned) in `buf`, in the order they were named: in() for what the kernels read,
 // out() for what they write; *d is the array's device pointer, null for a null array — a host caller's from begin() on.
 struct staging {
-  static constexpr int kMaxSegs = 10;  // the most arrays one call names (wf_rollout_run: two inputs, eight outputs)
+  static constexpr int kMaxSegs = 13;  // the most arrays one call names (wf_retgrad_run: three inputs, ten outputs)
   ext_base* x;
   dev_buf<char>& buf;
   bool host;

@@ -1,6 +1,6 @@
-// wf_ext_kernels.h — the device side the extensions share (yawopt/, robust/, rose/, grad/, credit/, lookahead/, plan/, rollout/): which farm a
+// wf_ext_kernels.h — the device side the extensions share (yawopt/, robust/, rose/, grad/, credit/, lookahead/, plan/, rollout/, retgrad/): which farm a
 // chunk's slot works on, a visit's candidate grid, the visit order of a slot's turbines, the phases the two searches' advance
-// kernels have in common, the fused env's transition, the staged row rewards of credit, lookahead and rollout, the returns of K sequences
+// kernels have in common, the fused env's transition, the staged row rewards of credit, lookahead, rollout and retgrad, the returns of K sequences
 // (lookahead, rollout), and the staged row sum of the rose and the robust search.  The per-extension headers build their kernels'
 // argument structs from these; wf_ext.h is the host side.
 #pragma once

@@ -449,6 +449,38 @@ class VecWindFarmEnv:
         return self.fi.lookahead_returns(a, gamma=gamma, wind=wind, farms=farms, strict=strict,
                                          want=("returns", "rewards", "final_yaw", "best"))
 
+    def return_gradient(self, action_sequences, gamma=1.0, terminal=None, delta=1.0, farms=None, strict=False, wind=None):
+        """The derivative of lookahead_returns' returns with respect to the action sequences, from the state the env is
+        in — call it BEFORE `step`: dict(returns (n_farms, K) float64, rewards (n_farms, K, H) float64, action_gradient
+        (n_farms, K, H, N) float64 [reward per degree], reward_gradient (n_farms, K, H, N) float64 — the undiscounted
+        per-step quotients —, state_gradient (n_farms, K, N) float64 — with respect to the yaw the env holds —, yaw
+        (n_farms, K, H, N) float32 — the trajectory —, pass_mask (n_farms, K, H, N) uint8), torch CUDA tensors when the env
+        returns torch.  action_sequences is {"yaw": (num_envs, K, H, N)} or the array itself; continuous control only.
+        terminal (n_farms, K, N) float64 is the derivative of a terminal value with respect to the final yaw (a critic's
+        gradient), delta the perturbation in degrees.  A difference quotient at a finite step chained through the
+        transition's 0/1 Jacobian (include/wfretgrad.h; backend.WfStep.return_gradient; the project's own definition).  Run
+        on a handle of its own: the env's yaw state, accumulators, wind and buffers are read, never changed.  strict=True
+        solves every row in float64.  On a time-series episode pass wind="series", as to lookahead_returns."""
+        self._series_keyword("return_gradient", wind, "steps")
+        if type(self.reward_shaper).__name__ != "DoNothingReward":
+            raise ValueError("return_gradient needs the plain reward (DoNothingReward): the return of a shaped reward is "
+                             "not defined here")
+        a = self._to_device(action_sequences["yaw"] if isinstance(action_sequences, dict) else action_sequences)
+        B, N = self.num_envs, self.num_turbines
+        if a.ndim != 4 or a.shape[0] != B or a.shape[3] != N:
+            raise ValueError("action_sequences must be (num_envs, K, H, num_turbines): K sequences of H joint actions per farm")
+        if farms is not None:
+            idx = np.ascontiguousarray(farms, dtype=np.int64).reshape(-1)
+            if self.return_torch:
+                import torch
+
+                a = a[torch.from_numpy(idx).to(a.device)]
+            else:
+                a = a[idx]
+        return self.fi.return_gradient(a, gamma=gamma, wind=wind, terminal=terminal, delta=delta, farms=farms, strict=strict,
+                                       want=("returns", "rewards", "action_gradient", "reward_gradient", "state_gradient", "yaw",
+                                             "pass_mask"))
+
     def plan_actions(self, horizon, candidates=64, elites=8, sigma=None, seed=0, gamma=1.0, wind=None, mean=None, farms=None,
                      strict=False, max_eval_farms=65536, want=("first_action", "plan_return")):
         """A receding-horizon plan for every farm from the state the env is in — call it BEFORE `step`, execute
