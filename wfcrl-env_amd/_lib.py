@@ -64,6 +64,12 @@ class WindDist(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("ws_scale", "ws_shape", "ws_lo", "ws_hi", "wd_mean", "wd_std", "wd_lo", "wd_hi")]
 
 
+class WindProcess(C.Structure):
+    """Mirror of `struct wf_wind_process` (include/wfwindgen.h)."""
+
+    _fields_ = [(n, C.c_double) for n in ("ws_revert", "ws_sigma", "wd_revert", "wd_sigma", "wd_ramp")]
+
+
 class KernelInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in (
         "lanes_per_env", "slots_per_lane", "envs_per_block", "threads_per_block", "grid_blocks",
@@ -277,15 +283,37 @@ RETGRAD_ABI = {
     "wf_retgrad_last_error": (C.c_char_p, [_P]),
 }
 
+# every symbol include/wfwindgen.h declares (synthetic wind episodes: a stochastic wind series per farm, generated and played on
+# the device; the wind source of the five row extensions' series-ahead mode): its own table
+WINDGEN_ABI = {
+    "wf_windgen_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "wf_windgen_destroy": (C.c_int, [_P]),
+    "wf_windgen_generate": (C.c_int, [_P, C.c_int, C.c_ulonglong, C.POINTER(WindDist), C.POINTER(WindProcess), _P, _P]),
+    "wf_windgen_set_kernel": (C.c_int, [_P, C.c_int]),
+    "wf_windgen_step": (C.c_int, [_P]),
+    "wf_windgen_get": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ulonglong),
+                                 C.POINTER(WindDist), C.POINTER(WindProcess)]),
+    "wf_windgen_seek": (C.c_int, [_P, C.c_int, C.c_int]),
+    "wf_windgen_window": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_int), C.c_int]),
+    "wf_windgen_read": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "wf_credit_set_wind_source": (C.c_int, [_P, _P]),
+    "wf_lookahead_set_wind_source": (C.c_int, [_P, _P]),
+    "wf_plan_set_wind_source": (C.c_int, [_P, _P]),
+    "wf_rollout_set_wind_source": (C.c_int, [_P, _P]),
+    "wf_retgrad_set_wind_source": (C.c_int, [_P, _P]),
+    "wf_windgen_kernel_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "wf_windgen_last_error": (C.c_char_p, [_P]),
+}
+
 _lib = None
 
 
 def build(force: bool = False) -> Path:
     """Compile csrc/ into libwfstep.so with hipcc for gfx950 (cross-compiles without a GPU)."""
     srcs = []
-    for d in ("", "ext", "probe", "yawopt", "rose", "robust", "grad", "credit", "lookahead", "plan", "series", "rollout", "retgrad"):  # csrc/ itself, the extensions' shared layer, the extensions
+    for d in ("", "ext", "probe", "yawopt", "rose", "robust", "grad", "credit", "lookahead", "plan", "series", "rollout", "retgrad", "windgen"):  # csrc/ itself, the extensions' shared layer, the extensions
         srcs += sorted((PKG_DIR / "csrc" / d).glob("*.hip")) + sorted((PKG_DIR / "csrc" / d).glob("*.h"))
-    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfprobe.h", "wfyawopt.h", "wfrose.h", "wfrobust.h", "wfgrad.h", "wfcredit.h", "wflookahead.h", "wfplan.h", "wfseries.h", "wfrollout.h", "wfretgrad.h")]
+    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfprobe.h", "wfyawopt.h", "wfrose.h", "wfrobust.h", "wfgrad.h", "wfcredit.h", "wflookahead.h", "wfplan.h", "wfseries.h", "wfrollout.h", "wfretgrad.h", "wfwindgen.h")]
     stale = (not LIB_PATH.exists()) or any(s.stat().st_mtime > LIB_PATH.stat().st_mtime for s in srcs)
     if force or stale:
         subprocess.run(["make", "-j4", "-C", str(PKG_DIR / "csrc")] + (["-B"] if force else []), check=True)
@@ -316,7 +344,7 @@ def load() -> C.CDLL:
             build()
         _share_hip_runtime_with_torch()
         lib = C.CDLL(str(LIB_PATH))
-        for table in (ABI, PROBE_ABI, YAWOPT_ABI, ROSE_ABI, ROBUST_ABI, GRAD_ABI, CREDIT_ABI, LOOKAHEAD_ABI, PLAN_ABI, SERIES_ABI, ROLLOUT_ABI, RETGRAD_ABI):
+        for table in (ABI, PROBE_ABI, YAWOPT_ABI, ROSE_ABI, ROBUST_ABI, GRAD_ABI, CREDIT_ABI, LOOKAHEAD_ABI, PLAN_ABI, SERIES_ABI, ROLLOUT_ABI, RETGRAD_ABI, WINDGEN_ABI):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
                 fn.restype, fn.argtypes = res, args

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import EnvParams, KernelChoice, KernelInfo, ModelParams, WindDist, check
+from ._lib import EnvParams, KernelChoice, KernelInfo, ModelParams, WindDist, WindProcess, check
 
 
 def _is_torch(a) -> bool:
@@ -89,6 +89,8 @@ class WfStep:
         self.device_id = int(device_id)
         self.num_turbines = 0
         self.env_batch = 0
+        self._windgen_obj = None  # the wf_windgen object (include/wfwindgen.h), created on first use ...
+        self._windgen = None  # ... and the same object while a generated wind episode is active (generate_wind), else None
         if model is not None:
             self.set_model(model)
         ragged = (not isinstance(xcoords, np.ndarray) and len(xcoords) > 0 and hasattr(xcoords[0], "__len__")
@@ -238,6 +240,7 @@ class WfStep:
     def set_batch(self, env_batch: int):
         check(self._lib.wf_set_batch(self._h, int(env_batch)), self._h)
         self.env_batch = int(env_batch)
+        self._windgen = None  # (a new batch has no wind: a generated episode ends)
 
     def set_stream(self, hip_stream: int | None, external: bool = True):
         """Adopt an external HIP stream (int handle; 0/None = the null stream) or, with external=False,
@@ -261,12 +264,14 @@ class WfStep:
             ws, wd = wind_speed.contiguous().reshape(-1), wind_direction.contiguous().reshape(-1)
             assert ws.dtype == wd.dtype and str(ws.dtype) == "torch.float64" and ws.is_cuda and wd.is_cuda
             self._follow_torch_stream()
+            self._windgen = None
             check(self._lib.wf_set_wind_counts(self._h, ws.data_ptr(), ws.numel(), wd.data_ptr(), wd.numel(), 1), self._h)
             return
         ws = np.ascontiguousarray(np.atleast_1d(wind_speed), dtype=np.float64)
         wd = np.ascontiguousarray(np.atleast_1d(wind_direction), dtype=np.float64)
         if ws.shape != wd.shape and wd.size != 1:
             raise ValueError("wind_speed and wind_direction must have the same shape (or one direction for all)")
+        self._windgen = None  # (a wind set another way ends a generated episode)
         check(self._lib.wf_set_wind_counts(self._h, ws.ctypes.data, ws.size, wd.ctypes.data, wd.size, 0), self._h)
 
     def sample_wind(self, seed: int, dist: dict | None = None, direction_step: float | None = None):
@@ -279,6 +284,7 @@ class WfStep:
             base.update(dist)
             d = C.byref(WindDist(**base))
         s = C.c_ulonglong(int(seed) & (2**64 - 1))
+        self._windgen = None
         if direction_step:
             check(self._lib.wf_wind_sample_binned(self._h, s, d, float(direction_step)), self._h)
         else:
@@ -293,11 +299,76 @@ class WfStep:
         st = None if start is None else np.ascontiguousarray(start, dtype=np.int32)
         if st is not None and st.shape != (self.env_batch,):
             raise ValueError("start must have one entry per farm")
+        self._windgen = None
         check(self._lib.wf_wind_series(self._h, ts.shape[0], ws.ctypes.data, wd.ctypes.data,
                                        None if st is None else st.ctypes.data, C.c_ulonglong(int(seed) & (2**64 - 1))), self._h)
 
     def wind_series_step(self):
+        if self._windgen is not None:
+            self._windgen.call("step")
+            return
         check(self._lib.wf_wind_series_step(self._h), self._h)
+
+    # -- synthetic wind episodes: a stochastic wind series per farm (include/wfwindgen.h) ---------------
+    def generate_wind(self, T: int, seed: int, process: dict, dist: dict | None = None, ws0=None, wd0=None, kernel: str | None = None):
+        """Generates a wind series of `T` ticks for every farm on the device (include/wfwindgen.h: DEFINITION) and starts
+        playing it: the handle holds tick 0, and wind_series_step, wind_preview, series_state, series_seek and wind="series"
+        of lookahead_returns, plan_actions, counterfactual_rewards, controller_returns and return_gradient work as on a
+        series episode — every farm on a realisation of its own.  set_wind, sample_wind and set_wind_series end the episode.
+          process   dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp): reverts in [0, 1]; sigmas and ramp >= 0 (missing: 0)
+          dist      tick 0's distribution (keys of sample_wind's; None: its default), whose ws_lo / ws_hi clip every speed
+          ws0, wd0  (B,) float64: tick 0 given instead of drawn (both or neither)
+          kernel    None: the library's choice; "serial" (a thread per farm) or "tiled" — the same bits, for measurements"""
+        if kernel not in (None, "serial", "tiled"):
+            raise ValueError('kernel must be None, "serial" or "tiled"')
+        keys = ("ws_revert", "ws_sigma", "wd_revert", "wd_sigma", "wd_ramp")
+        unknown = set(process) - set(keys)
+        if unknown:
+            raise ValueError(f"unknown wind process parameter(s): {sorted(unknown)}")
+        p = WindProcess(**{k: float(process.get(k, 0.0)) for k in keys})
+        d = None
+        if dist is not None:
+            base = dict(ws_scale=8.0, ws_shape=8.0, ws_lo=3.0, ws_hi=28.0, wd_mean=270.0, wd_std=20.0, wd_lo=0.0, wd_hi=360.0)
+            base.update(dist)
+            d = C.byref(WindDist(**base))
+        a0 = [None if a is None else np.ascontiguousarray(np.atleast_1d(a), dtype=np.float64) for a in (ws0, wd0)]
+        for a in a0:
+            if a is not None and a.shape != (self.env_batch,):
+                raise ValueError("ws0 and wd0 must have one entry per farm")
+        if self._windgen_obj is None:
+            self._windgen_obj = _WindGen(self)
+        self._windgen = None
+        self._windgen_obj.call("set_kernel", {None: -1, "serial": 0, "tiled": 1}[kernel])
+        self._windgen_obj.call("generate", int(T), C.c_ulonglong(int(seed) & (2**64 - 1)), d, C.byref(p),
+                               *[None if a is None else a.ctypes.data for a in a0])
+        self._windgen = self._windgen_obj
+
+    def _generated(self) -> "_WindGen":
+        if self._windgen is None:
+            raise ValueError("no generated wind episode is active: generate_wind comes first")
+        return self._windgen
+
+    def generated_wind(self, farms=None, first: int = 0, n: int | None = None) -> np.ndarray:
+        """(n_farms, n, 2) float64 [speed, direction]: ticks first .. first + n - 1 (None: to the last) of the generated series of
+        the listed farms (None: all), read back from the device whatever the cursor is."""
+        g = self._generated()
+        fa = None if farms is None else np.ascontiguousarray(farms, dtype=np.int32).reshape(-1)
+        nf = self.env_batch if fa is None else int(fa.size)
+        first = int(first)
+        n = g.state()["T"] - first if n is None else int(n)
+        out = np.empty((nf, max(n, 0), 2), np.float64)
+        g.call("read", first, n, nf, None if fa is None else fa.ctypes.data, out.ctypes.data)
+        return out
+
+    def generated_wind_state(self) -> dict:
+        """What regenerates the active episode: {"T", "t", "prev_pending", "seed", "dist", "process"}."""
+        return self._generated().state()
+
+    def windgen_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the generator's kernel as the runtime reports them."""
+        if self._windgen_obj is None:
+            self._windgen_obj = _WindGen(self)
+        return self._windgen_obj.kernel_info()
 
     # -- time-series episodes beyond reset / step (include/wfseries.h) ---------------------------------
     def wind_preview(self, H: int, first: int = 1, farms=None, as_torch: bool = False, out=None):
@@ -325,6 +396,9 @@ class WfStep:
             assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (n, H, 2), "out"
             ptr = out.ctypes.data
         avail = C.c_int(0)
+        if self._windgen is not None:
+            self._windgen.call("window", first, H, n, None if fa is None else fa.ctypes.data, ptr, C.byref(avail), int(on_device))
+            return out, int(avail.value)
         check(self._lib.wf_series_window(self._h, first, H, n, None if fa is None else fa.ctypes.data, ptr, C.byref(avail),
                                          int(on_device)), self._h)
         return out, int(avail.value)
@@ -332,6 +406,9 @@ class WfStep:
     def series_state(self) -> dict:
         """The series cursor (include/wfseries.h: wf_series_get): {"T", "t" — ticks made since set_wind_series —, "start" (B,)
         int32, "prev_pending" — the speed of tick t - 1 waits for the next env step's reward}."""
+        if self._windgen is not None:  # every farm plays its own series from row 0
+            st = self._windgen.state()
+            return {"T": st["T"], "t": st["t"], "start": np.zeros(self.env_batch, np.int32), "prev_pending": st["prev_pending"]}
         T, t, pending = C.c_int(), C.c_int(), C.c_int()
         start = np.empty(self.env_batch, np.int32)
         check(self._lib.wf_series_get(self._h, C.byref(T), C.byref(t), start.ctypes.data, C.byref(pending)), self._h)
@@ -339,7 +416,10 @@ class WfStep:
 
     def series_seek(self, t: int, prev_pending: bool = False):
         """Puts the handle in the state `t` ticks after set_wind_series would have left (include/wfseries.h: wf_series_seek);
-        the series and the start rows stay."""
+        the series and the start rows stay.  On a generated episode: include/wfwindgen.h: wf_windgen_seek."""
+        if self._windgen is not None:
+            self._windgen.call("seek", int(t), int(bool(prev_pending)))
+            return
         check(self._lib.wf_series_seek(self._h, int(t), int(bool(prev_pending))), self._h)
 
     def series_kernel_info(self) -> dict:
@@ -1124,11 +1204,12 @@ class WfStep:
             # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h,
             # wfcredit.h, wflookahead.h, wfplan.h, wfretgrad.h, wfrollout.h — the rollout object, created on the rose object, before it)
             for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rollout_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
-                         "_lookahead_obj", "_plan_obj", "_retgrad_obj"):
+                         "_lookahead_obj", "_plan_obj", "_retgrad_obj", "_windgen_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
                     ext.close()
                     setattr(self, name, None)
+            self._windgen = None
             self._lib.wf_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -1158,6 +1239,13 @@ class _Ext:
     def _call(self, name, *args):
         """wf_<NAME>_<name>(object, *args); a failure raises with the text of wf_<NAME>_last_error."""
         _lib.check_ext(self._fn(name)(self._r, *args), self._r, f"wf_{self.NAME}_last_error")
+
+    def _series_mode(self, ahead):
+        """The series-ahead mode of a row extension (include/wfseries.h), and whose series it reads: the generator's while a
+        generated episode is active (include/wfwindgen.h), else the handle's own."""
+        self._call("set_series", int(bool(ahead)))
+        gen = self._w._windgen if ahead else None
+        self._call("set_wind_source", None if gen is None else gen._r)
 
     def timing(self, detail=None):
         if detail is not None:
@@ -1222,6 +1310,24 @@ class _Ext:
         for k, (s, d) in spec.items():
             assert out[k].dtype == d and out[k].flags.c_contiguous and out[k].shape == s, k
         return out, [out[k].ctypes.data for k in spec]
+
+
+class _WindGen(_Ext):
+    """The `wf_windgen` object of a WfStep handle (include/wfwindgen.h)."""
+
+    NAME = "windgen"
+    KERNELS = ("generate", "generate_tiled")
+
+    def call(self, name, *args):
+        self._call(name, *args)
+
+    def state(self) -> dict:
+        T, t, pending, seed = C.c_int(), C.c_int(), C.c_int(), C.c_ulonglong()
+        d, p = WindDist(), WindProcess()
+        self._call("get", C.byref(T), C.byref(t), C.byref(pending), C.byref(seed), C.byref(d), C.byref(p))
+        return {"T": int(T.value), "t": int(t.value), "prev_pending": bool(pending.value), "seed": int(seed.value),
+                "dist": {n: float(getattr(d, n)) for n, _ in WindDist._fields_},
+                "process": {n: float(getattr(p, n)) for n, _ in WindProcess._fields_}}
 
 
 class _Probe(_Ext):
@@ -1520,7 +1626,7 @@ class _Credit(_Ext):
         N = w.num_turbines
         if wind is not None and not _is_series(wind):
             raise ValueError('wind must be None (the current wind) or "series" (the series\' coming row)')
-        self._call("set_series", int(wind is not None))
+        self._series_mode(wind is not None)
         if base_kind not in self.KIND or alt_kind not in self.KIND:
             raise ValueError("base_kind and alt_kind must be 'yaw' or 'action'")
         want = (want,) if isinstance(want, str) else tuple(want)
@@ -1592,7 +1698,7 @@ class _Lookahead(_Ext):
             raise ValueError("actions must be (n_farms, K, H, num_turbines): K sequences of H joint actions per listed farm")
         K, H = int(shape[1]), int(shape[2])
         wptr = None
-        self._call("set_series", int(_is_series(wind)))
+        self._series_mode(_is_series(wind))
         if _is_series(wind):
             wind = None
         if wind is not None:
@@ -1645,7 +1751,7 @@ class _RetGrad(_Ext):
         if len(shape) != 4 or shape[0] != n or shape[3] != N:
             raise ValueError("actions must be (n_farms, K, H, num_turbines): K sequences of H joint actions per listed farm")
         K, H = int(shape[1]), int(shape[2])
-        self._call("set_series", int(_is_series(wind)))
+        self._series_mode(_is_series(wind))
         if _is_series(wind):
             wind = None
 
@@ -1714,7 +1820,7 @@ class _Rollout(_Ext):
         ctl, K = self._controllers(controllers)
         H = int(horizon)
         self._call("config", int(bool(strict)), int(max_eval_farms or 0))
-        self._call("set_series", int(_is_series(wind)))
+        self._series_mode(_is_series(wind))
         if _is_series(wind):
             wind = None
         fa, n, fptr = self._farms(farms)
@@ -1775,7 +1881,7 @@ class _Plan(_Ext):
             sigma = (step, 0.5 * step, 0.25 * step)
         sg = np.ascontiguousarray(np.atleast_1d(sigma), dtype=np.float64).reshape(-1)
         self._call("config", int(bool(strict)), int(max_eval_farms or 0))
-        self._call("set_series", int(_is_series(wind)))
+        self._series_mode(_is_series(wind))
         if _is_series(wind):
             wind = None
         fa, n, fptr = self._farms(farms)

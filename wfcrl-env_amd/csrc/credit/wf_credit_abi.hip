@@ -7,6 +7,7 @@
 // the next env step stays for that step.
 #include "../../../include/wfcredit.h"
 #include "../ext/wf_ext.h"
+#include "../../../include/wfwindgen.h"
 #include "../series/wf_series.h"
 #include "wf_credit.h"
 
@@ -16,6 +17,7 @@ struct wf_credit : ext_base {
   // configuration
   int strict = 0, max_eval = 65536;
   int series_ahead = 0;   // wf_credit_set_series (include/wfseries.h): the rows' wind is the series' coming row
+  const wf_windgen* wind_source = nullptr;  // wf_credit_set_wind_source (include/wfwindgen.h): that series is a generator's, not the parent's
   // device buffers (grow-only)
   row_batch rows;         // E = C (1 + N K) farms, with loads
   dev_buf<double> d_window;  // [n_farms][2] that row of every listed farm
@@ -58,6 +60,12 @@ int wf_credit_set_series(wf_credit* c, int ahead) {
   return WF_OK;
 }
 
+int wf_credit_set_wind_source(wf_credit* c, wf_windgen* g) {
+  if (!c) return WF_E_INVALID;
+  c->wind_source = g;
+  return WF_OK;
+}
+
 int wf_credit_run(wf_credit* c, int base_kind, const float* base, int alt_kind, const float* alt, int K, int n_farms,
                   const int* farms, double* reward, double* farm_power, double* difference, int on_device) {
   if (!c) return WF_E_INVALID;
@@ -83,7 +91,7 @@ int wf_credit_run(wf_credit* c, int base_kind, const float* base, int alt_kind, 
     const bool needs_env = !base || base_kind == WF_CREDIT_ACTION || alt_kind == WF_CREDIT_ACTION;
     if (needs_env && !h->d_env_yaw) return ext_fail(c, WF_E_INVALID, kNoEnv);
     if (ahead) {
-      const int rc = series_ahead_check(c, false, 1);
+      const int rc = series_ahead_check(c, c->wind_source, false, 1);
       if (rc != WF_OK) return rc;
     }
     k.rows = 1 + N * K;
@@ -94,7 +102,7 @@ int wf_credit_run(wf_credit* c, int base_kind, const float* base, int alt_kind, 
     st.in(base, fn, &d_base); st.in(alt, fn * K, &d_alt);
     st.out(reward, fr, &d_rew); st.out(farm_power, fr, &d_fp); st.out(difference, fn * K, &d_dif);
     if (ahead)  // (the farm list is on the device by now: run_rows uploads it before this hook)
-      return series_ahead_window(c, c->d_window, 1, n_farms, farms ? b.farms.d.p : nullptr);
+      return series_ahead_window(c, c->wind_source, c->d_window, 1, n_farms, farms ? b.farms.d.p : nullptr);
     return WF_OK;
   };
   k.layout = [&](const WfSlots& sl, int E) -> int {

@@ -9,6 +9,7 @@
 
 #include "../../../include/wflookahead.h"
 #include "../ext/wf_ext.h"
+#include "../../../include/wfwindgen.h"
 #include "../series/wf_series.h"
 #include "wf_lookahead.h"
 
@@ -18,6 +19,7 @@ struct wf_lookahead : ext_base {
   // configuration
   int strict = 0, max_eval = 65536;
   int series_ahead = 0;   // wf_lookahead_set_series (include/wfseries.h): the rows' wind is the window of the series' coming rows
+  const wf_windgen* wind_source = nullptr;  // wf_lookahead_set_wind_source (include/wfwindgen.h): that series is a generator's, not the parent's
   // device buffers (grow-only)
   row_batch rows;         // E = C K H farms, with loads
   dev_buf<double> d_window;  // [n_farms][H][2] that window, laid out like a caller's wind
@@ -57,6 +59,12 @@ int wf_lookahead_set_series(wf_lookahead* l, int ahead) {
   return WF_OK;
 }
 
+int wf_lookahead_set_wind_source(wf_lookahead* l, wf_windgen* g) {
+  if (!l) return WF_E_INVALID;
+  l->wind_source = g;
+  return WF_OK;
+}
+
 int wf_lookahead_run(wf_lookahead* l, const float* actions, int K, int H, const double* wind, double gamma, int n_farms,
                      const int* farms, double* returns, double* rewards, double* farm_power, float* final_yaw, int* best,
                      int on_device) {
@@ -86,7 +94,7 @@ int wf_lookahead_run(wf_lookahead* l, const float* actions, int K, int H, const 
     if (!actions) return ext_fail(l, WF_E_INVALID, "wf_lookahead_run: actions is NULL");
     if (!h->d_env_yaw || !h->d_env_acc || !h->d_env_moves) return ext_fail(l, WF_E_INVALID, kNoEnv);
     if (ahead) {
-      const int rc = series_ahead_check(l, wind != nullptr, H);
+      const int rc = series_ahead_check(l, l->wind_source, wind != nullptr, H);
       if (rc != WF_OK) return rc;
     }
     k.rows = K * H;
@@ -96,7 +104,7 @@ int wf_lookahead_run(wf_lookahead* l, const float* actions, int K, int H, const 
     const size_t fk = (size_t)n_farms * K, fr = fk * H;
     st.in(actions, fr * N, &d_act); st.in(wind, (size_t)n_farms * H * 2, &d_wind);
     if (ahead) {  // (the farm list is on the device by now: run_rows uploads it before this hook)
-      const int rc = series_ahead_window(l, l->d_window, H, n_farms, farms ? b.farms.d.p : nullptr);
+      const int rc = series_ahead_window(l, l->wind_source, l->d_window, H, n_farms, farms ? b.farms.d.p : nullptr);
       if (rc != WF_OK) return rc;
       d_wind = l->d_window;
     }

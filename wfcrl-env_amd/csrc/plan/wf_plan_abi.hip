@@ -10,6 +10,7 @@
 
 #include "../../../include/wfplan.h"
 #include "../ext/wf_ext.h"
+#include "../../../include/wfwindgen.h"
 #include "../series/wf_series.h"
 #include "wf_plan.h"
 
@@ -19,6 +20,7 @@ struct wf_plan : ext_base {
   // configuration
   int strict = 0, max_eval = 65536;
   int series_ahead = 0;    // wf_plan_set_series (include/wfseries.h): the rows' wind is the window of the series' coming rows
+  const wf_windgen* wind_source = nullptr;  // wf_plan_set_wind_source (include/wfwindgen.h): that series is a generator's, not the parent's
   // device buffers (grow-only)
   row_batch rows;          // E = C K H farms, with loads
   dev_buf<double> d_window;  // [n_farms][H][2] that window, laid out like a caller's wind
@@ -65,6 +67,12 @@ int wf_plan_set_series(wf_plan* p, int ahead) {
   return WF_OK;
 }
 
+int wf_plan_set_wind_source(wf_plan* p, wf_windgen* g) {
+  if (!p) return WF_E_INVALID;
+  p->wind_source = g;
+  return WF_OK;
+}
+
 int wf_plan_run(wf_plan* p, int H, int K, int E, int I, const double* sigma, unsigned long long seed, double gamma,
                 const double* wind, const float* mean0, int n_farms, const int* farms, float* plan, double* plan_return,
                 double* hold_return, float* first_action, float* final_yaw, float* mean, int on_device) {
@@ -98,7 +106,7 @@ int wf_plan_run(wf_plan* p, int H, int K, int E, int I, const double* sigma, uns
     if (h->env.discrete)
       return ext_fail(p, WF_E_UNSUPPORTED, "planning serves the continuous action encoding: this handle is configured discrete (wf_env_config)");
     if (ahead) {
-      const int rc = series_ahead_check(p, wind != nullptr, H);
+      const int rc = series_ahead_check(p, p->wind_source, wind != nullptr, H);
       if (rc != WF_OK) return rc;
     }
     sg.assign(sigma, sigma + I);
@@ -114,7 +122,7 @@ int wf_plan_run(wf_plan* p, int H, int K, int E, int I, const double* sigma, uns
     const size_t fh = (size_t)n_farms * H;
     st.in(wind, fh * 2, &d_wind); st.in(mean0, fh * N, &d_mean0);
     if (ahead) {  // (the farm list is on the device by now: run_rows uploads it before this hook)
-      rc = series_ahead_window(p, p->d_window, H, n_farms, farms ? b.farms.d.p : nullptr);
+      rc = series_ahead_window(p, p->wind_source, p->d_window, H, n_farms, farms ? b.farms.d.p : nullptr);
       if (rc != WF_OK) return rc;
       d_wind = p->d_window;
     }

@@ -27,6 +27,7 @@
 
 #include <climits>
 
+#include "../ext/wf_deviate.h"
 #include "../wf_philox.h"
 #include "wf_plan.h"
 
@@ -150,8 +151,7 @@ __device__ __forceinline__ void wf_plan_layout(const WfPlanRun& a, const WfSlots
         if (k >= 2) {
           unsigned r[4];
           philox4x32_10(a.seed, hi | (unsigned)o, (unsigned)v, r);
-          const unsigned long long S = (unsigned long long)r[0] + r[1] + r[2] + r[3];
-          const double z = ((double)S * (1.0 / 4294967296.0) - 2.0) * 1.7320508075688772;
+          const double z = wf_deviate_of(r);
           double c = (double)act + sigma * z;
           c = c < -lim ? -lim : c;
           c = c > lim ? lim : c;

@@ -9,6 +9,7 @@
 
 #include "../../../include/wfretgrad.h"
 #include "../ext/wf_ext.h"
+#include "../../../include/wfwindgen.h"
 #include "../series/wf_series.h"
 #include "wf_retgrad.h"
 
@@ -18,6 +19,7 @@ struct wf_retgrad : ext_base {
   // configuration
   int strict = 0, max_eval = WF_RETGRAD_DEFAULT_EVAL_FARMS;
   int series_ahead = 0;   // wf_retgrad_set_series: the rows' wind is the window of the series' coming rows
+  const wf_windgen* wind_source = nullptr;  // wf_retgrad_set_wind_source (include/wfwindgen.h): that series is a generator's, not the parent's
   // device buffers (grow-only)
   row_batch rows;                   // E = C K H (2 N + 1) farms, with loads
   dev_buf<double> d_div;            // [C][K][H][N] the divisors
@@ -60,6 +62,12 @@ int wf_retgrad_set_series(wf_retgrad* r, int ahead) {
   return WF_OK;
 }
 
+int wf_retgrad_set_wind_source(wf_retgrad* r, wf_windgen* g) {
+  if (!r) return WF_E_INVALID;
+  r->wind_source = g;
+  return WF_OK;
+}
+
 int wf_retgrad_run(wf_retgrad* r, const float* actions, int K, int H, const double* wind, double gamma, double delta,
                    const double* terminal, int n_farms, const int* farms, double* returns, double* rewards, double* farm_power,
                    float* final_yaw, int* best, double* action_gradient, double* reward_gradient, double* state_gradient,
@@ -94,7 +102,7 @@ int wf_retgrad_run(wf_retgrad* r, const float* actions, int K, int H, const doub
     if (h->env.discrete) return ext_fail(r, WF_E_UNSUPPORTED, "return gradients serve the continuous action encoding only: the env is configured for the discrete encoding");
     if (N > WF_RETGRAD_MAX_N) return ext_fail(r, WF_E_UNSUPPORTED, "return gradients serve at most 1024 turbines");
     if (ahead) {
-      const int rc = series_ahead_check(r, wind != nullptr, H);
+      const int rc = series_ahead_check(r, r->wind_source, wind != nullptr, H);
       if (rc != WF_OK) return rc;
     }
     const long long rows = (long long)K * H * (2 * N + 1);
@@ -111,7 +119,7 @@ int wf_retgrad_run(wf_retgrad* r, const float* actions, int K, int H, const doub
     if (rc != WF_OK) return rc;
     st.in(actions, fr * N, &d_act); st.in(wind, (size_t)n_farms * H * 2, &d_wind); st.in(terminal, fk * N, &d_term);
     if (ahead) {  // (the farm list is on the device by now: run_rows uploads it before this hook)
-      rc = series_ahead_window(r, r->d_window, H, n_farms, farms ? b.farms.d.p : nullptr);
+      rc = series_ahead_window(r, r->wind_source, r->d_window, H, n_farms, farms ? b.farms.d.p : nullptr);
       if (rc != WF_OK) return rc;
       d_wind = r->d_window;
     }

@@ -10,6 +10,7 @@
 
 #include "../../../include/wfrollout.h"
 #include "../ext/wf_ext.h"
+#include "../../../include/wfwindgen.h"
 #include "../series/wf_series.h"
 #include "wf_rollout.h"
 
@@ -20,6 +21,7 @@ struct wf_rollout : ext_base {
   // configuration
   int strict = 0, max_eval = 65536;
   int series_ahead = 0;  // wf_rollout_set_series: the rows' wind is the window of the series' coming rows
+  const wf_windgen* wind_source = nullptr;  // wf_rollout_set_wind_source (include/wfwindgen.h): that series is a generator's, not the parent's
   // the controllers the device holds: [K] slot, lead (ints), alpha (doubles), deadband (floats), and the host copy the upload reads
   std::vector<int> c_int;
   std::vector<double> c_alpha;
@@ -75,6 +77,12 @@ int wf_rollout_set_series(wf_rollout* r, int ahead) {
   return WF_OK;
 }
 
+int wf_rollout_set_wind_source(wf_rollout* r, wf_windgen* g) {
+  if (!r) return WF_E_INVALID;
+  r->wind_source = g;
+  return WF_OK;
+}
+
 int wf_rollout_run(wf_rollout* r, int K, const int* slot, const double* alpha, const float* deadband, const int* lead, int H,
                    const double* wind, const double* filter0, double gamma, int n_farms, const int* farms, double* returns,
                    double* rewards, double* farm_power, float* actions, float* final_yaw, int* gated, double* filter_final,
@@ -114,7 +122,7 @@ int wf_rollout_run(wf_rollout* r, int K, const int* slot, const double* alpha, c
     if (!std::isfinite(gamma) || gamma < 0.0 || gamma > 1.0) return ext_fail(r, WF_E_INVALID, "gamma must be finite and in [0, 1]");
     if (!h->d_env_yaw || !h->d_env_acc || !h->d_env_moves) return ext_fail(r, WF_E_INVALID, kNoEnv);
     if (ahead) {
-      const int rc = series_ahead_check(r, wind != nullptr, H);
+      const int rc = series_ahead_check(r, r->wind_source, wind != nullptr, H);
       if (rc != WF_OK) return rc;
     }
     k.rows = K * H;
@@ -141,7 +149,7 @@ int wf_rollout_run(wf_rollout* r, int K, const int* slot, const double* alpha, c
     }
     st.in(wind, (size_t)n_farms * H * 2, &d_wind); st.in(filter0, fk * 2, &d_f0);
     if (ahead) {  // (the farm list is on the device by now: run_rows uploads it before this hook)
-      rc = series_ahead_window(r, r->d_window, H, n_farms, farms ? b.farms.d.p : nullptr);
+      rc = series_ahead_window(r, r->wind_source, r->d_window, H, n_farms, farms ? b.farms.d.p : nullptr);
       if (rc != WF_OK) return rc;
       d_wind = r->d_window;
     }

@@ -11,33 +11,59 @@ using namespace wfi;
 
 namespace wfi {
 
-int series_available(const wf_handle* h, int first, int H) {
-  const long long left = (long long)h->series_T - h->series_t - first;
+series_view handle_series(const wf_handle* h) {
+  series_view v;
+  v.T = h->series_T; v.t = h->series_t;
+  v.start = h->d_series_start; v.ws = h->d_series_ws; v.wd = h->d_series_wd;
+  v.row_stride = 1; v.farm_stride = 0;
+  return v;
+}
+
+int series_available(int T, int t, int first, int H) {
+  const long long left = (long long)T - t - first;
   return left <= 0 ? 0 : (left < H ? (int)left : H);
 }
 
-hipError_t series_window_enqueue(wf_handle* h, int first, int H, int n, const int* d_farms, double* d_wind) {
-  const long long t0 = (long long)h->series_t + first;
+hipError_t series_window_enqueue(const series_view& v, hipStream_t s, int first, int H, int n, const int* d_farms, double* d_wind) {
+  const long long t0 = (long long)v.t + first;
   WfSeriesWindowArgs a{};
-  a.farms = d_farms; a.n = n; a.H = H; a.T = h->series_T;
-  a.tick0 = (int)(t0 < (long long)h->series_T - 1 ? t0 : (long long)h->series_T - 1);
-  a.start = h->d_series_start; a.s_ws = h->d_series_ws; a.s_wd = h->d_series_wd;
+  a.farms = d_farms; a.n = n; a.H = H; a.T = v.T;
+  a.tick0 = (int)(t0 < (long long)v.T - 1 ? t0 : (long long)v.T - 1);
+  a.start = v.start; a.s_ws = v.ws; a.s_wd = v.wd;
+  a.row_stride = v.row_stride; a.farm_stride = v.farm_stride;
   a.wind = d_wind;
-  return wfk_launch_series_window(&a, h->stream);
+  return wfk_launch_series_window(&a, s);
 }
 
-int series_ahead_check(ext_base* x, bool caller_wind, int H) {
+// the series a series-ahead run reads: the source's, or the parent's own
+static int series_ahead_view(ext_base* x, const wf_windgen* source, series_view* v) {
   const wf_handle* h = x->h;
+  if (source) {
+    const char* why = "";
+    if (!windgen_series(source, h, v, &why)) return ext_fail(x, WF_E_INVALID, std::string("series-ahead mode: ") + why);
+    return WF_OK;
+  }
   if (h->series_T <= 0) return ext_fail(x, WF_E_INVALID, "series-ahead mode needs a parent in series mode: wf_wind_series comes first");
-  if (caller_wind) return ext_fail(x, WF_E_INVALID, "series-ahead mode reads the series' coming rows: pass no wind of your own, or switch the mode off");
-  if (series_available(h, 1, H) == 0) return ext_fail(x, WF_E_INVALID, "wind series exhausted: the coming step has no row left");
+  *v = handle_series(h);
   return WF_OK;
 }
 
-int series_ahead_window(ext_base* x, dev_buf<double>& buf, int H, int n, const int* d_farms) {
-  const int rc = reserve(x, buf, 2 * (size_t)n * H);
+int series_ahead_check(ext_base* x, const wf_windgen* source, bool caller_wind, int H) {
+  series_view v;
+  const int rc = series_ahead_view(x, source, &v);
   if (rc != WF_OK) return rc;
-  WFX_HIP(x, series_window_enqueue(x->h, 1, H, n, d_farms, buf));
+  if (caller_wind) return ext_fail(x, WF_E_INVALID, "series-ahead mode reads the series' coming rows: pass no wind of your own, or switch the mode off");
+  if (series_available(v.T, v.t, 1, H) == 0) return ext_fail(x, WF_E_INVALID, "wind series exhausted: the coming step has no row left");
+  return WF_OK;
+}
+
+int series_ahead_window(ext_base* x, const wf_windgen* source, dev_buf<double>& buf, int H, int n, const int* d_farms) {
+  series_view v;
+  int rc = series_ahead_view(x, source, &v);
+  if (rc != WF_OK) return rc;
+  rc = reserve(x, buf, 2 * (size_t)n * H);
+  if (rc != WF_OK) return rc;
+  WFX_HIP(x, series_window_enqueue(v, x->h->stream, 1, H, n, d_farms, buf));
   return WF_OK;
 }
 
@@ -77,10 +103,10 @@ int wf_series_window(wf_handle* h, int first, int H, int n_farms, const int* far
     WF_HIP(h, hipMemcpyAsync(d_farms.p, farms, sizeof(int) * (size_t)n_farms, hipMemcpyHostToDevice, h->stream));
   }
   if (!on_device) WF_HIP(h, hipMalloc(&d_wind.p, bytes));
-  WF_HIP(h, series_window_enqueue(h, first, H, n_farms, (const int*)d_farms.p, on_device ? wind : (double*)d_wind.p));
+  WF_HIP(h, series_window_enqueue(handle_series(h), h->stream, first, H, n_farms, (const int*)d_farms.p, on_device ? wind : (double*)d_wind.p));
   if (!on_device) WF_HIP(h, hipMemcpyAsync(wind, d_wind.p, bytes, hipMemcpyDeviceToHost, h->stream));
   if (!on_device || farms) WF_HIP(h, hipStreamSynchronize(h->stream));  // (before the call's own buffers go)
-  if (available) *available = series_available(h, first, H);
+  if (available) *available = series_available(h->series_T, h->series_t, first, H);
   return WF_OK;
 }
 

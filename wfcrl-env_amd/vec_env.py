@@ -32,7 +32,7 @@ class VecWindFarmEnv:
                  device_id: int = 0, model: dict = None, return_torch: bool = True, backend=None,
                  wind_sampling: str = "host", reuse_buffers: bool = True, wind_direction_step: float = None,
                  actuation_budget: float = 0.1, kernel_choice: dict = None, risk_resolve: bool = None,
-                 layouts: dict = None):
+                 layouts: dict = None, wind_process: dict = None):
         controls = {"yaw": (-40, 40, 5)} if controls is None else dict(controls)
         if list(controls) != ["yaw"]:
             raise ValueError(f"Cannot control {list(controls)}. Interface HipFlorisInterface only allows for the "
@@ -107,6 +107,24 @@ class VecWindFarmEnv:
             self._series = np.ascontiguousarray(_load_time_series(ts)[:, :2], dtype=np.float64)
         else:
             self._series = None
+        # wind_process: a synthetic wind episode — a stochastic wind series per farm, generated on the device at every reset
+        # (include/wfwindgen.h; backend.WfStep.generate_wind): dict(ws_revert=, ws_sigma=, wd_revert=, wd_sigma=, wd_ramp=,
+        # dist=None), missing parameters 0.  Every farm then sees a changing wind of its own, reproducible from the reset's
+        # seed, and everything the env does on a time-series episode applies: the tick before the step, wind_preview,
+        # wind="series".  None (the default): the wind holds from reset to truncation, as in the reference.
+        self._wind_process = self._wind_dist = None
+        if wind_process is not None:
+            if has_series:
+                raise ValueError("wind_process generates the episode's wind: it cannot be combined with a case's wind_time_series")
+            wp = dict(wind_process)
+            self._wind_dist = wp.pop("dist", None)
+            unknown = set(wp) - {"ws_revert", "ws_sigma", "wd_revert", "wd_sigma", "wd_ramp"}
+            if unknown:
+                raise ValueError(f"unknown wind_process parameter(s): {sorted(unknown)}")
+            self._wind_process = {k: float(v) for k, v in wp.items()}
+        self._generated = None  # what regenerates the running episode: seed, T, ws0, wd0 (get_state)
+        # an episode whose wind changes from step to step: a file series or a generated one
+        self._playing = self._series is not None or self._wind_process is not None
         self._num_iter = 0
         self._freewind = None
         self._shaper_ref = None
@@ -209,6 +227,15 @@ class VecWindFarmEnv:
             # random row (interface.py:516-518), then each solve consumes one row
             s = seed if seed is not None else int(np.random.randint(0, 2**31 - 1))
             self.fi.set_wind_series(self._series, start=None, seed=s)
+        elif self._wind_process is not None:
+            # a generated episode: reset consumes start_iter + 1 ticks and every step one more, so the last step of the
+            # episode plays the last tick; options give tick 0 instead of the draw
+            s = seed if seed is not None else int(np.random.randint(0, 2**31 - 1))
+            ws0 = wd0 = None
+            if options and ("wind_speed" in options or "wind_direction" in options):
+                ws0, wd0 = self._sample_wind(seed, options)
+            self._generated = {"seed": int(s), "T": int(self.start_iter + self.max_num_steps + 2), "ws0": ws0, "wd0": wd0}
+            self.fi.generate_wind(self._generated["T"], s, self._wind_process, dist=self._wind_dist, ws0=ws0, wd0=wd0)
         elif self.wind_sampling == "device" and not (options and ("wind_speed" in options or "wind_direction" in options)) \
                 and not (self.farm_case.set_wind_speed or self.farm_case.set_wind_direction):
             s = seed if seed is not None else int(np.random.randint(0, 2**31 - 1))
@@ -230,7 +257,7 @@ class VecWindFarmEnv:
         self._num_iter = 0
         out = None
         for _ in range(self.start_iter + 1):
-            if self._series is not None:
+            if self._playing:
                 self.fi.wind_series_step()
             out = self.fi.env_step(None, want=("yaw", "wind_speed", "wind_direction"), out=seed_out)
             self._num_iter += 1
@@ -249,10 +276,10 @@ class VecWindFarmEnv:
 
             clipped = torch.minimum(torch.maximum(fw, torch.as_tensor(lo, dtype=fw.dtype, device=fw.device)),
                                     torch.as_tensor(hi, dtype=fw.dtype, device=fw.device))
-            changed = bool((clipped[:, 0] != fw[:, 0]).any()) if self._series is None else False
+            changed = bool((clipped[:, 0] != fw[:, 0]).any()) if not self._playing else False
         else:
             clipped = np.clip(fw, lo, hi)
-            changed = bool((clipped[:, 0] != fw[:, 0]).any()) if self._series is None else False
+            changed = bool((clipped[:, 0] != fw[:, 0]).any()) if not self._playing else False
         obs["freewind_measurements"] = clipped
         if changed:
             self.fi.env_set_prev_wind(clipped[:, 0].cpu().numpy() if self.return_torch else clipped[:, 0])
@@ -262,7 +289,7 @@ class VecWindFarmEnv:
         """actions: {"yaw": (B, N)} or the (B, N) array itself.  Returns (obs, reward[B], terminated[B],
         truncated[B], info) with info["power"] in MW and info["load"] (B, N, 4) — units of the reference."""
         a = actions["yaw"] if isinstance(actions, dict) else actions
-        if self._series is not None:
+        if self._playing:
             self.fi.wind_series_step()  # ValueError("wind series exhausted") ~ the reference's StopIteration
             self._refresh_freewind()
         buf = self._next_buf()
@@ -291,7 +318,7 @@ class VecWindFarmEnv:
         """Learner-facing variant: only reward + local wind observations leave the kernel (no power/load
         arrays are written: 2N+1 instead of 7N floats per env)."""
         a = actions["yaw"] if isinstance(actions, dict) else actions
-        if self._series is not None:
+        if self._playing:
             self.fi.wind_series_step()
             self._refresh_freewind()
         buf = self._next_buf()
@@ -493,9 +520,9 @@ class VecWindFarmEnv:
         wind="series" reads the series' coming rows on the device (include/wfseries.h), or the caller passes them as
         wind=(n_farms, horizon, 2)."""
         series = isinstance(wind, str) and wind == "series"
-        if series and self._series is None:
+        if series and not self._playing:
             raise ValueError('wind="series" needs a time-series episode: this env has no wind_time_series')
-        if self._series is not None and wind is None:
+        if self._playing and wind is None:
             raise NotImplementedError("plan_actions on a time-series episode needs wind=(n_farms, horizon, 2): the series tick "
                                       "precedes the step, so the wind of the coming steps is not the one the env holds "
                                       '(or wind="series": the series\' coming rows, read on the device)')
@@ -533,9 +560,9 @@ class VecWindFarmEnv:
         wind="series" reads the series' coming rows on the device (include/wfseries.h), or the caller passes them as
         wind=(n_farms, horizon, 2)."""
         series = isinstance(wind, str) and wind == "series"
-        if series and self._series is None:
+        if series and not self._playing:
             raise ValueError('wind="series" needs a time-series episode: this env has no wind_time_series')
-        if self._series is not None and wind is None:
+        if self._playing and wind is None:
             raise NotImplementedError("controller_returns on a time-series episode needs wind=(n_farms, horizon, 2): the series "
                                       "tick precedes the step, so the wind of the coming steps is not the one the env holds "
                                       '(or wind="series": the series\' coming rows, read on the device)')
@@ -566,11 +593,11 @@ class VecWindFarmEnv:
         "series", any other episode None."""
         if wind is not None and not (isinstance(wind, str) and wind == "series"):
             raise ValueError(f'{name}: wind must be None or "series"')
-        if self._series is not None and wind is None:
+        if self._playing and wind is None:
             raise NotImplementedError(f"{name} is not supported on a time-series episode: the series tick precedes the step, so "
                                       f"the wind of the coming {steps} is not the one the env holds (pass wind=\"series\": the "
                                       "series' coming rows, read on the device)")
-        if self._series is None and wind is not None:
+        if not self._playing and wind is not None:
             raise ValueError(f'{name}: wind="series" needs a time-series episode: this env has no wind_time_series')
 
     def wind_preview(self, H: int):
@@ -579,7 +606,7 @@ class VecWindFarmEnv:
         the first `available` entries are real, the rest hold the series' last wind (the step that would follow it fails
         with "exhausted").  A torch CUDA tensor when the env returns torch: one kernel launch, nothing read back
         (include/wfseries.h; backend.WfStep.wind_preview).  What a feed-forward or preview controller observes."""
-        if self._series is None:
+        if not self._playing:
             raise ValueError("wind_preview needs a time-series episode: this env has no wind_time_series")
         return self.fi.wind_preview(H, first=1, as_torch=self.return_torch)
 
@@ -606,13 +633,29 @@ class VecWindFarmEnv:
         if self._series is not None:  # a time-series episode: one cursor per farm (include/wfseries.h)
             cur = self.fi.series_state()
             st.update(series_t=cur["t"], series_start=cur["start"], series_prev_pending=cur["prev_pending"])
+        if self._wind_process is not None:  # a generated episode: what generates the same series again, and the cursor
+            if self._generated is None:
+                raise ValueError("get_state: the env has not been reset")
+            cur = self.fi.series_state()
+            st["generated_wind"] = {**self._generated, "process": dict(self._wind_process),
+                                    "dist": None if self._wind_dist is None else dict(self._wind_dist),
+                                    "t": cur["t"], "prev_pending": cur["prev_pending"]}
         return st
 
     def set_state(self, state: dict):
         if ("series_t" in state) != (self._series is not None):
             raise ValueError("the state of a time-series episode resumes on an env with that wind_time_series, and only there: "
                              + ("this env has none" if self._series is None else "this state holds no series cursor"))
-        if self._series is not None:
+        if ("generated_wind" in state) != (self._wind_process is not None):
+            raise ValueError("the state of a generated wind episode resumes on an env with a wind_process, and only there: "
+                             + ("this env has none" if self._wind_process is None else "this state holds no generated wind"))
+        if self._wind_process is not None:
+            # the same seed, distribution, process and tick 0 give the same bits; then the cursor
+            g = state["generated_wind"]
+            self._generated = {k: g[k] for k in ("seed", "T", "ws0", "wd0")}
+            self.fi.generate_wind(g["T"], g["seed"], g["process"], dist=g["dist"], ws0=g["ws0"], wd0=g["wd0"])
+            self.fi.series_seek(g["t"], g["prev_pending"])
+        elif self._series is not None:
             # the env's own series with the state's start rows, then the cursor: the wind is the series' row again
             self.fi.set_wind_series(self._series, start=state["series_start"])
             self.fi.series_seek(state["series_t"], state["series_prev_pending"])
