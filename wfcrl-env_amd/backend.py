@@ -748,6 +748,56 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the lookahead kernels as the runtime reports them."""
         return self._lookahead().kernel_info()
 
+    # -- scenario look-ahead: returns of action sequences over a wind ensemble (include/wfscenario.h) ------
+    def _scenario(self) -> "_Scenario":
+        """The handle's scenario object; created on first use, destroyed in close() before the handle."""
+        so = getattr(self, "_scenario_obj", None)
+        if so is None:
+            so = self._scenario_obj = _Scenario(self)
+        return so
+
+    def scenario_returns(self, actions, members, process, seed=0, gamma=1.0, tail=None, risk_weight=0.0, anchor=None,
+                         bounds=(3.0, 28.0), farms=None, strict=False, max_eval_farms=65536,
+                         want=("expected_returns", "cvar", "score", "best"), out=None):
+        """The returns of K candidate action sequences over an ensemble of `members` wind futures drawn on the device from a
+        wind process, from the wind and the env state the handle holds, which are read and never changed
+        (include/wfscenario.h; the project's own definition, PARITY UNPINNED beyond the oracle).  Every farm draws M paths
+        of H ticks that start at its current wind and revert to the anchor (Philox streams 16 to 18, keyed by the farm's index
+        in the batch: the K sequences share the paths — common random numbers); step h of every sequence is solved under
+        every member's wind of tick h + 1, the K M H rows of a farm in one batched step; a member's return is
+        lookahead_returns' discounted sum, step 0 normalised by the current speed, step h by the member's speed of step
+        h - 1; then per sequence the mean over the members, the tail mean (CVaR) of the `tail` lowest member returns and
+        score = (1 - risk_weight) mean + risk_weight cvar, in float64 in fixed orders.
+          actions    (n_farms, K, H, N) float32 in the env's encoding (block i belongs to farms[i]) — torch CUDA tensor or
+                     NumPy; 1 <= H <= 64, K M H <= 4096
+          members    M in 1..64
+          process    dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp) as generate_wind's (missing: 0)
+          seed       64-bit seed of the draws
+          gamma      discount in [0, 1]
+          tail       q in 1..M (None: M, the tail mean is the mean in another summation order)
+          risk_weight  lam in [0, 1]
+          anchor     (n_farms, 2) float64 (speed > 0, direction) the paths revert to; None: every farm's current wind
+          bounds     (ws_lo, ws_hi) the stored speeds are clipped to, 0 < ws_lo < ws_hi
+          farms, strict, max_eval_farms   as lookahead_returns'; a farm takes K M H rows
+          want       of "expected_returns", "cvar", "score" (n, K) float64, "member_returns" (n, K, M) float64, "rewards"
+                     (n, K, M, H) float64, "wind_paths" (n, M, H, 2) float64 — (speed, direction) of tick h + 1 —,
+                     "final_yaw" (n, K, N) float32, "best" (n,) int32 — the sequence of the largest score, the lowest index
+                     among equal maxima
+          out        dict of tensors / arrays of those names to write into
+        Works under any wind the handle holds — set, sampled, a file series or a generated episode: only the current wind
+        is read.  Deterministic: fixed summation orders, no atomics; any chunking and any farm list give the same bits in
+        strict mode.  With torch tensors the call only enqueues work on torch's current stream."""
+        return self._scenario().run(actions, members, process, seed, gamma, tail, risk_weight, anchor, bounds, farms, strict,
+                                    max_eval_farms, want, out)
+
+    def scenario_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last scenario_returns {"total_ms", "step_ms", "glue_ms"}."""
+        return self._scenario().timing(detail)
+
+    def scenario_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the scenario kernels as the runtime reports them."""
+        return self._scenario().kernel_info()
+
     # -- the gradient of look-ahead returns w.r.t. the action sequences (include/wfretgrad.h) ------------
     def _retgrad(self) -> "_RetGrad":
         """The handle's retgrad object; created on first use, destroyed in close() before the handle."""
@@ -1204,7 +1254,7 @@ class WfStep:
             # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h,
             # wfcredit.h, wflookahead.h, wfplan.h, wfretgrad.h, wfrollout.h — the rollout object, created on the rose object, before it)
             for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rollout_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
-                         "_lookahead_obj", "_plan_obj", "_retgrad_obj", "_windgen_obj"):
+                         "_lookahead_obj", "_scenario_obj", "_plan_obj", "_retgrad_obj", "_windgen_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
                     ext.close()
@@ -1719,6 +1769,70 @@ class _Lookahead(_Ext):
         p = dict(zip(spec, ptrs))
         self._call("run", actions.data_ptr() if on_device else actions.ctypes.data, K, H, wptr, float(gamma), n, fptr,
                    *[p.get(k) for k in self.OUTPUTS], int(on_device))
+        return {k: out[k] for k in spec}
+
+
+class _Scenario(_Ext):
+    """The `wf_scenario` object of a WfStep handle (include/wfscenario.h)."""
+
+    NAME = "scenario"
+    KERNELS = ("layout", "reduce")
+    OUTPUTS = ("expected_returns", "cvar", "score", "member_returns", "rewards", "wind_paths", "final_yaw", "best")
+    PROCESS = ("ws_revert", "ws_sigma", "wd_revert", "wd_sigma", "wd_ramp")
+
+    def run(self, actions, members, process, seed, gamma, tail, risk_weight, anchor, bounds, farms, strict, max_eval_farms, want, out):
+        w = self._w
+        N = w.num_turbines
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.OUTPUTS for k in want):
+            raise ValueError("want must name expected_returns, cvar, score, member_returns, rewards, wind_paths, final_yaw and / or best")
+        if process is None:
+            raise ValueError("scenario_returns needs a wind process: dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp)")
+        unknown = set(process) - set(self.PROCESS)
+        if unknown:
+            raise ValueError(f"unknown wind process parameter(s): {sorted(unknown)}")
+        p = WindProcess(**{k: float(process.get(k, 0.0)) for k in self.PROCESS})
+        M = int(members)
+        q = M if tail is None else int(tail)
+        ws_lo, ws_hi = (float(v) for v in bounds)
+        self._call("config", int(bool(strict)), int(max_eval_farms or 0))
+        fa, n, fptr = self._farms(farms)
+        on_device = _is_torch(actions)
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            assert actions.is_cuda and actions.dtype == torch.float32, "actions"
+            actions = actions.contiguous()
+        else:
+            actions = np.ascontiguousarray(actions, dtype=np.float32)
+        shape = tuple(actions.shape)
+        if len(shape) != 4 or shape[0] != n or shape[3] != N:
+            raise ValueError("actions must be (n_farms, K, H, num_turbines): K sequences of H joint actions per listed farm")
+        K, H = int(shape[1]), int(shape[2])
+        aptr = None
+        if anchor is not None:
+            if on_device:
+                if not _is_torch(anchor):
+                    anchor = torch.as_tensor(np.array(anchor, np.float64), device=actions.device)
+                assert anchor.is_cuda and anchor.dtype == torch.float64, "anchor"
+                anchor = anchor.contiguous()
+            else:
+                anchor = np.ascontiguousarray(anchor, dtype=np.float64)
+            if tuple(anchor.shape) != (n, 2):
+                raise ValueError("anchor must be (n_farms, 2): the (speed, direction) every listed farm's paths revert to")
+            aptr = anchor.data_ptr() if on_device else anchor.ctypes.data
+        shapes = {"expected_returns": ((n, K), np.float64), "cvar": ((n, K), np.float64), "score": ((n, K), np.float64),
+                  "member_returns": ((n, K, M), np.float64), "rewards": ((n, K, M, H), np.float64),
+                  "wind_paths": ((n, M, H, 2), np.float64), "final_yaw": ((n, K, N), np.float32), "best": ((n,), np.int32)}
+        spec = {k: shapes[k] for k in self.OUTPUTS if k in want}
+        if out is None and not (1 <= M <= 64 and 1 <= H <= 64 and K * M * H <= 4096):
+            spec = {k: ((0,), d) for k, (_, d) in spec.items()}  # (the library refuses these limits by name: nothing to allocate)
+        out, ptrs = self._outputs(out, spec, on_device, actions)
+        ptr = dict(zip(spec, ptrs))
+        self._call("run", actions.data_ptr() if on_device else actions.ctypes.data, K, H, M, C.byref(p), ws_lo, ws_hi,
+                   C.c_ulonglong(int(seed) & (2**64 - 1)), float(gamma), q, float(risk_weight), aptr, n, fptr,
+                   *[ptr.get(k) for k in self.OUTPUTS], int(on_device))
         return {k: out[k] for k in spec}
 
 

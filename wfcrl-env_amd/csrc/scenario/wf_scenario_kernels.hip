@@ -1,0 +1,270 @@
+// wf_scenario_kernels.hip — the kernels around the step kernel that make scenario look-ahead run on the device
+// (include/wfscenario.h).  The farm solve is the existing wf_step on the object's evaluator handle; these two kernels are the
+// glue, so that a whole run — the ensemble's draws included — is enqueued without a host read:
+//
+//   wf_scenario_layout_kernel  once per chunk, ONE WORKGROUP PER SLOT.  The M member paths of the slot's farm go by in TILES
+//                              of Ht ticks (all H of them where M H <= 2048), two [M][Hs] arrays of doubles in LDS, Hs = Ht | 1:
+//                              (1) every thread draws the deviates of its (member, tick) pairs, streams 17 and 18, into the
+//                              tile — the draws are not serial, the recursion is —; (2) thread m < M, which keeps member m's
+//                              latents and ramp rate in registers across the tiles, walks the tile's ticks and leaves the
+//                              stored speed and direction in place; (3) after the barrier the threads fill every row's
+//                              evaluator wind, thread r on row r — consecutive lanes read consecutive doubles of a member's
+//                              LDS row and write consecutive doubles —, and wind_paths, consecutive lanes on consecutive
+//                              (speed, direction) pairs.  Then thread (k, t), t fastest, keeps the yaw and the accumulator
+//                              of turbine t in registers and walks sequence k's steps with the env's transition
+//                              (wf_env_transition, ext/wf_ext_kernels.h), as wf_lookahead_layout_kernel does, and stores
+//                              each yaw to the M member rows of that step: consecutive lanes write consecutive floats.
+//   wf_scenario_reduce_kernel  once per chunk, after the step, ONE WORKGROUP PER SLOT.  The slot's R = K M H rows go by in the
+//                              shared reward tile (wf_staged_row_rewards); the thread of a tile's row leaves the row's
+//                              reward in LDS ([K M][Hs] doubles) and writes rewards.  Thread (k, m) forms its discounted
+//                              return in ascending h, as wf_sequence_returns does, and leaves it in its row's first entry.
+//                              The statistics run in PASSES of nth / M whole sequences: thread (k, m) counts its rank over the
+//                              M members of its sequence in LDS — (return, m) ascending, a count — and scatters its return
+//                              to sorted[k][rank] (a pass's [nth] doubles); thread k adds the mean in ascending m and the
+//                              tail in ascending rank, forms the score and keeps its argmax, ascending k.  A fixed-order
+//                              tree over the threads follows: the larger score and among equal ones the lower index.
+//
+// The row normalisers: step 0's is the farm's CURRENT speed (a pending prev-wind speed is not read), step h >= 1's the speed
+// of row (k, m, h - 1), read from the evaluator's wind block.  LDS per block stays below 64 KiB: the lay-out's tile is at most
+// 2 x (2048 + 64) doubles (33 KiB); the reduce kernel's is laid out as wf_lookahead_reduce_kernel's with K M sequences (36 KiB
+// of rewards at most, 3 KiB — 12 KiB with 1024 threads — for the passes and the argmax) and its tile takes the rest of 63 KiB,
+// 24 KiB at the least.  Trip counts are run-time values: no private segment,
+// no spill (tests/test_scenario.py reads the metadata); every barrier sits in block-uniform control flow.  The library is
+// built with -ffp-contract=off: every product and sum of the paths and the statistics is one rounding, in the header's order.
+#include <hip/hip_runtime.h>
+
+#include "../ext/wf_deviate.h"
+#include "../wf_philox.h"
+#include "wf_scenario.h"
+
+#define WF_SCENARIO_TILE 2048  // (member, tick) pairs of a lay-out tile
+#define WF_SCENARIO_WIDE 8192  // floats of power per slot (R N) from which the reduce kernel runs 1024 threads
+#define WF_SCENARIO_IN_VGPR(v) asm volatile("" : "+v"(v))  // the value is held in a vector register from here on
+
+__global__ __launch_bounds__(256) void wf_scenario_layout_kernel(const WfScenarioLayoutArgs a, int Ht, int Hs) {
+  extern __shared__ double sc_tile[];
+  const int tid = threadIdx.x, nth = blockDim.x;
+  const int N = a.N, K = a.K, M = a.M, H = a.H, MH = M * H, R = K * MH;
+  double* sp = sc_tile;     // [M][Hs] deviates of stream 17, then the stored speeds
+  double* dr = sp + M * Hs; // [M][Hs] ... of stream 18, then the stored directions
+  const int slot = blockIdx.x;
+  const int b = wf_slot_farm(a.sl, slot);
+  const bool writes = slot < a.sl.n_slots;
+  const size_t in = writes ? slot : 0;  // the slot's input block
+  double Sc = a.ws[(size_t)b * a.wind_stride], Dc = a.wd[(size_t)b * a.wind_stride];
+  WF_SCENARIO_IN_VGPR(Sc); WF_SCENARIO_IN_VGPR(Dc);
+  double Sa = a.anchor ? a.anchor[in * 2] : Sc, Da = a.anchor ? a.anchor[in * 2 + 1] : Dc;
+  // the walk's parameters live in vector registers: block-uniform values held in scalar ones across the Philox rounds of the
+  // draws would not fit (spilled scalar registers; tests/test_scenario.py reads the metadata)
+  double ws_revert = a.ws_revert, ws_sigma = a.ws_sigma, wd_revert = a.wd_revert, wd_sigma = a.wd_sigma;
+  double ws_lo = a.ws_lo, ws_hi = a.ws_hi;
+  WF_SCENARIO_IN_VGPR(Sa); WF_SCENARIO_IN_VGPR(Da);
+  WF_SCENARIO_IN_VGPR(ws_revert); WF_SCENARIO_IN_VGPR(ws_sigma); WF_SCENARIO_IN_VGPR(wd_revert); WF_SCENARIO_IN_VGPR(wd_sigma);
+  WF_SCENARIO_IN_VGPR(ws_lo); WF_SCENARIO_IN_VGPR(ws_hi);
+  const unsigned long long hi = (unsigned long long)b << 32;
+  // the walkers: thread m keeps member m's state
+  const bool walker = tid < M;
+  double x = Sc, y = Dc, rate = 0.0;
+  if (walker) {
+    unsigned r[4];
+    philox4x32_10(a.seed, hi | (unsigned)tid, 16u, r);
+    rate = a.wd_ramp * (2.0 * u01(r[0], r[1]) - 1.0);
+  }
+  double* __restrict__ ews = a.ews + (size_t)slot * R;
+  double* __restrict__ ewd = a.ewd + (size_t)slot * R;
+  double* __restrict__ paths = (writes && a.wind_paths) ? a.wind_paths + in * MH * 2 : nullptr;
+  for (int h0 = 0; h0 < H; h0 += Ht) {  // (block-uniform)
+    const int nt = H - h0 < Ht ? H - h0 : Ht;
+    const int n = M * nt;
+    for (int i = tid; i < n; i += nth) {
+      const int m = i / nt, j = i - m * nt;
+      const unsigned long long ctr = hi | (unsigned)(m * 64 + h0 + j);
+      sp[m * Hs + j] = wf_deviate(a.seed, ctr, 17u);
+      dr[m * Hs + j] = wf_deviate(a.seed, ctr, 18u);
+    }
+    __syncthreads();
+    if (walker) {
+      double* s = sp + tid * Hs;
+      double* d = dr + tid * Hs;
+      for (int j = 0; j < nt; ++j) {
+        x = (x + ws_revert * (Sa - x)) + ws_sigma * s[j];
+        const double mu = Da + rate * (double)(h0 + j + 1);
+        y = (y + wd_revert * (mu - y)) + wd_sigma * d[j];
+        double w = fmod(y, 360.0);
+        if (w < 0.0) w += 360.0;
+        s[j] = fmin(fmax(x, ws_lo), ws_hi);
+        d[j] = w;
+      }
+    }
+    __syncthreads();
+    for (int r = tid; r < R; r += nth) {
+      const int km = r / H, h = r - km * H, j = h - h0;
+      if (j >= 0 && j < nt) {
+        const int m = km % M;
+        ews[r] = sp[m * Hs + j];
+        ewd[r] = dr[m * Hs + j];
+      }
+    }
+    if (paths) {
+      for (int i = tid; i < n; i += nth) {
+        const int m = i / nt, j = i - m * nt;
+        const size_t e = ((size_t)m * H + h0 + j) * 2;
+        paths[e] = sp[m * Hs + j];
+        paths[e + 1] = dr[m * Hs + j];
+      }
+    }
+    __syncthreads();  // (the next tile's draws overwrite sp / dr)
+  }
+  // the trajectories: what addresses them is formed HERE, from the slot and the farm in vector registers — formed at the top
+  // and held in scalar registers across the draws it would not fit (spilled scalar registers)
+  int slot_v = slot, b_v = b;
+  WF_SCENARIO_IN_VGPR(slot_v); WF_SCENARIO_IN_VGPR(b_v);
+  const bool writes_v = slot_v < a.sl.n_slots;
+  const size_t in_v = writes_v ? slot_v : 0, st0 = (size_t)b_v * N;
+  const int moves0 = a.env.moves[b_v];
+  const float* __restrict__ act = a.actions + in_v * K * H * N;
+  float* __restrict__ out = a.yaw + (size_t)slot_v * R * N;
+  const int n_traj = K * N;
+  const size_t member = (size_t)H * N;  // floats from a member's row of step h to the next member's
+  for (int q = tid; q < n_traj; q += nth) {
+    const int k = q / N, t = q - k * N;
+    float yw = a.env.yaw[st0 + t], acc = a.env.acc[st0 + t];
+    size_t i = (size_t)k * H * N + t;   // the action of step h
+    size_t o = (size_t)k * MH * N + t;  // row (k, 0, h)
+    for (int h = 0; h < H; ++h, i += N, o += N) {
+      float da;
+      yw = wf_env_transition(a.env, yw, act[i], acc, moves0 + 1 + h, da);
+      acc += fabsf(da);
+      size_t om = o;
+      for (int m = 0; m < M; ++m, om += member) out[om] = yw;
+    }
+    if (writes_v && a.final_yaw) a.final_yaw[in_v * n_traj + q] = yw;
+  }
+}
+
+// `red` is the block's dynamic LDS: [K M][Hs] + [nth] doubles (bv), [nth] ints (bi), then the tile's [T][sp] + [T][sl] floats
+__global__ __launch_bounds__(1024) void wf_scenario_reduce_kernel(const WfScenarioReduceArgs a, int T, int sp, int sl, int Hs) {
+  extern __shared__ double sc_red[];
+  const int tid = threadIdx.x, nth = blockDim.x;
+  const int N = a.N, K = a.K, M = a.M, H = a.H, KM = K * M, R = KM * H;
+  double* rw = sc_red;                              // [K M][Hs] row rewards; entry 0 of a row becomes the member return
+  float* pw = reinterpret_cast<float*>(reinterpret_cast<int*>(rw + KM * Hs + nth) + nth);  // [T][sp] a tile's powers
+  float* ld = pw + T * sp;                                                                  // [T][sl] ... and load values
+  const int slot = blockIdx.x;
+  const int b = wf_slot_farm(a.sl, slot);
+  double wr0 = a.ws[(size_t)b * a.wind_stride];
+  WF_SCENARIO_IN_VGPR(wr0);  // (as the lay-out's parameters: no spilled scalar register)
+  const double* __restrict__ ews = a.ews + (size_t)slot * R;
+  const float* __restrict__ pblk = a.power_ev + (size_t)slot * R * N;
+  const float* __restrict__ lblk = a.load_ev + (size_t)slot * R * 4 * N;
+  double* const rewards = a.rewards ? a.rewards + (size_t)slot * R : nullptr;
+  wf_staged_row_rewards(
+      pblk, lblk, R, N, T, sp, sl, a.load_coef, pw, ld,
+      [H, wr0, ews](int row) { return row % H == 0 ? wr0 : ews[row - 1]; },  // the speed BEFORE the step, of the row's member
+      [H, Hs, rw, rewards](int row, double r, double) {
+        const int km = row / H, h = row - km * H;
+        rw[km * Hs + h] = r;
+        if (rewards) rewards[row] = r;
+      });
+  int after = KM * Hs;  // (formed again, in a vector register, and not held in scalar ones across the tiles)
+  WF_SCENARIO_IN_VGPR(after);
+  double* bv = rw + after;                     // [nth] a pass's sorted returns, then the argmax tree: scores ...
+  int* bi = reinterpret_cast<int*>(bv + nth);  // [nth] ... and their sequences
+  double gamma = a.gamma;
+  WF_SCENARIO_IN_VGPR(gamma);
+  for (int km = tid; km < KM; km += nth) {
+    double* r = rw + km * Hs;
+    double g = 1.0, ret = 0.0;
+    for (int h = 0; h < H; ++h) {
+      ret += g * r[h];
+      g = g * gamma;
+    }
+    r[0] = ret;
+    if (a.member_returns) a.member_returns[(size_t)slot * KM + km] = ret;
+  }
+  __syncthreads();
+  const int spp = nth / M;  // whole sequences per pass (M <= 64 <= nth)
+  const int kk = tid / M, m = tid - kk * M;
+  const int q = a.q;
+  double lam = a.lam;
+  WF_SCENARIO_IN_VGPR(lam);
+  double best_v = -HUGE_VAL;
+  int best_k = INT_MAX;
+  for (int k0 = 0; k0 < K; k0 += spp) {  // (block-uniform)
+    const bool member = kk < spp && k0 + kk < K;
+    double v = 0.0;
+    int rank = 0;
+    if (member) {
+      const double* s = rw + (size_t)(k0 + kk) * M * Hs;
+      v = s[m * Hs];
+      for (int j = 0; j < M; ++j) {
+        const double vj = s[j * Hs];
+        rank += (vj < v) || (vj == v && j < m);
+      }
+    }
+    __syncthreads();  // (the previous pass's tails have been added)
+    if (member) bv[kk * M + rank] = v;
+    __syncthreads();
+    if (tid < spp && k0 + tid < K) {
+      const int k = k0 + tid;
+      const double* s = rw + (size_t)k * M * Hs;
+      double sum = 0.0, tail = 0.0;
+      for (int j = 0; j < M; ++j) sum += s[j * Hs];
+      for (int j = 0; j < q; ++j) tail += bv[tid * M + j];
+      const double mean = sum / (double)M, cvar = tail / (double)q;
+      const double score = ((1.0 - lam) * mean) + (lam * cvar);
+      const size_t o = (size_t)slot * K + k;
+      if (a.expected) a.expected[o] = mean;
+      if (a.cvar) a.cvar[o] = cvar;
+      if (a.score) a.score[o] = score;
+      if (score > best_v || (score == best_v && k < best_k)) { best_v = score; best_k = k; }
+    }
+  }
+  __syncthreads();  // (the last pass's tails have been added: bv becomes the tree)
+  bv[tid] = best_v;
+  bi[tid] = best_k;
+  __syncthreads();
+  for (int s = nth >> 1; s > 0; s >>= 1) {  // (block-uniform)
+    if (tid < s) {
+      const double v = bv[tid + s];
+      const int k = bi[tid + s];
+      if (v > bv[tid] || (v == bv[tid] && k < bi[tid])) { bv[tid] = v; bi[tid] = k; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0 && a.best) a.best[slot] = bi[0] == INT_MAX ? 0 : bi[0];
+}
+
+extern "C" hipError_t wfk_launch_scenario_layout(const WfScenarioLayoutArgs* a, hipStream_t s) {
+  const int R = a->K * a->M * a->H;
+  const int threads = (R <= 128 && a->K * a->N <= 64) ? 64 : 256;  // a few short sequences of a small farm: one wave
+  int Ht = WF_SCENARIO_TILE / a->M;
+  Ht = Ht > a->H ? a->H : Ht;
+  const int Hs = Ht | 1;
+  const size_t lds = sizeof(double) * 2 * (size_t)a->M * Hs;
+  hipLaunchKernelGGL(wf_scenario_layout_kernel, dim3(a->sl.C), dim3(threads), lds, s, *a, Ht, Hs);
+  return hipGetLastError();
+}
+extern "C" hipError_t wfk_launch_scenario_reduce(const WfScenarioReduceArgs* a, hipStream_t s) {
+  // wf_returns_launch's choices with K M sequences — one wave for a few short rows, the odd stride where it fits in 36 KiB —
+  // with two differences, both because a slot has up to 4096 rows here and one workgroup takes them all.  A slot of many
+  // floats (R N >= WF_SCENARIO_WIDE) gets 1024 threads where that leaves the tile its 24 KiB: staging a tile is a chain of
+  // global loads per thread, and its time goes with their number.  And the tile takes what the rewards leave of 63 KiB, 24 KiB at
+  // the least: a tile's rows are added by a thread each, one dependent chain of 5 N additions, so that part goes with the
+  // NUMBER of tiles.
+  const int KM = a->K * a->M, R = KM * a->H;
+  const int Hs = KM * (a->H | 1) <= 4608 ? (a->H | 1) : a->H;
+  const auto head_of = [&](int threads) { return sizeof(double) * ((size_t)KM * Hs + threads) + sizeof(int) * threads; };
+  const size_t room = 63 * 1024, least = 24 * 1024;
+  int threads = R * a->N <= 512 ? 64 : 256;
+  if (R * a->N >= WF_SCENARIO_WIDE && head_of(1024) + least <= room) threads = 1024;
+  const size_t head = head_of(threads);
+  const WfRewardTile t = wf_reward_tile(R, a->N, threads, (int)((room - head) / sizeof(float)));
+  hipLaunchKernelGGL(wf_scenario_reduce_kernel, dim3(a->sl.n_slots), dim3(threads), head + t.lds_bytes, s, *a, t.T, t.sp, t.sl, Hs);
+  return hipGetLastError();
+}
+extern "C" hipError_t wfk_scenario_func_attributes(int kernel, hipFuncAttributes* a) {
+  const void* fn[WF_SCENARIO_KERNELS] = {(const void*)wf_scenario_layout_kernel, (const void*)wf_scenario_reduce_kernel};
+  if (kernel < 0 || kernel >= WF_SCENARIO_KERNELS) return hipErrorInvalidValue;
+  return hipFuncGetAttributes(a, fn[kernel]);
+}

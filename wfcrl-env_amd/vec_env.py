@@ -476,6 +476,48 @@ class VecWindFarmEnv:
         return self.fi.lookahead_returns(a, gamma=gamma, wind=wind, farms=farms, strict=strict,
                                          want=("returns", "rewards", "final_yaw", "best"))
 
+    def scenario_returns(self, action_sequences, members=8, process=None, seed=0, gamma=1.0, tail=None, risk_weight=0.0,
+                         anchor=None, bounds=None, farms=None, strict=False,
+                         want=("expected_returns", "cvar", "score", "best")):
+        """The returns of K candidate action sequences over an ensemble of `members` wind futures drawn from the wind
+        process, from the state the env is in — call it BEFORE `step`: per sequence the mean over the members
+        ("expected_returns"), the tail mean of the `tail` lowest member returns ("cvar"), score = (1 - risk_weight) mean +
+        risk_weight cvar, and "best", the sequence of the largest score; `want` may also name "member_returns", "rewards",
+        "wind_paths" and "final_yaw" (include/wfscenario.h; backend.WfStep.scenario_returns; the project's own definition).
+        action_sequences is {"yaw": (num_envs, K, H, N)} or the array itself, in the env's action encoding; K M H <= 4096.
+        process=None takes the env's wind_process and its distribution's speed bounds; an env without wind_process must be
+        given `process` (and may be given `bounds`, default 3 to 28 m/s).  The paths start at every farm's current wind and
+        revert to `anchor` (n_farms, 2), default the current wind: the planner knows the process, not the episode's
+        realisation — between lookahead_returns(wind=None), which holds the wind, and wind="series", which reads the
+        future.  Works on any episode kind (held wind, file series, generated): only the current wind is read.  Run on a
+        handle of its own: the env's yaw state, accumulators, wind and buffers are read, never changed."""
+        if type(self.reward_shaper).__name__ != "DoNothingReward":
+            raise ValueError("scenario_returns needs the plain reward (DoNothingReward): the return of a shaped reward is "
+                             "not defined here")
+        if process is None:
+            if self._wind_process is None:
+                raise ValueError("scenario_returns needs a wind process: this env was built without wind_process, so pass "
+                                 "process=dict(ws_revert=, ws_sigma=, wd_revert=, wd_sigma=, wd_ramp=)")
+            process = self._wind_process
+            if bounds is None and self._wind_dist is not None:
+                bounds = (float(self._wind_dist.get("ws_lo", 3.0)), float(self._wind_dist.get("ws_hi", 28.0)))
+        if bounds is None:
+            bounds = (3.0, 28.0)
+        a = self._to_device(action_sequences["yaw"] if isinstance(action_sequences, dict) else action_sequences)
+        B, N = self.num_envs, self.num_turbines
+        if a.ndim != 4 or a.shape[0] != B or a.shape[3] != N:
+            raise ValueError("action_sequences must be (num_envs, K, H, num_turbines): K sequences of H joint actions per farm")
+        if farms is not None:
+            idx = np.ascontiguousarray(farms, dtype=np.int64).reshape(-1)
+            if self.return_torch:
+                import torch
+
+                a = a[torch.from_numpy(idx).to(a.device)]
+            else:
+                a = a[idx]
+        return self.fi.scenario_returns(a, members, process, seed=seed, gamma=gamma, tail=tail, risk_weight=risk_weight,
+                                        anchor=anchor, bounds=bounds, farms=farms, strict=strict, want=want)
+
     def return_gradient(self, action_sequences, gamma=1.0, terminal=None, delta=1.0, farms=None, strict=False, wind=None):
         """The derivative of lookahead_returns' returns with respect to the action sequences, from the state the env is
         in — call it BEFORE `step`: dict(returns (n_farms, K) float64, rewards (n_farms, K, H) float64, action_gradient
