@@ -887,6 +887,55 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the plan kernel as the runtime reports them."""
         return self._plan().kernel_info()
 
+    # -- scenario planner: CEM over action sequences scored over a wind ensemble (include/wfscenplan.h) ----
+    def _scenplan(self) -> "_ScenPlan":
+        """The handle's scenplan object; created on first use, destroyed in close() before the handle."""
+        so = getattr(self, "_scenplan_obj", None)
+        if so is None:
+            so = self._scenplan_obj = _ScenPlan(self)
+        return so
+
+    def plan_scenarios(self, horizon, candidates=64, elites=8, members=8, process=None, sigma=None, seed=0, scenario_seed=0,
+                       gamma=1.0, tail=None, risk_weight=0.0, anchor=None, bounds=(3.0, 28.0), mean=None, farms=None,
+                       strict=False, max_eval_farms=65536,
+                       want=("plan", "plan_score", "plan_expected", "plan_cvar", "plan_member_returns", "hold_score",
+                             "first_action", "final_yaw", "mean", "wind_paths"), out=None):
+        """A receding-horizon plan under wind uncertainty for every farm, from the wind and the env state the handle holds,
+        which are read and never changed (include/wfscenplan.h; the project's own definition, PARITY UNPINNED beyond the
+        oracle): plan_actions' cross-entropy method over (horizon, N) raw actions, every candidate scored as
+        scenario_returns scores a sequence — over `members` wind futures drawn once per farm from the process, by
+        score = (1 - risk_weight) mean + risk_weight cvar of its member returns.  The futures are the same for every
+        candidate and every iteration (common random numbers), so the best sequence carried forward scores the same bits
+        again and the plan's score never decreases.  One glue kernel stands between two evaluator steps.
+          horizon    H, 1 <= H <= 64
+          candidates K >= 3;  elites 1 <= E <= K;  members M in 1..64;  K M H <= 4096
+          process    dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp) as generate_wind's (missing: 0)
+          sigma      one width per iteration (at most 16), degrees, non-negative; None: (1, 1/2, 1/4) yaw_step
+          seed       of the candidates' draws;  scenario_seed  of the member paths (scenario_returns' `seed`)
+          gamma      discount in [0, 1]
+          tail       q in 1..M (None: M);  risk_weight  lam in [0, 1]
+          anchor     (n_farms, 2) float64 (speed > 0, direction) the paths revert to; None: every farm's current wind
+          bounds     (ws_lo, ws_hi) the stored speeds are clipped to, 0 < ws_lo < ws_hi
+          mean       (n_farms, H, N) float32 the warm start, or None: zeros
+          farms, strict, max_eval_farms   as plan_actions'; a farm takes K M H rows
+          want       of "plan" (n, H, N) float32, "plan_score", "plan_expected", "plan_cvar" (n,) float64 — the winner's in the
+                     last iteration —, "plan_member_returns" (n, M) float64, "hold_score" (n,) float64 — the score of doing
+                     nothing —, "first_action" (n, N) float32, "final_yaw" (n, N) float32, "mean" (n, H, N) float32,
+                     "wind_paths" (n, M, H, 2) float64
+          out        dict of tensors / arrays of those names to write into
+        Returns a dict of the outputs.  Deterministic: fixed summation orders, no atomics.  With torch tensors (anchor, mean
+        or out) the call only enqueues work on torch's current stream and returns torch CUDA tensors."""
+        return self._scenplan().run(horizon, candidates, elites, members, process, sigma, seed, scenario_seed, gamma, tail,
+                                    risk_weight, anchor, bounds, mean, farms, strict, max_eval_farms, want, out)
+
+    def plan_scenarios_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last plan_scenarios {"total_ms", "step_ms", "glue_ms"}."""
+        return self._scenplan().timing(detail)
+
+    def plan_scenarios_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the scenplan kernels as the runtime reports them."""
+        return self._scenplan().kernel_info()
+
     # -- wind-rose expected power and the yaw look-up table (include/wfrose.h) -------------------------
     def _rose(self) -> "_Rose":
         """The handle's rose object; created on first use, destroyed in close() before the handle."""
@@ -1254,7 +1303,7 @@ class WfStep:
             # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h,
             # wfcredit.h, wflookahead.h, wfplan.h, wfretgrad.h, wfrollout.h — the rollout object, created on the rose object, before it)
             for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rollout_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
-                         "_lookahead_obj", "_scenario_obj", "_plan_obj", "_retgrad_obj", "_windgen_obj"):
+                         "_lookahead_obj", "_scenario_obj", "_plan_obj", "_scenplan_obj", "_retgrad_obj", "_windgen_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
                     ext.close()
@@ -2036,4 +2085,79 @@ class _Plan(_Ext):
         p = dict(zip(spec, ptrs))
         self._call("run", H, K, E, int(sg.size), sg.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF, float(gamma), wptr, mptr, n, fptr,
                    *[p.get(k) for k in self.OUTPUTS], int(on_device))
+        return {k: out[k] for k in spec}
+
+
+class _ScenPlan(_Ext):
+    """The `wf_scenplan` object of a WfStep handle (include/wfscenplan.h)."""
+
+    NAME = "scenplan"
+    KERNELS = ("paths", "advance")
+    OUTPUTS = ("plan", "plan_score", "plan_expected", "plan_cvar", "plan_member_returns", "hold_score", "first_action", "final_yaw",
+               "mean", "wind_paths")
+
+    def run(self, horizon, candidates, elites, members, process, sigma, seed, scenario_seed, gamma, tail, risk_weight, anchor,
+            bounds, mean, farms, strict, max_eval_farms, want, out):
+        w = self._w
+        N = w.num_turbines
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.OUTPUTS for k in want):
+            raise ValueError("want must name " + ", ".join(self.OUTPUTS[:-1]) + " and / or " + self.OUTPUTS[-1])
+        if process is None:
+            raise ValueError("plan_scenarios needs a wind process: dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp)")
+        unknown = set(process) - set(_Scenario.PROCESS)
+        if unknown:
+            raise ValueError(f"unknown wind process parameter(s): {sorted(unknown)}")
+        proc = WindProcess(**{k: float(process.get(k, 0.0)) for k in _Scenario.PROCESS})
+        H, K, E, M = int(horizon), int(candidates), int(elites), int(members)
+        q = M if tail is None else int(tail)
+        ws_lo, ws_hi = (float(v) for v in bounds)
+        if sigma is None:
+            step = getattr(w, "_env_yaw_step", 5.0)
+            sigma = (step, 0.5 * step, 0.25 * step)
+        sg = np.ascontiguousarray(np.atleast_1d(sigma), dtype=np.float64).reshape(-1)
+        self._call("config", int(bool(strict)), int(max_eval_farms or 0))
+        fa, n, fptr = self._farms(farms)
+        on_device = _is_torch(anchor) or _is_torch(mean) or (out is not None and any(_is_torch(v) for v in out.values()))
+        like = None
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            like = next(v for v in [anchor, mean] + list((out or {}).values()) if _is_torch(v))
+        aptr = mptr = None
+        if anchor is not None:
+            if on_device:
+                if not _is_torch(anchor):
+                    anchor = torch.as_tensor(np.array(anchor, np.float64), device=like.device)
+                assert anchor.is_cuda and anchor.dtype == torch.float64, "anchor"
+                anchor = anchor.contiguous()
+            else:
+                anchor = np.ascontiguousarray(anchor, dtype=np.float64)
+            if tuple(anchor.shape) != (n, 2):
+                raise ValueError("anchor must be (n_farms, 2): the (speed, direction) every listed farm's paths revert to")
+            aptr = anchor.data_ptr() if on_device else anchor.ctypes.data
+        if mean is not None:
+            if on_device:
+                if not _is_torch(mean):
+                    mean = torch.as_tensor(np.asarray(mean, np.float32), device=like.device)
+                assert mean.is_cuda and mean.dtype == torch.float32, "mean"
+                mean = mean.contiguous()
+            else:
+                mean = np.ascontiguousarray(mean, dtype=np.float32)
+            if tuple(mean.shape) != (n, H, N):
+                raise ValueError("mean must be (n_farms, H, num_turbines): the warm start of every listed farm")
+            mptr = mean.data_ptr() if on_device else mean.ctypes.data
+        shapes = {"plan": ((n, H, N), np.float32), "plan_score": ((n,), np.float64), "plan_expected": ((n,), np.float64),
+                  "plan_cvar": ((n,), np.float64), "plan_member_returns": ((n, M), np.float64), "hold_score": ((n,), np.float64),
+                  "first_action": ((n, N), np.float32), "final_yaw": ((n, N), np.float32), "mean": ((n, H, N), np.float32),
+                  "wind_paths": ((n, M, H, 2), np.float64)}
+        spec = {k: shapes[k] for k in self.OUTPUTS if k in want}
+        if out is None and not (1 <= M <= 64 and 1 <= H <= 64 and K * M * H <= 4096):
+            spec = {k: ((0,), d) for k, (_, d) in spec.items()}  # (the library refuses these limits by name: nothing to allocate)
+        out, ptrs = self._outputs(out, spec, on_device, like)
+        ptr = dict(zip(spec, ptrs))
+        self._call("run", H, K, E, int(sg.size), sg.ctypes.data, C.c_ulonglong(int(seed) & (2**64 - 1)), float(gamma), M, C.byref(proc),
+                   ws_lo, ws_hi, C.c_ulonglong(int(scenario_seed) & (2**64 - 1)), q, float(risk_weight), aptr, mptr, n, fptr,
+                   *[ptr.get(k) for k in self.OUTPUTS], int(on_device))
         return {k: out[k] for k in spec}

@@ -588,6 +588,53 @@ class VecWindFarmEnv:
         return self.fi.plan_actions(horizon, candidates=candidates, elites=elites, sigma=sigma, seed=seed, gamma=gamma, wind=wind,
                                     mean=mean, farms=farms, strict=strict, max_eval_farms=max_eval_farms, want=want, out=out)
 
+    def plan_scenarios(self, horizon, candidates=64, elites=8, members=8, process=None, sigma=None, seed=0, scenario_seed=0,
+                       gamma=1.0, tail=None, risk_weight=0.0, anchor=None, bounds=None, mean=None, farms=None, strict=False,
+                       max_eval_farms=65536, want=("first_action", "plan_score")):
+        """A receding-horizon plan under wind uncertainty for every farm from the state the env is in — call it BEFORE
+        `step`, execute {"yaw": first_action}, shift "mean" by one step and pass it back as `mean`: plan_actions' search,
+        every candidate scored as scenario_returns scores a sequence, over `members` wind futures drawn from the wind process
+        (include/wfscenplan.h; backend.WfStep.plan_scenarios has the arguments; the project's own definition).  Returns the
+        outputs `want` names — "plan", "plan_score", "plan_expected", "plan_cvar", "plan_member_returns", "hold_score",
+        "first_action", "final_yaw", "mean", "wind_paths" —, torch CUDA tensors when the env returns torch.  process=None takes
+        the env's wind_process and its distribution's speed bounds, as scenario_returns does; an env without wind_process must
+        be given `process` (and may be given `bounds`, default 3 to 28 m/s).  Continuous control only.  Works on any episode
+        kind (held wind, file series, generated): only the current wind is read.  Run on a handle of its own: the env's yaw
+        state, accumulators, wind and buffers are read, never changed."""
+        if type(self.reward_shaper).__name__ != "DoNothingReward":
+            raise ValueError("plan_scenarios needs the plain reward (DoNothingReward): the return of a shaped reward is not "
+                             "defined here")
+        if process is None:
+            if self._wind_process is None:
+                raise ValueError("plan_scenarios needs a wind process: this env was built without wind_process, so pass "
+                                 "process=dict(ws_revert=, ws_sigma=, wd_revert=, wd_sigma=, wd_ramp=)")
+            process = self._wind_process
+            if bounds is None and self._wind_dist is not None:
+                bounds = (float(self._wind_dist.get("ws_lo", 3.0)), float(self._wind_dist.get("ws_hi", 28.0)))
+        if bounds is None:
+            bounds = (3.0, 28.0)
+        out = None
+        if self.return_torch:
+            import torch
+
+            anchor = None if anchor is None else self._to_device(anchor).double()
+            mean = None if mean is None else self._to_device(mean).float()
+            want = (want,) if isinstance(want, str) else tuple(want)
+            n = self.num_envs if farms is None else int(np.asarray(farms).size)
+            H, M, N = int(horizon), int(members), self.num_turbines
+            f32, f64 = torch.float32, torch.float64
+            shapes = {"plan": ((n, H, N), f32), "plan_score": ((n,), f64), "plan_expected": ((n,), f64), "plan_cvar": ((n,), f64),
+                      "plan_member_returns": ((n, M), f64), "hold_score": ((n,), f64), "first_action": ((n, N), f32),
+                      "final_yaw": ((n, N), f32), "mean": ((n, H, N), f32), "wind_paths": ((n, M, H, 2), f64)}
+            if any(k not in shapes for k in want):
+                raise ValueError("want must name " + ", ".join(list(shapes)[:-1]) + " and / or wind_paths")
+            if 1 <= H <= 64 and 1 <= M <= 64:  # (else the library refuses by name: nothing to allocate)
+                out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=f"cuda:{self.fi.device_id}") for k in want}
+        return self.fi.plan_scenarios(horizon, candidates=candidates, elites=elites, members=members, process=process, sigma=sigma,
+                                      seed=seed, scenario_seed=scenario_seed, gamma=gamma, tail=tail, risk_weight=risk_weight,
+                                      anchor=anchor, bounds=bounds, mean=mean, farms=farms, strict=strict,
+                                      max_eval_farms=max_eval_farms, want=want, out=out)
+
     def controller_returns(self, controllers, horizon, gamma=1.0, wind=None, filter0=None, farms=None, strict=False,
                            max_eval_farms=65536, want=("returns", "best")):
         """What each of K look-up-table controllers — table slot, filter gain alpha, deadband, preview `lead` — earns over
