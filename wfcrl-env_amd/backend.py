@@ -1068,6 +1068,56 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the rollout kernels as the runtime reports them."""
         return self._rollout().kernel_info()
 
+    # -- scenario rollouts: yaw-table controllers in closed loop over a wind ensemble (include/wfrollscen.h) --
+    def _rollscen(self) -> "_RollScen":
+        """The handle's scenario-rollout object, created on its rose object on first use; destroyed in close() before it."""
+        ro = getattr(self, "_rollscen_obj", None)
+        if ro is None:
+            ro = self._rollscen_obj = _RollScen(self)
+        return ro
+
+    def controller_scenarios(self, controllers, horizon, members, process, seed=0, gamma=1.0, tail=None, risk_weight=0.0,
+                             anchor=None, bounds=(3.0, 28.0), filter0=None, farms=None, strict=False, max_eval_farms=65536,
+                             want=("expected_returns", "cvar", "score", "best"), out=None):
+        """What each of K look-up-table controllers earns over the next `horizon` steps of the fused env, in closed loop,
+        under each of `members` wind futures drawn on the device from a wind process, from the wind and the env state the
+        handle holds, which are read and never changed (include/wfrollscen.h; the project's own definition, PARITY UNPINNED
+        beyond the oracle): controller_returns' controller under scenario_returns' paths, rows, rewards and statistics.
+        Every farm draws M paths of H ticks that start at its current wind (scenario_returns' paths, bit for bit); under
+        member m controller k observes obs[min(h + lead, H)] — obs[0] the current wind, obs[j] member m's tick j —, filters
+        it, looks its table up, holds inside its deadband and goes through the step's own budget gate, increment and clip;
+        the K M H yaws of a farm are rows of one batched step, row (k, m, h) solved under member m's tick h + 1; then per
+        controller the mean over the members, the tail mean (CVaR) of the `tail` lowest member returns and
+        score = (1 - risk_weight) mean + risk_weight cvar.  A controller with lead >= 1 previews ITS OWN member's future: a
+        perfect forecast inside each scenario.
+          controllers  as controller_returns takes them (controller_grid builds a tuning grid), K <= 64
+          horizon      H in 1..64;  members  M in 1..64;  K M H <= 4096
+          process, seed, gamma, tail, risk_weight, anchor, bounds   as scenario_returns'
+          filter0      (n_farms, K, 2) float64 the filter states to start from, the same under every member; None: the
+                       farm's current wind
+          farms, strict, max_eval_farms   as scenario_returns'; a farm takes K M H rows
+          want         of "expected_returns", "cvar", "score" (n, K) float64, "member_returns" (n, K, M) float64, "rewards"
+                       (n, K, M, H) float64, "wind_paths" (n, M, H, 2) float64, "actions" (n, K, M, H, N) float32 — the RAW
+                       actions —, "final_yaw" (n, K, M, N) float32, "gated" (n, K, M) int32, "first_action" (n, K, N)
+                       float32 — member 0's action of step 0, the same under every member iff lead == 0 —, "best" (n,) int32 —
+                       the controller of the largest score, the lowest index among equal maxima
+          out          dict of tensors / arrays of those names to write into
+        wind_paths, actions, final_yaw, gated and first_action do not depend on the solver: the same bits in every mode.
+        Deterministic: fixed summation orders, no floating-point atomics; any chunking and any farm list give the same bits
+        in strict mode.  With torch tensors (anchor, filter0 or out) the call only enqueues work on torch's current stream
+        and returns torch CUDA tensors."""
+        return self._rollscen().run(controllers, horizon, members, process, seed, gamma, tail, risk_weight, anchor, bounds,
+                                    filter0, farms, strict, max_eval_farms, want, out)
+
+    def controller_scenarios_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last controller_scenarios {"total_ms", "step_ms", "glue_ms"}."""
+        return self._rollscen().timing(detail)
+
+    def controller_scenarios_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the scenario-rollout kernels as the runtime reports them:
+        "layout" (its brackets in LDS), "layout_spill" (its brackets in global memory), "reduce"."""
+        return self._rollscen().kernel_info()
+
     # -- fused env step (SURVEY f1) ---------------------------------------------------------------
     def env_config(self, yaw_lo=-40.0, yaw_hi=40.0, yaw_step=5.0, actuator_rate=0.3, dt=60.0, budget=0.1,
                    load_coef=0.1, discrete=False, power_mw=False):
@@ -1301,8 +1351,9 @@ class WfStep:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h,
-            # wfcredit.h, wflookahead.h, wfplan.h, wfretgrad.h, wfrollout.h — the rollout object, created on the rose object, before it)
-            for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rollout_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
+            # wfcredit.h, wflookahead.h, wfplan.h, wfretgrad.h, wfrollout.h, wfrollscen.h — the rollout and the scenario-rollout
+            # object, created on the rose object, before it)
+            for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rollout_obj", "_rollscen_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
                          "_lookahead_obj", "_scenario_obj", "_plan_obj", "_scenplan_obj", "_retgrad_obj", "_windgen_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
@@ -2022,6 +2073,74 @@ class _Rollout(_Ext):
         p = dict(zip(spec, ptrs))
         self._call("run", K, ctl["slot"].ctypes.data, ctl["alpha"].ctypes.data, ctl["deadband"].ctypes.data, ctl["lead"].ctypes.data,
                    H, wptr, f0ptr, float(gamma), n, fptr, *[p.get(k) for k in self.OUTPUTS], int(on_device))
+        return {k: out[k] for k in spec}
+
+
+class _RollScen(_Rollout):
+    """The `wf_rollscen` object of a WfStep handle (include/wfrollscen.h), created on the handle's rose object; the
+    controllers are taken as the rollout object takes them."""
+
+    NAME = "rollscen"
+    KERNELS = ("layout", "layout_spill", "reduce")
+    OUTPUTS = ("expected_returns", "cvar", "score", "member_returns", "rewards", "wind_paths", "actions", "final_yaw", "gated",
+               "first_action", "best")
+
+    def run(self, controllers, horizon, members, process, seed, gamma, tail, risk_weight, anchor, bounds, filter0, farms, strict,
+            max_eval_farms, want, out):
+        w = self._w
+        N = w.num_turbines
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.OUTPUTS for k in want):
+            raise ValueError("want must name " + ", ".join(self.OUTPUTS[:-1]) + " and / or " + self.OUTPUTS[-1])
+        if process is None:
+            raise ValueError("controller_scenarios needs a wind process: dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp)")
+        unknown = set(process) - set(_Scenario.PROCESS)
+        if unknown:
+            raise ValueError(f"unknown wind process parameter(s): {sorted(unknown)}")
+        p = WindProcess(**{k: float(process.get(k, 0.0)) for k in _Scenario.PROCESS})
+        ctl, K = self._controllers(controllers)
+        H, M = int(horizon), int(members)
+        q = M if tail is None else int(tail)
+        ws_lo, ws_hi = (float(v) for v in bounds)
+        self._call("config", int(bool(strict)), int(max_eval_farms or 0))
+        fa, n, fptr = self._farms(farms)
+        on_device = _is_torch(anchor) or _is_torch(filter0) or (out is not None and any(_is_torch(v) for v in out.values()))
+        like = None
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            like = next(v for v in [anchor, filter0] + list((out or {}).values()) if _is_torch(v))
+
+        def f64(a, shape, name, what):
+            if a is None:
+                return None, None
+            if on_device:
+                if not _is_torch(a):
+                    a = torch.as_tensor(np.asarray(a, np.float64), device=like.device)
+                assert a.is_cuda and a.dtype == torch.float64, name
+                a = a.contiguous()
+            else:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+            if tuple(a.shape) != shape:
+                raise ValueError(f"{name} must be {what}")
+            return a, (a.data_ptr() if on_device else a.ctypes.data)
+
+        anchor, aptr = f64(anchor, (n, 2), "anchor", "(n_farms, 2): the (speed, direction) every listed farm's paths revert to")
+        filter0, f0ptr = f64(filter0, (n, K, 2), "filter0", "(n_farms, K, 2): the (speed, direction) every controller's filter starts from")
+        f8, f4, i4 = np.float64, np.float32, np.int32
+        shapes = {"expected_returns": ((n, K), f8), "cvar": ((n, K), f8), "score": ((n, K), f8), "member_returns": ((n, K, M), f8),
+                  "rewards": ((n, K, M, H), f8), "wind_paths": ((n, M, H, 2), f8), "actions": ((n, K, M, H, N), f4),
+                  "final_yaw": ((n, K, M, N), f4), "gated": ((n, K, M), i4), "first_action": ((n, K, N), f4), "best": ((n,), i4)}
+        if not (1 <= K <= 64 and 1 <= M <= 64 and 1 <= H <= 64 and K * M * H <= 4096):
+            shapes = {k: ((0,), d) for k, (_, d) in shapes.items()}  # (the library names the limit; no output is sized from a refused shape)
+            out = None
+        spec = {k: shapes[k] for k in self.OUTPUTS if k in want}
+        out, ptrs = self._outputs(out, spec, on_device, like)
+        ptr = dict(zip(spec, ptrs))
+        self._call("run", K, ctl["slot"].ctypes.data, ctl["alpha"].ctypes.data, ctl["deadband"].ctypes.data, ctl["lead"].ctypes.data,
+                   H, M, C.byref(p), ws_lo, ws_hi, C.c_ulonglong(int(seed) & (2**64 - 1)), float(gamma), q, float(risk_weight),
+                   aptr, f0ptr, n, fptr, *[ptr.get(k) for k in self.OUTPUTS], int(on_device))
         return {k: out[k] for k in spec}
 
 

@@ -677,6 +677,54 @@ class VecWindFarmEnv:
         return self.fi.controller_returns(controllers, horizon, gamma=gamma, wind=wind, filter0=filter0, farms=farms, strict=strict,
                                           max_eval_farms=max_eval_farms, want=want, out=out)
 
+    def controller_scenarios(self, controllers, horizon, members=8, process=None, seed=0, gamma=1.0, tail=None, risk_weight=0.0,
+                             anchor=None, bounds=None, filter0=None, farms=None, strict=False, max_eval_farms=65536,
+                             want=("expected_returns", "cvar", "score", "best")):
+        """What each of K look-up-table controllers earns over the next `horizon` steps in closed loop under each of `members`
+        wind futures drawn from the wind process, from the state the env is in — call it BEFORE `step`: per controller the
+        mean over the members ("expected_returns"), the tail mean of the `tail` lowest member returns ("cvar"),
+        score = (1 - risk_weight) mean + risk_weight cvar, and "best", the controller of the largest score; `want` may also
+        name "member_returns", "rewards", "wind_paths", "actions", "final_yaw", "gated" and "first_action" — {"yaw":
+        first_action[farm, best[farm]]} is what a receding-horizon selector gives `step` (include/wfrollscen.h;
+        backend.WfStep.controller_scenarios has the arguments and WfStep.controller_grid builds a tuning grid; the project's
+        own definition).  process=None takes the env's wind_process and its distribution's speed bounds, exactly as
+        scenario_returns does; an env without wind_process must be given `process` (and may be given `bounds`, default 3 to
+        28 m/s).  The tables are those of `self.fi.set_yaw_table`.  Works on any episode kind (held wind, file series,
+        generated): only the current wind is read.  Run on a handle of its own: the env's yaw state, accumulators, wind
+        and buffers are read, never changed."""
+        if type(self.reward_shaper).__name__ != "DoNothingReward":
+            raise ValueError("controller_scenarios needs the plain reward (DoNothingReward): the return of a shaped reward is "
+                             "not defined here")
+        if process is None:
+            if self._wind_process is None:
+                raise ValueError("controller_scenarios needs a wind process: this env was built without wind_process, so pass "
+                                 "process=dict(ws_revert=, ws_sigma=, wd_revert=, wd_sigma=, wd_ramp=)")
+            process = self._wind_process
+            if bounds is None and self._wind_dist is not None:
+                bounds = (float(self._wind_dist.get("ws_lo", 3.0)), float(self._wind_dist.get("ws_hi", 28.0)))
+        if bounds is None:
+            bounds = (3.0, 28.0)
+        out = None
+        if self.return_torch:
+            import torch
+
+            anchor = None if anchor is None else self._to_device(anchor).double()
+            filter0 = None if filter0 is None else self._to_device(filter0).double()
+            want = (want,) if isinstance(want, str) else tuple(want)
+            n = self.num_envs if farms is None else int(np.asarray(farms).size)
+            K, H, M, N = self.fi._rollscen()._controllers(controllers)[1], int(horizon), int(members), self.num_turbines
+            f32, f64, i32 = torch.float32, torch.float64, torch.int32
+            shapes = {"expected_returns": ((n, K), f64), "cvar": ((n, K), f64), "score": ((n, K), f64), "member_returns": ((n, K, M), f64),
+                      "rewards": ((n, K, M, H), f64), "wind_paths": ((n, M, H, 2), f64), "actions": ((n, K, M, H, N), f32),
+                      "final_yaw": ((n, K, M, N), f32), "gated": ((n, K, M), i32), "first_action": ((n, K, N), f32), "best": ((n,), i32)}
+            if any(k not in shapes for k in want):
+                raise ValueError("want must name " + ", ".join(list(shapes)[:-1]) + " and / or best")
+            if 1 <= K <= 64 and 1 <= M <= 64 and 1 <= H <= 64 and K * M * H <= 4096:  # (else the library refuses by name)
+                out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=f"cuda:{self.fi.device_id}") for k in want}
+        return self.fi.controller_scenarios(controllers, horizon, members, process, seed=seed, gamma=gamma, tail=tail,
+                                            risk_weight=risk_weight, anchor=anchor, bounds=bounds, filter0=filter0, farms=farms,
+                                            strict=strict, max_eval_farms=max_eval_farms, want=want, out=out)
+
     def _series_keyword(self, name, wind, steps):
         """The wind keyword of counterfactual_rewards / lookahead_returns: None or "series"; a time-series episode needs
         "series", any other episode None."""
