@@ -352,15 +352,33 @@ ROLLSCEN_ABI = {
     "wf_rollscen_last_error": (C.c_char_p, [_P]),
 }
 
+# every symbol include/wfmodelset.h declares (wake-model parameter sets per farm): its own table
+_MODEL_SET_FIELDS = ("ambient_ti", "shear", "veer", "alpha", "beta", "ka", "kb", "ad", "bd", "dm",
+                     "ch_initial", "ch_constant", "ch_ai", "ch_downstream", "defl_alpha", "defl_beta", "defl_ka", "defl_kb")
+
+
+class ModelSet(C.Structure):
+    """Mirror of `struct wf_model_set` (include/wfmodelset.h)."""
+
+    _fields_ = [(n, C.c_double) for n in _MODEL_SET_FIELDS]
+
+
+MODELSET_ABI = {
+    "wf_set_model_sets": (C.c_int, [_P, C.c_int, C.POINTER(ModelSet), C.POINTER(C.c_int)]),
+    "wf_get_model_sets": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(ModelSet), C.POINTER(C.c_int)]),
+    "wf_model_set_from_model": (C.c_int, [_P, C.POINTER(ModelSet)]),
+    "wf_model_sets_last_kernel": (C.c_int, [_P, C.POINTER(C.c_int)]),
+}
+
 _lib = None
 
 
 def build(force: bool = False) -> Path:
     """Compile csrc/ into libwfstep.so with hipcc for gfx950 (cross-compiles without a GPU)."""
     srcs = []
-    for d in ("", "ext", "probe", "yawopt", "rose", "robust", "grad", "credit", "lookahead", "plan", "series", "rollout", "retgrad", "windgen", "scenario", "scenplan", "rollscen"):  # csrc/ itself, the extensions' shared layer, the extensions
+    for d in ("", "ext", "modelset", "probe", "yawopt", "rose", "robust", "grad", "credit", "lookahead", "plan", "series", "rollout", "retgrad", "windgen", "scenario", "scenplan", "rollscen"):  # csrc/ itself, the extensions' shared layer, the extensions
         srcs += sorted((PKG_DIR / "csrc" / d).glob("*.hip")) + sorted((PKG_DIR / "csrc" / d).glob("*.h"))
-    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfprobe.h", "wfyawopt.h", "wfrose.h", "wfrobust.h", "wfgrad.h", "wfcredit.h", "wflookahead.h", "wfplan.h", "wfseries.h", "wfrollout.h", "wfretgrad.h", "wfwindgen.h", "wfscenario.h", "wfscenplan.h", "wfrollscen.h")]
+    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfmodelset.h", "wfprobe.h", "wfyawopt.h", "wfrose.h", "wfrobust.h", "wfgrad.h", "wfcredit.h", "wflookahead.h", "wfplan.h", "wfseries.h", "wfrollout.h", "wfretgrad.h", "wfwindgen.h", "wfscenario.h", "wfscenplan.h", "wfrollscen.h")]
     stale = (not LIB_PATH.exists()) or any(s.stat().st_mtime > LIB_PATH.stat().st_mtime for s in srcs)
     if force or stale:
         subprocess.run(["make", "-j4", "-C", str(PKG_DIR / "csrc")] + (["-B"] if force else []), check=True)
@@ -391,7 +409,7 @@ def load() -> C.CDLL:
             build()
         _share_hip_runtime_with_torch()
         lib = C.CDLL(str(LIB_PATH))
-        for table in (ABI, PROBE_ABI, YAWOPT_ABI, ROSE_ABI, ROBUST_ABI, GRAD_ABI, CREDIT_ABI, LOOKAHEAD_ABI, PLAN_ABI, SERIES_ABI, ROLLOUT_ABI, RETGRAD_ABI, WINDGEN_ABI, SCENARIO_ABI, SCENPLAN_ABI, ROLLSCEN_ABI):
+        for table in (ABI, MODELSET_ABI, PROBE_ABI, YAWOPT_ABI, ROSE_ABI, ROBUST_ABI, GRAD_ABI, CREDIT_ABI, LOOKAHEAD_ABI, PLAN_ABI, SERIES_ABI, ROLLOUT_ABI, RETGRAD_ABI, WINDGEN_ABI, SCENARIO_ABI, SCENPLAN_ABI, ROLLSCEN_ABI):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
                 fn.restype, fn.argtypes = res, args

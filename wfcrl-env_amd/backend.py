@@ -80,9 +80,43 @@ def wd_uncertainty_members(spec) -> tuple:
     return delta, weight, frame
 
 
+def normalize_model_sets(sets, base: dict) -> tuple:
+    """({field: float64 array [S]} over the eighteen fields of include/wfmodelset.h, S) from a list of dicts or a dict of
+    arrays; a field that is not given takes `base[field]` (the handle's model).  Unknown keys are refused by name; needs no
+    device."""
+    fields = _lib._MODEL_SET_FIELDS
+    if isinstance(sets, dict):
+        unknown = sorted(set(sets) - set(fields))
+        if unknown:
+            raise ValueError(f"unknown model-set field(s): {unknown} (a set may change: {list(fields)})")
+        cols = {k: np.atleast_1d(np.asarray(v, dtype=np.float64)) for k, v in sets.items()}
+        sizes = {v.shape for v in cols.values()}
+        if len(sizes) != 1 or len(next(iter(sizes))) != 1 or next(iter(sizes))[0] < 1:
+            raise ValueError("model sets as a dict of arrays: every field needs one 1-D array of the same length S >= 1")
+        S = next(iter(sizes))[0]
+    else:
+        sets = list(sets)
+        if not sets or not all(isinstance(d, dict) for d in sets):
+            raise ValueError("model sets: a list of dicts or a dict of arrays")
+        unknown = sorted(set().union(*sets) - set(fields))
+        if unknown:
+            raise ValueError(f"unknown model-set field(s): {unknown} (a set may change: {list(fields)})")
+        S = len(sets)
+        cols = {k: np.array([float(d.get(k, base[k])) for d in sets], dtype=np.float64) for k in set().union(*sets)}
+    out = {f: np.ascontiguousarray(cols[f]) if f in cols else np.full(S, float(base[f])) for f in fields}
+    for f, v in out.items():
+        if not np.isfinite(v).all():
+            raise ValueError(f"model sets: {f} is not finite")
+    if not (out["ambient_ti"] > 0.0).all():
+        raise ValueError("model sets: ambient_ti must be > 0")
+    return out, S
+
+
 class WfStep:
     def __init__(self, xcoords, ycoords, env_batch: int = 1, device_id: int = 0, model: dict | None = None,
-                 kernel_choice: dict | None = None, layout_of=None):
+                 kernel_choice: dict | None = None, layout_of=None, model_sets=None, model_set_of=None):
+        if model_sets is None and model_set_of is not None:
+            raise ValueError("model_set_of comes with model_sets")
         self._lib = _lib.load()
         self._h = C.c_void_p()
         check(self._lib.wf_create(int(device_id), C.byref(self._h)))
@@ -104,6 +138,8 @@ class WfStep:
             self._apply_turbine_defs()
             if kernel_choice:
                 self.set_kernel_choice(**kernel_choice)
+            if model_sets is not None:
+                self.set_model_sets(model_sets, model_set_of)
             return
         xy = np.asarray(xcoords, dtype=np.float64), np.asarray(ycoords, dtype=np.float64)
         if xy[0].ndim == 2:  # several layouts in the batch: [n_layouts][n_turbines], layout_of[env_batch] (set_layouts)
@@ -118,6 +154,8 @@ class WfStep:
         self._apply_turbine_defs()
         if kernel_choice:  # keyword arguments of set_kernel_choice: which kernels may serve this handle
             self.set_kernel_choice(**kernel_choice)
+        if model_sets is not None:  # wake-model parameter sets per farm (set_model_sets)
+            self.set_model_sets(model_sets, model_set_of)
 
     # -- configuration ---------------------------------------------------------------------------
     def set_model(self, model: dict):
@@ -196,6 +234,55 @@ class WfStep:
         n = C.c_int(0)
         check(self._lib.wf_get_turbine_types(self._h, C.byref(n)), self._h)
         return int(n.value)
+
+    # -- wake-model parameter sets per farm (include/wfmodelset.h) ------------------------------------------------
+    def model_set_from_model(self) -> dict:
+        """The handle's model as a parameter set (wf_model_set_from_model): the starting point of a perturbation."""
+        s = _lib.ModelSet()
+        check(self._lib.wf_model_set_from_model(self._h, C.byref(s)), self._h)
+        return {n: float(getattr(s, n)) for n in _lib._MODEL_SET_FIELDS}
+
+    def set_model_sets(self, sets, set_of=None):
+        """Wake-model parameter sets per farm (include/wfmodelset.h: wf_set_model_sets).  `sets`: a list of dicts of any of the
+        eighteen fields of `_lib._MODEL_SET_FIELDS`, or a dict of arrays of one length S; a missing field is the handle's
+        model.  `set_of[env_batch]`: the set of each farm (None: S == env_batch, farm b takes set b).  While sets are held
+        EVERY farm is solved by the float64 kernels on every step (risk_resolve() reports 2): that is the cost.  None / []
+        clears them (clear_model_sets)."""
+        if sets is None or len(sets) == 0:
+            return self.clear_model_sets()
+        arr, S = normalize_model_sets(sets, self.model_set_from_model())
+        so = None
+        if set_of is not None:
+            so = np.ascontiguousarray(set_of, dtype=np.int32)
+            if so.shape != (self.env_batch,):
+                raise ValueError("set_of must have one entry per env")
+        c = (_lib.ModelSet * S)()
+        for k in range(S):
+            for n in _lib._MODEL_SET_FIELDS:
+                setattr(c[k], n, float(arr[n][k]))
+        check(self._lib.wf_set_model_sets(self._h, S, c, so.ctypes.data_as(C.POINTER(C.c_int)) if so is not None else None), self._h)
+
+    def clear_model_sets(self):
+        """Back to the handle's one model; the re-solve mode set before is in force again."""
+        check(self._lib.wf_set_model_sets(self._h, 0, None, None), self._h)
+
+    def model_sets(self):
+        """(dict of float64 arrays of length S, set_of int32 [env_batch]) in force; ({field: empty}, empty) without sets."""
+        n = C.c_int(0)
+        check(self._lib.wf_get_model_sets(self._h, C.byref(n), None, None), self._h)
+        S = int(n.value)
+        if S == 0:
+            return {f: np.zeros(0) for f in _lib._MODEL_SET_FIELDS}, np.zeros(0, np.int32)
+        c = (_lib.ModelSet * S)()
+        so = np.zeros(self.env_batch, np.int32)
+        check(self._lib.wf_get_model_sets(self._h, C.byref(n), c, so.ctypes.data_as(C.POINTER(C.c_int))), self._h)
+        return {f: np.array([getattr(c[k], f) for k in range(S)], dtype=np.float64) for f in _lib._MODEL_SET_FIELDS}, so
+
+    def model_sets_kernel(self) -> int:
+        """Waves per farm of the float64 kernel behind the last step with sets: 4 (four-wave kernel), 1 (one-wave kernel), 0."""
+        w = C.c_int(0)
+        check(self._lib.wf_model_sets_last_kernel(self._h, C.byref(w)), self._h)
+        return int(w.value)
 
     def set_layout(self, xcoords, ycoords):
         x = np.ascontiguousarray(xcoords, dtype=np.float64)
@@ -981,6 +1068,8 @@ class WfStep:
             raise ValueError("wd_axis and ws_axis must be 1-D with at least one node each")
         if self.turbine_types():
             raise ValueError("WF_E_UNSUPPORTED: a yaw table is built for one turbine definition (and the layout of set_layout)")
+        if self.model_sets()[1].size:
+            raise ValueError("WF_E_UNSUPPORTED: a yaw table is built for one wake model: this handle holds parameter sets per farm")
         Dt, St = wd_axis.size, ws_axis.size
         x, y = self._layout_xy
         helper = WfStep(x, y, env_batch=Dt * St, device_id=self.device_id, model=getattr(self, "_model", None))

@@ -71,6 +71,8 @@ int check_parent(ext_base* x, const char* what, const char* call) {
     return ext_fail(x, WF_E_UNSUPPORTED, std::string(what) + " a handle with ONE layout: this one holds several layouts (wf_set_layouts / wf_set_layouts_counts)");
   if (!h->types.empty())
     return ext_fail(x, WF_E_UNSUPPORTED, std::string(what) + " one turbine definition: this handle holds several turbine definitions (wf_set_turbine_types)");
+  if (!h->msets.empty())
+    return ext_fail(x, WF_E_UNSUPPORTED, std::string(what) + " one wake model: this handle holds wake-model parameter sets per farm (wf_set_model_sets)");
   return call ? check_wind(x, call) : WF_OK;
 }
 

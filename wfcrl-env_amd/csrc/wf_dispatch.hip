@@ -770,7 +770,8 @@ int launch_step(wf_handle* h, const float* yaw, float* power, float* wspd, float
   // the farms with WF_RISK_THRUST_UNITY — a thrust coefficient above 0.995, where float32 carries no bound at all
   // (wf_kernel_common.h: table_ct) — and that only when the handle's thrust table gets there (nrel_5MW does not: nothing
   // is enqueued for it).
-  const int mode = h->types.empty() ? h->resolve_mode : 2;  // (several turbine definitions: the float64 kernels solve every farm)
+  const int mode = every_farm_f64(h) ? 2 : h->resolve_mode;  // (several turbine definitions / parameter sets: the float64 kernels solve every farm)
+  if (!h->msets.empty()) { int rc = modelset_check(h); if (rc != WF_OK) return rc; }
   int mask = mode == 1 ? 0x1F : 0;
   if (mode == 0) {
     double ct_max = 0.0;
@@ -822,6 +823,7 @@ int launch_step(wf_handle* h, const float* yaw, float* power, float* wspd, float
     ra.power_mw = ea->power_mw;
   }
   h->rconsts.N = h->N;
+  if (!h->msets.empty()) return modelset_launch(h, &ra);  // (include/wfmodelset.h: with or without turbine definitions)
   if (!h->types.empty()) {
     ra.tab64 = h->d_tab64_mt; ra.n_types = (int)h->types.size(); ra.type_of = h->d_type_of; ra.type_consts = h->d_type_consts;
     WF_HIP(h, wfk_launch_resolve_mt(&h->rconsts, &ra, h->B, 1, h->d_flags_raw, h->n_cu, h->stream));

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/wfstep.h"
+#include "../../include/wfmodelset.h"
 #include "wf_device.h"
 #include "wf_resolve.h"
 
@@ -214,6 +215,17 @@ struct wf_handle {
   double* d_tab64_mt = nullptr;    // [n_types][3][WF_TABLE_PAD]
   double* d_type_consts = nullptr; // [n_types][1 + WF_TYPE_CONSTS]
   int* d_type_of = nullptr;        // [N]
+  // wake-model parameter sets per farm (include/wfmodelset.h; host side: modelset/wf_modelset.hip): every farm is solved by the
+  // float64 kernels of wf_resolve_ms.hip, whatever resolve_mode says
+  std::vector<wf_model_set> msets;  // empty: the one model
+  std::vector<int> mset_of;         // [mset_batch] set of each farm
+  int mset_batch = 0;               // env_batch the assignment was given for (another batch: the sets must be set again)
+  bool msets_dirty = false;         // the device table below is older than the sets, the model or the turbine count
+  WfResolveConsts* d_msets = nullptr;  // [msets.size()]
+  int* d_mset_of = nullptr;            // [B]
+  double* d_mset_type = nullptr;       // [1 + WF_TYPE_CONSTS]: the model as the one turbine definition of a handle without definitions
+  int* d_mset_type_of = nullptr;       // [N] zeros
+  int mset_waves = 0;               // waves per farm of the kernel behind the last step with sets (4 / 1)
 };
 
 namespace wfi {
@@ -255,6 +267,12 @@ void free_batch(wf_handle* h);
 // wf_model.hip
 void init_default_table();
 int build_consts(wf_handle* h);
+void fill_resolve_consts(const wf_model_params& m, int N, int n_table, WfResolveConsts* out);
+// modelset/wf_modelset.hip
+inline bool every_farm_f64(const wf_handle* h) { return !h->types.empty() || !h->msets.empty(); }  // (mode 2 whatever resolve_mode says)
+int modelset_check(wf_handle* h);   // the sets fit the batch (ahead of a step)
+int modelset_launch(wf_handle* h, WfResolveArgs* ra);  // uploads a stale table, then the float64 solve of every farm
+void modelset_free(wf_handle* h);
 // wf_dispatch.hip
 int pick_variant(const wf_handle* h, int N, int B);
 int pick_ll(const wf_handle* h, int N, int B);  // (G << 4) | S, 0 = keep wf_step_kernel

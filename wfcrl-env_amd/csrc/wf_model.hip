@@ -44,6 +44,65 @@ namespace wfi {
 
 void init_default_table() { std::call_once(g_tab_once, fill_default_table); }  // concurrent wf_create calls
 
+// the float64 solve's constants (wf_resolve.h) of a model: what build_consts puts into h->rconsts, and — the same code, hence the
+// same bytes for the same fields — what a wake-model parameter set of include/wfmodelset.h becomes (modelset/wf_modelset.hip)
+void fill_resolve_consts(const wf_model_params& m, int N, int n_table, WfResolveConsts* out) {
+  WfResolveConsts& r = *out;
+  const double D = m.rotor_diameter, HH = m.hub_height, R = D / 2, eps = m.eps_gain * D, eps2 = eps * eps;
+  const double off[3] = {-D / 4, 0.0, D / 4};
+  double shearf[3];
+  for (int k = 0; k < 3; ++k) shearf[k] = std::pow((HH + off[k]) / HH, m.shear);
+  const double m_eps = m.num_eps;
+  const double q = D / 4.0;
+  const double hs[3] = {HH + R, HH - R, HH};
+  const double vel_top = std::pow((HH + R) / HH, m.shear), vel_bot = std::pow((HH - R) / HH, m.shear);
+  r.N = N; r.n_table = n_table;
+  r.sw_steer = m.enable_secondary_steering ? 1 : 0; r.sw_yar = m.enable_yaw_added_recovery ? 1 : 0;
+  r.sw_tv = m.enable_transverse_velocities ? 1 : 0;
+  r.D = D; r.HH = HH; r.TSR = m.tsr; r.amb = m.ambient_ti; r.eps2 = eps2; r.num_eps = m.num_eps; r.sqrt2 = std::sqrt(2.0);
+  r.inv_D = 1.0 / D; r.inv_TSR = 1.0 / m.tsr; r.inv_eps2 = 1.0 / eps2;
+  r.uinf1 = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    r.off[k] = off[k];
+    r.shearf[k] = shearf[k];
+    r.uinf1 += shearf[k];
+    const double z = HH + off[k];
+    const double dudz1 = m.shear * std::pow(1.0 / HH, m.shear) * std::pow(z, m.shear - 1.0);
+    const double lm = m.kappa * z / (1.0 + m.kappa * z / (D / 8.0));
+    r.nu1[k] = lm * lm * std::fabs(dudz1);
+  }
+  r.uinf1 /= 3.0;
+  r.vel_top = vel_top; r.vel_bot = vel_bot;
+  double kk[3] = {0, 0, 0};
+  for (int v = 0; v < 3; ++v)
+    for (int k = 0; k < 3; ++k) {
+      const double zc = HH + off[k] - hs[v] + m_eps;
+      for (int j = 0; j < 3; ++j) {
+        const double yL = off[j] + m_eps;
+        const double rr = yL * yL + zc * zc;
+        kk[v] += zc / (2.0 * M_PI * rr) * (1.0 - std::exp(-rr / eps2)) / 9.0;
+      }
+    }
+  r.mirror_core = 0;
+  for (int mm = -3; mm <= 3; ++mm) {
+    const double zc = mm * q + m_eps, zm = 2.0 * HH + mm * q + m_eps;
+    r.zc[mm + 3] = zc; r.zc2[mm + 3] = zc * zc; r.ezc[mm + 3] = std::exp(-zc * zc / eps2);
+    r.zm7[mm + 3] = zm; r.zm2[mm + 3] = zm * zm; r.ezm7[mm + 3] = std::exp(-zm * zm / eps2);
+    if (r.ezm7[mm + 3] >= 1.0e-17) r.mirror_core = 1;
+  }
+  r.k_top = kk[0]; r.k_bot = kk[1]; r.k_core = kk[2];
+  r.alpha = m.alpha; r.beta = m.beta; r.ka = m.ka; r.kb = m.kb; r.ad = m.ad; r.bd = m.bd; r.dm = m.dm;
+  r.defl_alpha = m.defl_alpha; r.defl_beta = m.defl_beta; r.defl_ka = m.defl_ka; r.defl_kb = m.defl_kb;
+  r.e0c1 = 3.0 * std::exp(1.0 / 12.0); r.e0c2 = 3.0 * std::exp(1.0 / 3.0);
+  r.near_c = m.near_wake_c * D;
+  r.ch_constant = m.ch_constant; r.ch_ai = m.ch_ai; r.ch_amb_pow = std::pow(m.ambient_ti, m.ch_initial); r.ch_down = m.ch_downstream;
+  r.gch_gain = m.gch_gain; r.overlap_thr = m.overlap_thresh;
+  const double vr = m.veer * M_PI / 180.0;
+  r.cos_veer = std::cos(vr); r.cos2_veer = std::cos(vr) * std::cos(vr); r.sin2_veer = std::sin(vr) * std::sin(vr);
+  r.sin_2veer = std::sin(2.0 * vr);
+  r.rho_ref = m.ref_density; r.dens_cbrt = std::pow(m.air_density / m.ref_density, 1.0 / 3.0); r.pP3 = m.pP / 3.0;
+}
+
 int build_consts(wf_handle* h) {
   const wf_model_params& m = h->model;
   const int n = (int)h->tws.size();
@@ -177,52 +236,7 @@ int build_consts(wf_handle* h) {
   c.max_probe = max_probe;
   // the float64 solve (wf_resolve.hip): the same model in double
   {
-    WfResolveConsts& r = h->rconsts;
-    r.N = h->N; r.n_table = n;
-    r.sw_steer = m.enable_secondary_steering ? 1 : 0; r.sw_yar = m.enable_yaw_added_recovery ? 1 : 0;
-    r.sw_tv = m.enable_transverse_velocities ? 1 : 0;
-    r.D = D; r.HH = HH; r.TSR = m.tsr; r.amb = m.ambient_ti; r.eps2 = eps2; r.num_eps = m.num_eps; r.sqrt2 = std::sqrt(2.0);
-    r.inv_D = 1.0 / D; r.inv_TSR = 1.0 / m.tsr; r.inv_eps2 = 1.0 / eps2;
-    r.uinf1 = 0.0;
-    for (int k = 0; k < 3; ++k) {
-      r.off[k] = off[k];
-      r.shearf[k] = shearf[k];
-      r.uinf1 += shearf[k];
-      const double z = HH + off[k];
-      const double dudz1 = m.shear * std::pow(1.0 / HH, m.shear) * std::pow(z, m.shear - 1.0);
-      const double lm = m.kappa * z / (1.0 + m.kappa * z / (D / 8.0));
-      r.nu1[k] = lm * lm * std::fabs(dudz1);
-    }
-    r.uinf1 /= 3.0;
-    r.vel_top = vel_top; r.vel_bot = vel_bot;
-    double kk[3] = {0, 0, 0};
-    for (int v = 0; v < 3; ++v)
-      for (int k = 0; k < 3; ++k) {
-        const double zc = HH + off[k] - hs[v] + m_eps;
-        for (int j = 0; j < 3; ++j) {
-          const double yL = off[j] + m_eps;
-          const double rr = yL * yL + zc * zc;
-          kk[v] += zc / (2.0 * M_PI * rr) * (1.0 - std::exp(-rr / eps2)) / 9.0;
-        }
-      }
-    r.mirror_core = 0;
-    for (int mm = -3; mm <= 3; ++mm) {
-      const double zc = mm * q + m_eps, zm = 2.0 * HH + mm * q + m_eps;
-      r.zc[mm + 3] = zc; r.zc2[mm + 3] = zc * zc; r.ezc[mm + 3] = std::exp(-zc * zc / eps2);
-      r.zm7[mm + 3] = zm; r.zm2[mm + 3] = zm * zm; r.ezm7[mm + 3] = std::exp(-zm * zm / eps2);
-      if (r.ezm7[mm + 3] >= 1.0e-17) r.mirror_core = 1;
-    }
-    r.k_top = kk[0]; r.k_bot = kk[1]; r.k_core = kk[2];
-    r.alpha = m.alpha; r.beta = m.beta; r.ka = m.ka; r.kb = m.kb; r.ad = m.ad; r.bd = m.bd; r.dm = m.dm;
-    r.defl_alpha = m.defl_alpha; r.defl_beta = m.defl_beta; r.defl_ka = m.defl_ka; r.defl_kb = m.defl_kb;
-    r.e0c1 = 3.0 * std::exp(1.0 / 12.0); r.e0c2 = 3.0 * std::exp(1.0 / 3.0);
-    r.near_c = m.near_wake_c * D;
-    r.ch_constant = m.ch_constant; r.ch_ai = m.ch_ai; r.ch_amb_pow = std::pow(m.ambient_ti, m.ch_initial); r.ch_down = m.ch_downstream;
-    r.gch_gain = m.gch_gain; r.overlap_thr = m.overlap_thresh;
-    const double vr = m.veer * M_PI / 180.0;
-    r.cos_veer = std::cos(vr); r.cos2_veer = std::cos(vr) * std::cos(vr); r.sin2_veer = std::sin(vr) * std::sin(vr);
-    r.sin_2veer = std::sin(2.0 * vr);
-    r.rho_ref = m.ref_density; r.dens_cbrt = std::pow(m.air_density / m.ref_density, 1.0 / 3.0); r.pP3 = m.pP / 3.0;
+    fill_resolve_consts(m, h->N, n, &h->rconsts);
     std::vector<double> t64(3 * WF_TABLE_PAD, 0.0);
     for (int i = 0; i < n; ++i) { t64[i] = h->tws[i]; t64[WF_TABLE_PAD + i] = h->tct[i]; t64[2 * WF_TABLE_PAD + i] = pwv[i]; }
     if (!h->d_tab64) {
@@ -267,6 +281,7 @@ int build_consts(wf_handle* h) {
     if (et != hipSuccess) return fail(h, WF_E_HIP, std::string("turbine definitions upload: ") + hipGetErrorString(et));
   }
   h->model_dirty = false;
+  h->msets_dirty = true;  // (include/wfmodelset.h: the sets' table follows the model and the turbine count, rebuilt before the next step)
   return WF_OK;
 }
 

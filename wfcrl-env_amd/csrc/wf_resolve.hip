@@ -55,14 +55,47 @@
 #define RES_PART 1
 #endif
 #define WF_RES_GRID_PER_CU 4  // persistent one-wave blocks per CU: one per SIMD (WF_RES_OCC)
+// Wake-model parameter sets per farm (include/wfmodelset.h: wf_set_model_sets): a third compilation, RES_MS = 1 on top of
+// RES_MT = 1 (wf_resolve_ms.hip, wf_resolve4_ms.hip).  Its kernels take a table of model constants and a set index per farm;
+// at the top of the farm loop the block copies its farm's WfResolveConsts into the `c` member of its LDS struct, and everything
+// the solve reads from the by-value argument inside the farm loop in the other builds (inflow, ambient TI, veer and mirror-core
+// switches, the level rule) is read from that copy.  The builds without sets are the code they always were: RES_CF expands to
+// the kernel argument and the extra parameters to nothing.
+#ifndef RES_MS
+#define RES_MS 0
+#endif
+#if RES_MS && !RES_MT
+#error "RES_MS builds on RES_MT (a handle without turbine definitions runs with one definition made from its model)"
+#endif
+#if RES_MS
+#define RES_CF(S, arg) ((S).c)
+#define RES_MS_KPARAMS , const WfResolveConsts* __restrict__ ms_sets, const int* __restrict__ ms_set_of
+#define RES_MS_HPARAMS , const WfResolveConsts* ms_sets, const int* ms_set_of
+#define RES_MS_ARGS , ms_sets, ms_set_of
+#define RES_SET_WORDS ((int)(sizeof(WfResolveConsts) / 8))
+static_assert(sizeof(WfResolveConsts) % 8 == 0 && sizeof(WfResolveConsts) / 8 <= 256, "a set is copied in 8-byte words, one pass of 256 threads");
+#else
+#define RES_CF(S, arg) (arg)
+#define RES_MS_KPARAMS
+#define RES_MS_HPARAMS
+#define RES_MS_ARGS
+#endif
 #if RES_MT
 #define RES_NT WF_MAX_TYPES
+#if RES_MS
+#define wf_list_all_kernel wf_list_all_ms_kernel
+#define wf_resolve_kernel wf_resolve_ms_kernel
+#define wf_resolve4_kernel wf_resolve4_ms_kernel
+#define wfk_launch_resolve wfk_launch_resolve_ms
+#define wfk_launch_resolve4 wfk_launch_resolve4_ms
+#else
 #define wf_list_all_kernel wf_list_all_mt_kernel
 #define wf_resolve_kernel wf_resolve_mt_kernel
 #define wf_resolve4_kernel wf_resolve4_mt_kernel
 #define wfk_launch_resolve wfk_launch_resolve_mt
 #if RES_PART == 2
 #define wfk_launch_resolve4 wfk_launch_resolve4_mt
+#endif
 #endif
 #define RES_TY(t) (reinterpret_cast<const int*>(res_dyn + (t) * RES_TS + 35)[0])  // (the record's first padding word)
 #define RES_TOFS(ty) ((ty) * WF_TABLE_PAD)
@@ -622,7 +655,7 @@ __device__ unsigned long long wf_res4_fstamp[16];  // inside the level's transve
 #define RES4_LACC(k, a, b) stl[k] += (b) - (a)
 #endif
 #if RES_PART == 1
-__global__ __launch_bounds__(64, WF_RES_OCC) void wf_resolve_kernel(const WfResolveConsts c_arg, const WfResolveArgs a_arg, int n_pad, int min_count) {
+__global__ __launch_bounds__(64, WF_RES_OCC) void wf_resolve_kernel(const WfResolveConsts c_arg, const WfResolveArgs a_arg, int n_pad, int min_count RES_MS_KPARAMS) {
   const int lane = threadIdx.x;
   const int N = c_arg.N;
   if (lane == 0) {
@@ -636,6 +669,13 @@ __global__ __launch_bounds__(64, WF_RES_OCC) void wf_resolve_kernel(const WfReso
   for (int li = blockIdx.x; li < n_list; li += gridDim.x) {
     const int b = a_arg.list[li];
     RES_T(t_farm);
+#if RES_MS
+    {  // the farm's own constants -> R.c (one wave: its LDS operations execute in order, the previous farm's reads are behind it)
+      const unsigned long long* src = reinterpret_cast<const unsigned long long*>(ms_sets + ms_set_of[b]);
+      unsigned long long* dst = reinterpret_cast<unsigned long long*>(&R.c);
+      for (int k = lane; k < RES_SET_WORDS; k += 64) dst[k] = src[k];
+    }
+#endif
     __syncthreads();  // (one wave: orders the constants / the previous farm's last reads before the new contents)
     RES_PHASE_FENCE;
     const WfResolveArgs& a = R.a;
@@ -647,8 +687,11 @@ __global__ __launch_bounds__(64, WF_RES_OCC) void wf_resolve_kernel(const WfReso
       const double ws = a.ws[(size_t)b * a.wind_stride];
       double wd = fmod(a.wd[(size_t)b * a.wind_stride], 360.0);  // reference interface.py:664 (Python's %)
       if (wd < 0.0) wd += 360.0;
-      R.ws = ws; R.wd = wd; R.Uinf = ws * c_arg.uinf1;  // inflow [A.2]
-      for (int k = 0; k < 3; ++k) { R.Uinit[k] = ws * c_arg.shearf[k]; R.dec_a[k] = 4.0 * (c_arg.nu1[k] * ws) / R.Uinf; }
+      R.ws = ws; R.wd = wd; R.Uinf = ws * RES_CF(R, c_arg).uinf1;  // inflow [A.2]
+      for (int k = 0; k < 3; ++k) { R.Uinit[k] = ws * RES_CF(R, c_arg).shearf[k]; R.dec_a[k] = 4.0 * (RES_CF(R, c_arg).nu1[k] * ws) / R.Uinf; }
+#if RES_MS
+      R.veer_on = R.c.sin2_veer != 0.0; R.mcore = R.c.mirror_core;  // (per farm: a set may turn the veer on, its shear moves nothing else here)
+#endif
     }
     for (int t = lane; t < N; t += 64) {
       const double g = (double)yaw_b[a.gidx[gofs + t]];
@@ -661,7 +704,7 @@ __global__ __launch_bounds__(64, WF_RES_OCC) void wf_resolve_kernel(const WfReso
 #endif
 #pragma unroll 1
       for (int q = 0; q < 27; ++q) res_dyn[t * RES_TS + 5 + q] = 0.0;
-      for (int j = 0; j < 3; ++j) res_dyn[t * RES_TS + 32 + j] = c_arg.amb;
+      for (int j = 0; j < 3; ++j) res_dyn[t * RES_TS + 32 + j] = RES_CF(R, c_arg).amb;
     }
     __syncthreads();
     for (int t = lane; t < N; t += 64) {  // start of the turbine's x' tie group (sorted order: ties are contiguous)
@@ -679,7 +722,7 @@ __global__ __launch_bounds__(64, WF_RES_OCC) void wf_resolve_kernel(const WfReso
       RES_T(t0);
       res_source_begin(i);
       RES_T(t1);
-      if (c_arg.sw_tv) res_transverse_pass();
+      if (RES_CF(R, c_arg).sw_tv) res_transverse_pass();
       RES_T(t2);
       res_source_finish(i);
       RES_T(t3);
@@ -1715,7 +1758,7 @@ __device__ unsigned long long wf_res_lvl_stat[8];
 // found (seen_host; the first launch is a narrow one).  Should a wide launch meet a list beyond two blocks per CU after all, waves
 // 4-7 return at once (the registers of a wave that has ended are NOT handed to a new block while its block lives — measured: + 1.64
 // — so this is damage control for one step, not a way to launch).
-__global__ __launch_bounds__(64 * RES4_MAX_WAVES, WF_RES4_OCC) RES4_WAVES_ATTR void wf_resolve4_kernel(const WfResolveConsts c_arg, const WfResolveArgs a_arg, int n_pad, int max_count, int levels, int helpers_max) {
+__global__ __launch_bounds__(64 * RES4_MAX_WAVES, WF_RES4_OCC) RES4_WAVES_ATTR void wf_resolve4_kernel(const WfResolveConsts c_arg, const WfResolveArgs a_arg, int n_pad, int max_count, int levels, int helpers_max RES_MS_KPARAMS) {
   const int tid = threadIdx.x;
   const int N = c_arg.N;
   const int n_list = *a_arg.count;
@@ -1754,11 +1797,26 @@ __global__ __launch_bounds__(64 * RES4_MAX_WAVES, WF_RES4_OCC) RES4_WAVES_ATTR v
   }
   res_stage_tables(R4, c_arg, a_arg, tid < 256 ? tid : 0x40000000, 256);
   for (int li = blockIdx.x; li < n_list; li += gridDim.x) {
+#if RES_MS
+    __syncthreads();  // the previous farm's last readers of ITS constants are done (first farm: thread 0's copy of the argument is in)
+    if (tid < RES_SET_WORDS)  // the farm's own constants -> R4.c: one coalesced pass, ordered by the barrier below
+      reinterpret_cast<unsigned long long*>(&R4.c)[tid] = reinterpret_cast<const unsigned long long*>(ms_sets + ms_set_of[a_arg.list[li]])[tid];
+#endif
     __syncthreads();  // the constants are in place / the previous farm's last readers are done
     RES_PHASE_FENCE;
     const WfResolveArgs& a = R4.a;
     if (tid == 0) {
       const int b = a_arg.list[li];
+#if RES_MS
+      {  // what the other builds derive from the argument once per launch: the veer and mirror-core switches, the level rule
+        const WfResolveConsts& cf = R4.c;
+        R4.veer_on = cf.sin2_veer != 0.0; R4.mcore = cf.mirror_core;
+        const double ky = fmax(cf.ka, cf.defl_ka) * 0.3 + fmax(cf.kb, cf.defl_kb);
+        const double s0 = fmax(0.35355339059327379 * cf.D, 0.70710678118654752 * cf.near_c);
+        R4.lvl_a = 0.35 * cf.D + 8.6 * s0;
+        R4.lvl_b = 8.6 * ky + 0.15;
+      }
+#endif
       const double ws = a.ws[(size_t)b * a.wind_stride];
       double wd = fmod(a.wd[(size_t)b * a.wind_stride], 360.0);  // reference interface.py:664 (Python's %)
       if (wd < 0.0) wd += 360.0;
@@ -2017,7 +2075,7 @@ extern int g_res_levels, g_res_helpers;
 // launched when `launch & 1` (the caller decides: always for a device-side count, for `all` when B fits); `launch & 2`: the list
 // is every farm of the batch (its length is known: B)
 extern "C" hipError_t wfk_launch_resolve4(const WfResolveConsts* c, const WfResolveArgs* a, int B, int n_cu, int launch, int* max4_out,
-                                          int any_count, hipStream_t s) {
+                                          int any_count, hipStream_t s RES_MS_HPARAMS) {
   const int n_pad = (c->N + 1) & ~1;  // (keeps the int arrays behind the doubles aligned)
   const size_t dyn4 = (RES4_DYN_BYTES(n_pad) + 15) & ~(size_t)15;
   if (g_res_levels < 0) { const char* e = getenv("WF_RES_LEVELS"); g_res_levels = e ? atoi(e) : 1; }
@@ -2055,27 +2113,32 @@ extern "C" hipError_t wfk_launch_resolve4(const WfResolveConsts* c, const WfReso
   const int grid4 = B < max4 ? B : max4;
   // any_count: this launch is the only one behind the step — its persistent blocks walk a list of any length
   hipLaunchKernelGGL(wf_resolve4_kernel, dim3(grid4), dim3(wide ? 64 * RES4_MAX_WAVES : 256), dyn4, s, *c, *a, n_pad,
-                     any_count ? 0x7fffffff : max4, levels, helpers_max);
+                     any_count ? 0x7fffffff : max4, levels, helpers_max RES_MS_ARGS);
   return hipGetLastError();
 }
 #endif  // RES_PART == 2
 
 #if RES_PART == 1
-#if RES_MT
+#if RES_MT && !RES_MS
 #define wfk_launch_resolve4 wfk_launch_resolve4_mt
 #endif
 extern int g_res_policy;
+#if RES_MS
+// waves per farm of the kernel that served the last launch with parameter sets (4: the four-wave kernel, 1: the one-wave kernel)
+static int g_res_ms_waves = 0;
+extern "C" int wfk_resolve_ms_last_waves() { return g_res_ms_waves; }
+#endif
 extern "C" hipError_t wfk_launch_resolve4(const WfResolveConsts* c, const WfResolveArgs* a, int B, int n_cu, int launch, int* max4_out,
-                                          int any_count, hipStream_t s);
+                                          int any_count, hipStream_t s RES_MS_HPARAMS);
 extern "C" hipError_t wfk_launch_resolve(const WfResolveConsts* c, const WfResolveArgs* a, int B, int all, int* raw_flags,
-                                         int n_cu, hipStream_t s) {
+                                         int n_cu, hipStream_t s RES_MS_HPARAMS) {
   hipError_t e = hipSuccess;
   if (all) {
     hipLaunchKernelGGL(wf_list_all_kernel, dim3((B + 255) / 256), dim3(256), 0, s, a->flags, B, a->list, a->count, raw_flags);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   int max4 = 0;
-  if ((e = wfk_launch_resolve4(c, a, B, n_cu, all ? 2 : 0, &max4, 0, s)) != hipSuccess) return e;
+  if ((e = wfk_launch_resolve4(c, a, B, n_cu, all ? 2 : 0, &max4, 0, s RES_MS_ARGS)) != hipSuccess) return e;
   // ONE launch behind a step (round 6): the four-wave kernel serves a flagged list of ANY length — its persistent blocks walk the
   // list, up to max4 farms resident at once.  With level stages it is the faster kernel at every count (2 011 flagged HornsRev2
   // farms: + 1.07 ms against the one-wave kernel's + 1.62, profiles/r06_four_wave_always_ab.txt), and an empty list costs one
@@ -2088,8 +2151,11 @@ extern "C" hipError_t wfk_launch_resolve(const WfResolveConsts* c, const WfResol
   // wind has none and is 25 % faster on the one-wave kernel: profiles/r06_mode2_ab.txt)
   const bool all4 = all && c->N >= 16 && !both;
   const bool only4 = (!all || all4) && max4 > 0 && !both;
+#if RES_MS
+  g_res_ms_waves = (only4 || B <= max4) ? 4 : 1;
+#endif
   if (max4 > 0 && (!all || B <= max4 || all4)) {
-    if ((e = wfk_launch_resolve4(c, a, B, n_cu, all ? 3 : 1, &max4, only4 ? 1 : 0, s)) != hipSuccess) return e;
+    if ((e = wfk_launch_resolve4(c, a, B, n_cu, all ? 3 : 1, &max4, only4 ? 1 : 0, s RES_MS_ARGS)) != hipSuccess) return e;
   }
   if (only4) return hipSuccess;
   if (!all || B > max4) {
@@ -2102,7 +2168,7 @@ extern "C" hipError_t wfk_launch_resolve(const WfResolveConsts* c, const WfResol
     const int per_cu_grid = all ? 4 * WF_RES_GRID_PER_CU : WF_RES_GRID_PER_CU;
     const int grid = B < n_cu * per_cu_grid ? B : n_cu * per_cu_grid;
     const size_t dyn = sizeof(double) * RES_TS * (size_t)n_pad + sizeof(int) * (size_t)n_pad;
-    hipLaunchKernelGGL(wf_resolve_kernel, dim3(grid), dim3(64), dyn, s, *c, *a, n_pad, max4 + 1);
+    hipLaunchKernelGGL(wf_resolve_kernel, dim3(grid), dim3(64), dyn, s, *c, *a, n_pad, max4 + 1 RES_MS_ARGS);
   }
   return hipGetLastError();
 }

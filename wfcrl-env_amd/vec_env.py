@@ -32,7 +32,7 @@ class VecWindFarmEnv:
                  device_id: int = 0, model: dict = None, return_torch: bool = True, backend=None,
                  wind_sampling: str = "host", reuse_buffers: bool = True, wind_direction_step: float = None,
                  actuation_budget: float = 0.1, kernel_choice: dict = None, risk_resolve: bool = None,
-                 layouts: dict = None, wind_process: dict = None):
+                 layouts: dict = None, wind_process: dict = None, model_randomization: dict = None):
         controls = {"yaw": (-40, 40, 5)} if controls is None else dict(controls)
         if list(controls) != ["yaw"]:
             raise ValueError(f"Cannot control {list(controls)}. Interface HipFlorisInterface only allows for the "
@@ -123,6 +123,22 @@ class VecWindFarmEnv:
                 raise ValueError(f"unknown wind_process parameter(s): {sorted(unknown)}")
             self._wind_process = {k: float(v) for k, v in wp.items()}
         self._generated = None  # what regenerates the running episode: seed, T, ws0, wd0 (get_state)
+        # model_randomization: wake-model parameter sets per farm (include/wfmodelset.h; backend.WfStep.set_model_sets) —
+        #   dict(ranges={field: (lo, hi), ...}, n_sets=min(B, 256), resample="reset" | "once")   n_sets sets drawn uniformly in
+        #       the ranges (other fields: the model), each farm assigned a set by a draw; at construction ("once") or at
+        #       every reset(seed) ("reset"), from a NumPy generator of their OWN seeded by (seed, a fixed tag): the wind
+        #       stream of _sample_wind is the one it always was
+        #   dict(sets=..., set_of=...)   given explicitly
+        # COST: every farm is then solved by the float64 kernels on every step.  The observation is unchanged; env.model_sets /
+        # env.model_set_of expose what is in force.  None (the default) changes nothing.
+        self._model_rand = None
+        if model_randomization is not None:
+            self._model_rand = self._check_model_randomization(model_randomization, self.num_envs)
+            mr = self._model_rand
+            if "sets" in mr:
+                self.fi.set_model_sets(mr["sets"], mr["set_of"])
+            elif mr["resample"] == "once":
+                self._draw_model_sets(mr.get("seed"))
         # an episode whose wind changes from step to step: a file series or a generated one
         self._playing = self._series is not None or self._wind_process is not None
         self._num_iter = 0
@@ -140,6 +156,60 @@ class VecWindFarmEnv:
         self._const = {}
 
     # -- helpers ------------------------------------------------------------------------------------
+    MODEL_RANDOMIZATION_TAG = 0x6D736574  # "mset": the second word of the seed of the sets' own generator
+
+    @staticmethod
+    def _check_model_randomization(mr, B) -> dict:
+        """Validated copy of a model_randomization argument (needs no device)."""
+        from . import _lib
+
+        if not isinstance(mr, dict):
+            raise ValueError("model_randomization must be a dict: (ranges[, n_sets, resample, seed]) or (sets[, set_of])")
+        mr = dict(mr)
+        if "sets" in mr:
+            unknown = set(mr) - {"sets", "set_of"}
+            if unknown:
+                raise ValueError(f"model_randomization: give either (sets, set_of) or (ranges, n_sets, resample): {sorted(unknown)}")
+            mr.setdefault("set_of", None)
+            return mr
+        unknown = set(mr) - {"ranges", "n_sets", "resample", "seed"}
+        if unknown or "ranges" not in mr:
+            raise ValueError(f"model_randomization: unknown key(s) {sorted(unknown)}; give ranges={{field: (lo, hi)}}")
+        ranges = {}
+        for k, v in dict(mr["ranges"]).items():
+            if k not in _lib._MODEL_SET_FIELDS:
+                raise ValueError(f"model_randomization: unknown model-set field(s): ['{k}'] (a set may change: {list(_lib._MODEL_SET_FIELDS)})")
+            lo, hi = float(v[0]), float(v[1])
+            if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+                raise ValueError(f"model_randomization: range of {k} must be finite with lo <= hi")
+            ranges[k] = (lo, hi)
+        n_sets = int(mr.get("n_sets", min(B, 256)))
+        if not 1 <= n_sets <= B:
+            raise ValueError("model_randomization: n_sets must be in 1..env_batch")
+        resample = mr.get("resample", "reset")
+        if resample not in ("reset", "once"):
+            raise ValueError("model_randomization: resample must be 'reset' or 'once'")
+        return {"ranges": ranges, "n_sets": n_sets, "resample": resample, "seed": mr.get("seed")}
+
+    def _draw_model_sets(self, seed):
+        """n_sets sets uniform in the ranges and a set per farm, from a generator of their own: (seed, tag)."""
+        mr = self._model_rand
+        s = int(seed) if seed is not None else int(np.random.randint(0, 2**31 - 1))
+        rng = np.random.default_rng([s, self.MODEL_RANDOMIZATION_TAG])
+        sets = {k: rng.uniform(lo, hi, mr["n_sets"]) for k, (lo, hi) in sorted(mr["ranges"].items())}
+        set_of = rng.integers(0, mr["n_sets"], self.num_envs).astype(np.int32)
+        self.fi.set_model_sets(sets, set_of)
+
+    @property
+    def model_sets(self):
+        """The parameter sets in force: dict of float64 arrays of length S (None without model_randomization)."""
+        return None if self._model_rand is None else self.fi.model_sets()[0]
+
+    @property
+    def model_set_of(self):
+        """The set of each farm, int32 [env_batch] (None without model_randomization)."""
+        return None if self._model_rand is None else self.fi.model_sets()[1]
+
     def _sample_wind(self, seed, options):
         rng = np.random.default_rng(seed)
         B = self.num_envs
@@ -222,6 +292,8 @@ class VecWindFarmEnv:
     def reset(self, seed=None, options=None):
         """Samples one wind per env, zeroes the env state, runs the warm-up solve(s) at yaw = 0 and returns
         the start observation (clipped to the observation space like the reference's, mdp.py:263-266)."""
+        if self._model_rand is not None and self._model_rand.get("resample") == "reset":
+            self._draw_model_sets(seed)
         if self._series is not None:
             # time-series mode: requested / sampled wind is ignored (interface.py:588-600); every farm starts at a
             # random row (interface.py:516-518), then each solve consumes one row
@@ -767,6 +839,9 @@ class VecWindFarmEnv:
         st = {**self.fi.env_get_state(), "wind_speed": ws, "wind_direction": wd, "num_iter": self._num_iter,
               "shaper_ref": None if self._shaper_ref is None else np.asarray(
                   self._shaper_ref.cpu() if hasattr(self._shaper_ref, "cpu") else self._shaper_ref).copy()}
+        if self._model_rand is not None:  # wake-model parameter sets per farm and their assignment
+            sets, set_of = self.fi.model_sets()
+            st["model_sets"] = {"sets": sets, "set_of": set_of}
         if self._series is not None:  # a time-series episode: one cursor per farm (include/wfseries.h)
             cur = self.fi.series_state()
             st.update(series_t=cur["t"], series_start=cur["start"], series_prev_pending=cur["prev_pending"])
@@ -786,6 +861,10 @@ class VecWindFarmEnv:
         if ("generated_wind" in state) != (self._wind_process is not None):
             raise ValueError("the state of a generated wind episode resumes on an env with a wind_process, and only there: "
                              + ("this env has none" if self._wind_process is None else "this state holds no generated wind"))
+        if ("model_sets" in state) != (self._model_rand is not None):
+            raise ValueError("the state of an env with model_randomization resumes on an env with model_randomization, and only there")
+        if self._model_rand is not None:  # (before the env state: the sets do not touch it, and the next step needs them)
+            self.fi.set_model_sets(state["model_sets"]["sets"], state["model_sets"]["set_of"])
         if self._wind_process is not None:
             # the same seed, distribution, process and tick 0 give the same bits; then the cursor
             g = state["generated_wind"]
