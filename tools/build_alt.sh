@@ -5,6 +5,7 @@
 # and linked with the product's other objects as they stand, the on-the-fly part included.  The replay's switches:
 #   -DWF_LL_TRANS_WAIT=0|1|2   where the transverse pass waits for its pair records (compiler / once per source / once per slot)
 #   -DWF_LL_COLD_DEPTH=1|2     cold records one / two near steps ahead
+#   -DWF_LL_BLOCK_EDGE=0|1|2|3 a block's first-chunk wait: bit 0 index / yaw prefetches behind it, bit 1 the previous block's output stores behind it
 #   -DWF_EXP_NOCOLD            timing only, wrong results: the deficit pass without its cold-record loads
 #   LICM=1 tools/build_alt.sh ...   leaves machine LICM on for the unit
 # Time with the library copied over wfcrl-env_amd/libwfstep.so (bench.py) or tools/time_variants.py build/alt/lib_*.so on the

@@ -45,7 +45,12 @@ print(f"{name} B={B} {w.kernel_info()}  {ms:.3f} ms with stamps; {nw} waves, {to
 for k in range(4):
     print(f"  {names[k]:14s} {buf[k] / nw:10.0f} cycles  {buf[k] / buf[4]:.3f}")
 print(f"  {'  of replay: transverse pass':28s} {buf[11] / nw:10.0f} cycles  {buf[11] / buf[4]:.3f}   deficit pass + chunk test {(buf[0] - buf[11]) / nw:10.0f}  {(buf[0] - buf[11]) / buf[4]:.3f}")
-print(f"  {'prologue/rest':14s} {(buf[4] - sum(buf[:4])) / nw:10.0f} cycles  {(buf[4] - sum(buf[:4])) / buf[4]:.3f}")
+rest = buf[4] - sum(buf[:4])
+print(f"  {'prologue/rest':14s} {rest / nw:10.0f} cycles  {rest / buf[4]:.3f}")
+# (the block start taken apart — WF_LL_BLOCK_EDGE in wf_kernels_ll.hip: stamp 14 around a block's first-chunk wait, 15 around its
+# top: register zeroing, index and yaw fetch, sincos of the yaw; what is left: kernel prologue, flush of kept outputs, loop set-up)
+print(f"  {'  of it: first-chunk wait':28s} {buf[14] / nw:10.0f} cycles  {buf[14] / buf[4]:.3f}   block top {buf[15] / nw:10.0f}  {buf[15] / buf[4]:.3f}"
+      f"   the rest {(rest - buf[14] - buf[15]) / nw:10.0f}  {(rest - buf[14] - buf[15]) / buf[4]:.3f}")
 print("  own-source step, cycles per source (the stamps themselves add ~10 %):")
 for k, nm in zip(range(6, 11), ["A state + broadcasts", "B cbrt, Ct lookup, induction", "C transverse pass in the block", "D steering, deflection/deficit constants, log store", "E deficit / TI pass in the block"]):
     print(f"    {nm:52s} {buf[k] / nw / N:8.0f}")

@@ -35,6 +35,9 @@
 //     (lds_dma16, wf_kernel_common.h: inline assembly the compiler's wait-count bookkeeping does not see), so nothing is waited for
 //     at the first LDS read of an iteration any more (rounds 2-4: the builtin made every iteration start with s_waitcnt vmcnt(0));
 //     the kernel waits where the data is needed — wf_dma_wait() in front of the chunk's closing barrier and at a block's first chunk.
+//   * a block's outputs (two-slot table-path unit, WF_LL_BLOCK_EDGE below) are computed where the block ends but STORED behind the
+//     next block's first-chunk wait (the last block's behind the block loop): that wait is vmcnt(0) on an in-order counter, and
+//     stores issued in front of it made every block start wait for the acknowledgements of up to 4 S scattered stores per lane.
 //   * A wind per farm (TAB = false): no pair table — the transverse pass is evaluated on the fly from the farm's own float64
 //     coordinates (apply_fly), same log, one loop; wf_set_wind sorts the launch slots by direction so that the farms of a
 //     wave lie within a fraction of a degree and the wave-uniform skips take.
@@ -65,9 +68,10 @@
 #ifndef WF_LL_PART
 #define WF_LL_PART 0
 #endif
-// Three switches of the replay of logged sources (table path); none changes an operation or the order of a sum, only where
-// loads are issued and waited for.  The defaults are what ships: the two-slot unit (part 1) with the chunk wait stated and
-// one wait per slot, every other kernel as it was.  A/B builds: tools/build_alt.sh; figures: profiles/replay_waits_ab.txt.
+// Four switches of the replay of logged sources and of the block edge (table path); none changes an operation or the order of a
+// sum, only where loads and stores are issued and waited for.  The defaults are what ships: the two-slot unit (part 1) with the
+// chunk wait stated, one wait per slot and a block's output stores behind the next block's first-chunk wait, every other kernel
+// as it was.  A/B builds: tools/build_alt.sh; figures: profiles/replay_waits_ab.txt, profiles/block_edge_ab.txt.
 //
 // WF_LL_CHUNK_VMCNT — the chunk's closing wait (wf_dma_wait(): vmcnt(0) in inline assembly, which the compiler does not
 // read) stated to the compiler as well: 0 = no, 1 = yes.  The deficit pass's LAST step fetches a cold record nobody reads
@@ -97,7 +101,25 @@
 #ifndef WF_LL_COLD_DEPTH
 #define WF_LL_COLD_DEPTH 1
 #endif
-static_assert(WF_LL_TRANS_WAIT >= 0 && WF_LL_TRANS_WAIT <= 2 && (WF_LL_COLD_DEPTH == 1 || WF_LL_COLD_DEPTH == 2), "replay A/B switches");
+// WF_LL_BLOCK_EDGE — what a block's FIRST chunk waits for (table path; figures: profiles/block_edge_ab.txt).  That chunk starts
+// with wf_dma_wait(), vmcnt(0), for the hot records staged behind the previous block's sources.  The counter is in order and
+// counts everything: the 2 S index / yaw prefetches issued at the block's top a few instructions earlier (a whole global-memory
+// latency) and the acknowledgements of the previous block's up to 4 S scattered output stores stand in front of it.  Two bits,
+// switched separately:
+//   1 = the block's index and yaw prefetches (oidx_n2, yaw_nx: read one block later) are issued BEHIND the wait;
+//   2 = the output phase keeps what it would store in registers (7 S floats and the caller's index per lane; V, W, the deficit
+//       sums and TI are dead by then) and the stores are issued behind the NEXT block's first-chunk wait — behind the block loop
+//       for the last block.  The reward sums and the risk flags stay where they were.
+// With either bit the wait is also stated to the compiler (as WF_LL_CHUNK_VMCNT does), so that no load it still believes in
+// flight puts an s_waitcnt vmcnt into the first chunk's loops.  With both bits the wave's only outstanding vector-memory
+// operations at the wait are the hot-record transfers.  0 = the listing without the switch, instruction for instruction.
+// Ships: 2 in part 1 (HornsRev1 x 65 536 -1.7 %; 248 instead of 234 VGPRs in the headline shape, no scratch).  Bit 1 alone
+// measured -0.6 %, bit 1 on top of bit 2 -0.1 %, both inside the spread: not shipped.  Part 2 (one-slot families) untouched.
+#ifndef WF_LL_BLOCK_EDGE
+#define WF_LL_BLOCK_EDGE (WF_LL_PART == 1 ? 2 : 0)
+#endif
+static_assert(WF_LL_TRANS_WAIT >= 0 && WF_LL_TRANS_WAIT <= 2 && (WF_LL_COLD_DEPTH == 1 || WF_LL_COLD_DEPTH == 2) &&
+              WF_LL_BLOCK_EDGE >= 0 && WF_LL_BLOCK_EDGE <= 3, "replay A/B switches");
 
 namespace {
 
@@ -734,7 +756,7 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
   float psum = 0.0f, lsum = 0.0f;  // per-lane partial sums for the fused reward
   const int n_real = ga.n_real ? ga.n_real[env] : N;  // turbines the farm really has (padded layouts: WfGroupArgs)
 #ifdef WF_LL_STAMP
-  unsigned long long st_acc[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   WF_T(st_begin);
 #endif
   int q = 0;                        // running chunk index (LDS buffer q & 1)
@@ -934,7 +956,29 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
   }
 #pragma unroll
   for (int p = 0; p < S; ++p) yaw_nx[p] = load_yaw(oidx_nx[p]);
+#if WF_LL_BLOCK_EDGE
+  // WF_LL_BLOCK_EDGE (at the top; everything of it stands between #if, so that 0 is the source without the switch): the
+  // prefetches behind the first chunk's wait / the outputs of a block kept for the next one's
+  constexpr bool EDGE_PF = TAB && (WF_LL_BLOCK_EDGE & 1), EDGE_ST = TAB && (WF_LL_BLOCK_EDGE & 2);
+  [[maybe_unused]] float d_power[S] = {}, d_ws[S] = {}, d_wd[S] = {};
+  [[maybe_unused]] float4 d_load[S] = {};
+  [[maybe_unused]] int d_o[S];  // the caller's index of the turbine whose outputs are kept; -1: nothing to store
+#pragma unroll
+  for (int p = 0; p < S; ++p) d_o[p] = -1;
+  auto flush_outputs = [&]() {
+#pragma unroll
+    for (int p = 0; p < S; ++p) {
+      if (d_o[p] < 0) continue;
+      const size_t oo = yofs + d_o[p];
+      if (o_power) o_power[oo] = d_power[p];
+      if (o_ws) o_ws[oo] = d_ws[p];
+      if (o_wd) o_wd[oo] = d_wd[p];
+      if (o_load) reinterpret_cast<float4*>(o_load)[oo] = d_load[p];
+    }
+  };
+#endif
   for (int J = 0; J < nblk; ++J) {
+    WF_T(st_top0);
     int tt[S];
     bool tvalid[S];
     float yaw_t[S], sg_t[S], cg_t[S];
@@ -958,10 +1002,17 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
       oidx[p] = oidx_nx[p];
       yaw_t[p] = yaw_nx[p];
       oidx_nx[p] = oidx_n2[p];
-      oidx_n2[p] = gidx[gofs + min(tt[p] + 2 * GS, N - 1)];
-      yaw_nx[p] = load_yaw(oidx_nx[p]);
+#if WF_LL_BLOCK_EDGE
+      if constexpr (!EDGE_PF)
+#endif
+      {
+        oidx_n2[p] = gidx[gofs + min(tt[p] + 2 * GS, N - 1)];
+        yaw_nx[p] = load_yaw(oidx_nx[p]);
+      }
       sincos_yaw(yaw_t[p] * kDeg2Rad, sg_t[p], cg_t[p]);  // this lane's turbines: source constants (own block), power output
     }
+    WF_T(st_top1);
+    WF_ACC(15, st_top0, st_top1);
 
     const int first_own = J * GS;                 // sources [0, first_own) come from the log, [first_own, n_src) are this block's
     const int n_src = min(N, first_own + GS);
@@ -1218,11 +1269,40 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
       if (own_ok) spec_J = own_ok[(size_t)grp * nblk + J] != 0;
     }
 
+#if WF_LL_BLOCK_EDGE
+    // The block's first-chunk wait, in front of the chunk loop (inside it, what is issued behind the wait would be live through
+    // every chunk: the kept outputs cost the replay sixteen registers it does not have), and what the wait need not cover behind
+    // it: the indices two blocks and the yaw one block ahead, read at the next block's top; the previous block's outputs.
+    if constexpr (TAB) {
+      if (first_own > 0) {
+        WF_T(st_w0);
+        wf_dma_wait();
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // the same wait on the compiler's books: vmcnt 0, expcnt 7, lgkmcnt 15
+        WF_T(st_w1);
+        WF_ACC(14, st_w0, st_w1);
+      }
+      if constexpr (EDGE_PF) {
+#pragma unroll
+        for (int p = 0; p < S; ++p) {
+          oidx_n2[p] = gidx[gofs + min(tt[p] + 2 * GS, N - 1)];
+          yaw_nx[p] = load_yaw(oidx_nx[p]);
+        }
+      }
+      if constexpr (EDGE_ST) flush_outputs();
+    }
+#endif
     for (int cq = 0; cq < n_chunks; ++cq, ++q) {
       if constexpr (TAB) {
         // (a block's first chunk: its hot records were staged behind the previous block's sources, in front of that block's
         // outputs — long landed; waited for here, before this chunk's own transfers are issued)
-        if (cq == 0 && first_own > 0) wf_dma_wait();
+#if !WF_LL_BLOCK_EDGE
+        if (cq == 0 && first_own > 0) {
+          WF_T(st_w0);
+          wf_dma_wait();
+          WF_T(st_w1);
+          WF_ACC(14, st_w0, st_w1);
+        }
+#endif
         if (cq + 1 < n_chunks || J + 1 < nblk) stage_chunk(q + 1);  // lands in the other buffer while this chunk is consumed
         // the next chunk's hot records, when it has logged sources and is a chunk of THIS block (everything it replays was
         // logged by earlier blocks); the first chunk of the NEXT block replays this block's sources too: staged behind them
@@ -1457,6 +1537,9 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
     // ---- outputs [A.4] of block J --------------------------------------------------------------
 #pragma unroll
     for (int p = 0; p < S; ++p) {
+#if WF_LL_BLOCK_EDGE
+      if constexpr (EDGE_ST) d_o[p] = -1;
+#endif
       if (!tvalid[p]) continue;
       const int o = oidx[p];
       float U[9], m3 = 0.0f, mu = 0.0f, mv = 0.0f, mw = 0.0f, adir = 0.0f;
@@ -1518,6 +1601,16 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
       const bool real = o < n_real;  // (a placeholder of a padded layout: zeros out, nothing into the reward)
       psum += real ? pwr : 0.0f;
       lsum += real ? (l.x + l.y) + (l.z + l.w) : 0.0f;
+#if WF_LL_BLOCK_EDGE
+      if constexpr (EDGE_ST) {
+        // (kept for flush_outputs behind the next block's first-chunk wait: the values as they would be stored)
+        d_o[p] = env_ok ? o : -1;
+        d_power[p] = real ? (ea.power_mw ? pwr * 1.0e-6f : pwr) : 0.0f;
+        d_ws[p] = real ? wsp : 0.0f;
+        d_wd[p] = real ? wd - adir * (kRad2Deg / 9.0f) : 0.0f;
+        d_load[p] = real ? l : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      } else
+#endif
       if (env_ok) {
         const size_t oo = yofs + o;
         if (o_power) o_power[oo] = real ? (ea.power_mw ? pwr * 1.0e-6f : pwr) : 0.0f;
@@ -1529,12 +1622,15 @@ __global__ __launch_bounds__(64 * WPB, ((S == 1 && !OCC2) ? 3 : 2) * 4 / WPB) vo
     WF_T(st_f);
     WF_ACC(3, st_e, st_f);
   }  // J
+#if WF_LL_BLOCK_EDGE
+  if constexpr (EDGE_ST) flush_outputs();  // the last block's outputs
+#endif
 #ifdef WF_LL_STAMP
   if (lane == 0) {
     st_acc[4] = __builtin_readcyclecounter() - st_begin;
     for (int k = 0; k < 5; ++k) atomicAdd(&wf_ll_stamp[k], st_acc[k]);
     atomicAdd(&wf_ll_stamp[5], 1ull);
-    for (int k = 6; k < 14; ++k) atomicAdd(&wf_ll_stamp[k], st_acc[k]);  // 12, 13: blocks that ran their sources as a stage / whose check failed  // parts of an own-source step; 11: transverse pass of the replay (tools/ll_stamps.py)
+    for (int k = 6; k < 16; ++k) atomicAdd(&wf_ll_stamp[k], st_acc[k]);  // 12, 13: blocks that ran their sources as a stage / whose check failed  // parts of an own-source step; 11: transverse pass of the replay; 14, 15: a block's first-chunk wait / its top (tools/ll_stamps.py)
   }
 #endif
 
