@@ -974,6 +974,67 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the plan kernel as the runtime reports them."""
         return self._plan().kernel_info()
 
+    # -- wake-model calibration: parameter sets scored against and fitted to measured powers (include/wfcalib.h) ----
+    def _calib(self) -> "_Calib":
+        """The handle's calib object; created on first use, destroyed in close() before the handle."""
+        co = getattr(self, "_calib_obj", None)
+        if co is None:
+            co = self._calib_obj = _Calib(self)
+        return co
+
+    def rated_power(self) -> float:
+        """The largest power of the handle's table, watts: 1/2 rho_ref A Cp eta ws^3 — the default `scale` of a calibration."""
+        m = getattr(self, "_model", None) or default_model()
+        ws, cp = np.asarray(m["table_ws"], np.float64), np.asarray(m["table_cp"], np.float64)
+        area = np.pi * (0.5 * float(m["rotor_diameter"])) ** 2
+        return float(np.max(0.5 * float(m["ref_density"]) * area * cp * float(m["gen_eff"]) * ws ** 3))
+
+    def model_loss(self, sets, ws, wd, yaw, power, weight=None, scale=None, out=None, want=("loss", "best"), max_eval_farms=65536):
+        """The losses of candidate wake-model parameter sets against measured turbine powers (include/wfcalib.h:
+        wf_calib_score; the project's own definition, PARITY UNPINNED beyond the oracle).  G problems of C conditions:
+          sets    the candidates, as set_model_sets takes them: a list of S dicts or a dict of arrays [S], shared by all
+                  problems — or a list of G such lists / a dict of arrays [G][S], a batch per problem
+          ws, wd  (G, C) float64 the wind of each condition;  yaw (G, C, N) float32;  power (G, C, N) float64, watts
+          weight  (G, C, N) float64 >= 0, or None: ones; 0 masks a turbine that was off-line or pads a problem: the power
+                  under it may be anything, NaN included.  A NaN power under a positive weight is refused in NumPy arrays; in
+                  torch tensors (not read on the host) it makes every loss of its problem +inf, and `best` is then 0
+          scale   watts, > 0; None: rated_power()
+          want    of "loss" (G, S) float64 — sum_c sum_t w ((P_dev - P) / scale)^2, float64 in a fixed order —, "best" (G,)
+                  int32 — the lowest loss, the lowest index among equals —, "row_power" (G, S, C, N) float32
+          max_eval_farms  rows the evaluator handle may hold, S C per problem: more problems run in chunks
+        The leading G axis is optional: without it (ws of shape (C,)) the outputs have none either.  The handle supplies the
+        model's other fields, its layout and its turbine; it needs no wind and is not changed.  Deterministic: two runs and
+        any chunking give the same bits.  With torch tensors (the observations or out) the call only enqueues work on
+        torch's current stream and returns torch CUDA tensors."""
+        return self._calib().score(sets, ws, wd, yaw, power, weight, scale, out, want, max_eval_farms)
+
+    def calibrate_model(self, ws, wd, yaw, power, bounds, init=None, candidates=64, elites=8, sigma=(0.25, 0.12, 0.06, 0.03),
+                        seed=0, weight=None, scale=None, max_eval_farms=65536):
+        """Fits wake-model fields to measured turbine powers on the device (include/wfcalib.h: wf_calib_fit; the project's
+        own definition, PARITY UNPINNED beyond the oracle): the cross-entropy method of plan_actions over the eighteen
+        fields of a parameter set, scored by model_loss.  One glue kernel stands between two evaluator steps; the
+        candidates' constants are written on the device and nothing is read back in between.
+          ws .. power, weight, scale   the observations, as model_loss takes them
+          bounds      {field: (lo, hi)}: the fields to fit; every other field is FIXED at init
+          init        the starting set(s): a dict, or a list of G dicts / dict of arrays [G]; missing fields and None: the
+                      handle's model.  Inside the bounds
+          candidates  S >= 3;  elites  1 <= E <= S
+          sigma       one width per iteration (at most 16), a fraction of hi - lo, non-negative
+          seed        of the draws; a problem's draws depend on (seed, its index, iteration, candidate, field) alone
+        Returns a dict: "best_set" and "mean" as {field: array (G,)} — what set_model_sets accepts —, "best_loss",
+        "init_loss" (G,), "history" (G, I) the winner's loss per iteration, "fit_power" (G, C, N) float32 the best set's
+        powers, "n_invalid" (G,) int32 candidates that left the model's domain (their loss is +inf).  best_loss <= init_loss:
+        candidate 0 is the best set so far, at first init.  Without a leading G axis the outputs have none either."""
+        return self._calib().fit(ws, wd, yaw, power, bounds, init, candidates, elites, sigma, seed, weight, scale, max_eval_farms)
+
+    def calib_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last model_loss / calibrate_model {"total_ms", "step_ms", "glue_ms"}."""
+        return self._calib().timing(detail)
+
+    def calib_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the calib kernel as the runtime reports them."""
+        return self._calib().kernel_info()
+
     # -- scenario planner: CEM over action sequences scored over a wind ensemble (include/wfscenplan.h) ----
     def _scenplan(self) -> "_ScenPlan":
         """The handle's scenplan object; created on first use, destroyed in close() before the handle."""
@@ -1440,10 +1501,10 @@ class WfStep:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h,
-            # wfcredit.h, wflookahead.h, wfplan.h, wfretgrad.h, wfrollout.h, wfrollscen.h — the rollout and the scenario-rollout
+            # wfcredit.h, wflookahead.h, wfplan.h, wfretgrad.h, wfrollout.h, wfrollscen.h, wfcalib.h — the rollout and the scenario-rollout
             # object, created on the rose object, before it)
             for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rollout_obj", "_rollscen_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
-                         "_lookahead_obj", "_scenario_obj", "_plan_obj", "_scenplan_obj", "_retgrad_obj", "_windgen_obj"):
+                         "_lookahead_obj", "_scenario_obj", "_plan_obj", "_scenplan_obj", "_retgrad_obj", "_calib_obj", "_windgen_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
                     ext.close()
@@ -2294,6 +2355,150 @@ class _Plan(_Ext):
         self._call("run", H, K, E, int(sg.size), sg.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF, float(gamma), wptr, mptr, n, fptr,
                    *[p.get(k) for k in self.OUTPUTS], int(on_device))
         return {k: out[k] for k in spec}
+
+
+class _Calib(_Ext):
+    """The `wf_calib` object of a WfStep handle (include/wfcalib.h)."""
+
+    NAME = "calib"
+    KERNELS = ("advance",)
+    FIT_OUTPUTS = ("best_set", "best_loss", "init_loss", "history", "mean", "fit_power", "n_invalid")
+
+    def _sets(self, sets, n_outer):
+        """(ctypes ModelSet array, S, per_problem) of a `sets` argument: [S] shared, or [n_outer][S] a batch per problem."""
+        base = self._w.model_set_from_model()
+        fields = _lib._MODEL_SET_FIELDS
+        per = False
+        if isinstance(sets, dict):
+            cols = {k: np.asarray(v, dtype=np.float64) for k, v in sets.items()}
+            if any(v.ndim == 2 for v in cols.values()):
+                if any(v.shape != (n_outer, next(iter(cols.values())).shape[1]) for v in cols.values()):
+                    raise ValueError("model sets per problem: every field needs an array (G, S)")
+                per = True
+                arr, n = normalize_model_sets({k: v.reshape(-1) for k, v in cols.items()}, base)
+                S = n // n_outer
+            else:
+                arr, S = normalize_model_sets(sets, base)
+        else:
+            sets = list(sets)
+            if sets and isinstance(sets[0], (list, tuple)):
+                if len(sets) != n_outer or len({len(r) for r in sets}) != 1:
+                    raise ValueError("model sets per problem: G lists of the same length S")
+                per = True
+                S = len(sets[0])
+                arr, _ = normalize_model_sets([d for r in sets for d in r], base)
+            else:
+                arr, S = normalize_model_sets(sets, base)
+        n = S * n_outer if per else S
+        c = (_lib.ModelSet * n)()
+        for k in range(n):
+            for f in fields:
+                setattr(c[k], f, float(arr[f][k]))
+        return c, S, per
+
+    def _observations(self, ws, wd, yaw, power, weight, out):
+        """The observations as contiguous arrays with their G axis: (ws, wd, yaw, power, weight, G, C, squeeze, on_device, like)."""
+        N = self._w.num_turbines
+        given = [ws, wd, yaw, power, weight] + list((out or {}).values())
+        on_device = any(_is_torch(v) for v in given)
+        like = None
+        if on_device:
+            import torch
+
+            self._w._follow_torch_stream()
+            like = next(v for v in given if _is_torch(v))
+
+            def conv(a, dt):
+                if a is None:
+                    return None
+                if not _is_torch(a):
+                    a = torch.as_tensor(np.asarray(a, dt), device=like.device)
+                assert a.is_cuda
+                return a.to(getattr(torch, np.dtype(dt).name)).contiguous()
+        else:
+            def conv(a, dt):
+                return None if a is None else np.ascontiguousarray(a, dtype=dt)
+        ws, wd, power, weight = conv(ws, np.float64), conv(wd, np.float64), conv(power, np.float64), conv(weight, np.float64)
+        yaw = conv(yaw, np.float32)
+        squeeze = ws.ndim == 1
+        if squeeze:
+            ws, wd, yaw, power = ws[None], wd[None], yaw[None], power[None]
+            weight = None if weight is None else weight[None]
+        if ws.ndim != 2:
+            raise ValueError("ws must be (G, C) or (C,): the wind speed of every condition")
+        G, C_ = int(ws.shape[0]), int(ws.shape[1])
+        for name, a, shape in (("wd", wd, (G, C_)), ("yaw", yaw, (G, C_, N)), ("power", power, (G, C_, N)), ("weight", weight, (G, C_, N))):
+            if a is not None and tuple(a.shape) != shape:
+                raise ValueError(f"{name} must be {'(G, C)' if len(shape) == 2 else '(G, C, num_turbines)'}, here {shape}: got {tuple(a.shape)}")
+        return ws, wd, yaw, power, weight, G, C_, squeeze, on_device, like
+
+    @staticmethod
+    def _ptr(a, on_device):
+        return None if a is None else (a.data_ptr() if on_device else a.ctypes.data)
+
+    def score(self, sets, ws, wd, yaw, power, weight, scale, out, want, max_eval_farms):
+        w = self._w
+        N = w.num_turbines
+        want = (want,) if isinstance(want, str) else tuple(want)
+        names = ("loss", "best", "row_power")
+        if not want or any(k not in names for k in want):
+            raise ValueError("want must name loss, best and / or row_power")
+        ws, wd, yaw, power, weight, G, C_, squeeze, on_device, like = self._observations(ws, wd, yaw, power, weight, out)
+        c, S, per = self._sets(sets, G)
+        scale = w.rated_power() if scale is None else float(scale)
+        self._call("config", int(max_eval_farms or 0))
+        shapes = {"loss": ((G, S), np.float64), "best": ((G,), np.int32), "row_power": ((G, S, C_, N), np.float32)}
+        spec = {k: shapes[k] for k in names if k in want}
+        if out is not None and squeeze:
+            out = {k: v[None] for k, v in out.items()}
+        out, ptrs = self._outputs(out, spec, on_device, like)
+        p = dict(zip(spec, ptrs))
+        self._call("score", G, C_, S, c, int(per), *[self._ptr(a, on_device) for a in (ws, wd, yaw, power, weight)], scale,
+                   *[p.get(k) for k in names], int(on_device))
+        return {k: (out[k][0] if squeeze else out[k]) for k in spec}
+
+    def fit(self, ws, wd, yaw, power, bounds, init, candidates, elites, sigma, seed, weight, scale, max_eval_farms):
+        w = self._w
+        N = w.num_turbines
+        fields = _lib._MODEL_SET_FIELDS
+        ws, wd, yaw, power, weight, G, C_, squeeze, on_device, like = self._observations(ws, wd, yaw, power, weight, None)
+        unknown = sorted(set(bounds) - set(fields))
+        if unknown:
+            raise ValueError(f"unknown model-set field(s) in bounds: {unknown} (a set may change: {list(fields)})")
+        if init is None:
+            init = [{}]
+        elif isinstance(init, dict) and not any(np.ndim(v) for v in init.values()):
+            init = [init]
+        ic, n_init, _ = self._sets(init, 1)
+        if n_init not in (1, G):
+            raise ValueError("init: one starting set, or one per problem")
+        lo = np.array([getattr(ic[0], f) for f in fields], np.float64)
+        hi = lo.copy()
+        for k in range(1, n_init):  # a field that is not fitted is fixed at init: it must then be one value for all problems
+            for j, f in enumerate(fields):
+                if f not in bounds and getattr(ic[k], f) != lo[j]:
+                    raise ValueError(f"init: {f} is not in bounds, so it is fixed — at ONE value for all problems")
+        for f, (a, b) in bounds.items():
+            lo[fields.index(f)], hi[fields.index(f)] = float(a), float(b)
+        sg = np.ascontiguousarray(np.atleast_1d(sigma), dtype=np.float64).reshape(-1)
+        S, E, I = int(candidates), int(elites), int(sg.size)
+        scale = w.rated_power() if scale is None else float(scale)
+        self._call("config", int(max_eval_farms or 0))
+        sets_t = np.dtype([(f, np.float64) for f in fields])
+        shapes = {"best_set": ((G,), sets_t), "best_loss": ((G,), np.float64), "init_loss": ((G,), np.float64),
+                  "history": ((G, I), np.float64), "mean": ((G,), sets_t), "fit_power": ((G, C_, N), np.float32),
+                  "n_invalid": ((G,), np.int32)}
+        # (a set goes through the C boundary as eighteen float64: (G, 18) arrays here, dicts of fields for the caller)
+        raw = {k: (((G, len(fields)), np.float64) if d is sets_t else (s, d)) for k, (s, d) in shapes.items()}
+        res, ptrs = self._outputs(None, raw, on_device, like)
+        self._call("fit", G, C_, S, E, I, sg.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF, lo.ctypes.data, hi.ctypes.data, ic,
+                   int(n_init == G and G > 1), *[self._ptr(a, on_device) for a in (ws, wd, yaw, power, weight)], scale, *ptrs,
+                   int(on_device))
+        ret = {}
+        for k in self.FIT_OUTPUTS:
+            v = res[k][0] if squeeze else res[k]
+            ret[k] = {f: v[..., j] for j, f in enumerate(fields)} if k in ("best_set", "mean") else v
+        return ret
 
 
 class _ScenPlan(_Ext):

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../wf_handle.h"
+#include "wf_modelset.h"
 
 extern "C" hipError_t wfk_launch_resolve_ms(const WfResolveConsts* c, const WfResolveArgs* a, int B, int all, int* raw_flags, int n_cu,
                                             hipStream_t s, const WfResolveConsts* ms_sets, const int* ms_set_of);
@@ -65,6 +66,35 @@ static int modelset_upload(wf_handle* h) {
   return WF_OK;
 }
 
+bool modelset_validate(const wf_model_set* sets, int n, std::string* why) {
+  for (int k = 0; k < n; ++k) {
+    const wf_model_set& s = sets[k];
+#define X(f) if (!std::isfinite(s.f)) { *why = "parameter set " + std::to_string(k) + ": " #f " is not finite"; return false; }
+    WF_MS_FIELDS(X)
+#undef X
+    if (!(s.ambient_ti > 0.0)) { *why = "parameter set " + std::to_string(k) + ": ambient_ti must be > 0"; return false; }
+    const struct { double v; const char* name; } positive[] = {  // what wf_set_model asks of these fields
+        {s.alpha, "alpha"}, {s.defl_alpha, "deflection alpha"}, {s.ka * s.ambient_ti + s.kb, "ka*TI + kb"},
+        {s.defl_ka * s.ambient_ti + s.defl_kb, "deflection ka*TI + kb"}, {s.ch_constant, "crespo_hernandez.constant"}};
+    for (const auto& q : positive)
+      if (!(q.v > 0.0)) { *why = "parameter set " + std::to_string(k) + ": must be > 0: " + q.name; return false; }
+  }
+  return true;
+}
+
+int modelset_device_table(wf_handle* h, WfResolveConsts** tab) {
+  int rc = modelset_check(h);
+  if (rc != WF_OK) return rc;
+  // (what a step does first: the model's own constants — building them marks the sets' table stale, so a table handed out before
+  // them would be built over again by the first step)
+  if (h->model_dirty && h->N > 0 && (rc = build_consts(h)) != WF_OK) return rc;
+  if (h->msets_dirty || !h->d_msets) {
+    if ((rc = modelset_upload(h)) != WF_OK) return rc;
+  }
+  *tab = h->d_msets;
+  return WF_OK;
+}
+
 int modelset_launch(wf_handle* h, WfResolveArgs* ra) {
   int rc = modelset_check(h);
   if (rc != WF_OK) return rc;
@@ -104,18 +134,8 @@ int wf_set_model_sets(wf_handle* h, int n_sets, const wf_model_set* sets, const 
   if (h->B <= 0) return fail(h, WF_E_INVALID, "wf_set_batch must be called first (the parameter sets are assigned per farm)");
   if (n_sets < 1 || n_sets > h->B || !sets) return fail(h, WF_E_INVALID, "parameter sets: 1..env_batch of them");
   if (!set_of && n_sets != h->B) return fail(h, WF_E_INVALID, "parameter sets: without set_of, n_sets must equal env_batch (farm b takes set b)");
-  for (int k = 0; k < n_sets; ++k) {
-    const wf_model_set& s = sets[k];
-#define X(f) if (!std::isfinite(s.f)) return fail(h, WF_E_INVALID, "parameter set " + std::to_string(k) + ": " #f " is not finite");
-    WF_MS_FIELDS(X)
-#undef X
-    if (!(s.ambient_ti > 0.0)) return fail(h, WF_E_INVALID, "parameter set " + std::to_string(k) + ": ambient_ti must be > 0");
-    const struct { double v; const char* name; } positive[] = {  // what wf_set_model asks of these fields
-        {s.alpha, "alpha"}, {s.defl_alpha, "deflection alpha"}, {s.ka * s.ambient_ti + s.kb, "ka*TI + kb"},
-        {s.defl_ka * s.ambient_ti + s.defl_kb, "deflection ka*TI + kb"}, {s.ch_constant, "crespo_hernandez.constant"}};
-    for (const auto& q : positive)
-      if (!(q.v > 0.0)) return fail(h, WF_E_INVALID, "parameter set " + std::to_string(k) + ": must be > 0: " + q.name);
-  }
+  std::string why;
+  if (!modelset_validate(sets, n_sets, &why)) return fail(h, WF_E_INVALID, why);
   if (set_of)
     for (int b = 0; b < h->B; ++b)
       if (set_of[b] < 0 || set_of[b] >= n_sets) return fail(h, WF_E_INVALID, "parameter sets: a farm's set_of entry is outside 0..n_sets-1");

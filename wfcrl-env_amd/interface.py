@@ -330,6 +330,14 @@ class HipFlorisInterface(BaseInterface):
         return {"reward_base": float(r["reward"][0, 0]), "reward_alt": r["reward"][0, 1:].reshape(N, K).copy(),
                 "difference": r["difference"][0].copy()}
 
+    def calibrate_model(self, ws, wd, yaw, power, bounds, **kw):
+        """Fits wake-model fields (ambient_ti, ka, kb, alpha, ...) to measured turbine powers: ws, wd (C,) the wind of C
+        conditions, yaw and power (C, N) what the turbines did and produced under them, bounds {field: (lo, hi)} the fields
+        to fit.  Forwards to backend.WfStep.calibrate_model (include/wfcalib.h; the project's own definition) and returns
+        its dict: best_set, best_loss, init_loss, history, mean, fit_power, n_invalid.  Neither the interface's wind and yaw
+        command nor its model are changed: hand best_set to a new interface's model, or to WfStep.set_model_sets."""
+        return self.fi.calibrate_model(ws, wd, yaw, power, bounds, **kw)
+
     def get_farm_AEP(self, wind_directions, wind_speeds, freq, cut_in_wind_speed=0.001, cut_out_wind_speed=None,
                      yaw_angles=None, no_wake=False, turbine_weights=None):
         """Annual energy production [GWh] over a wind rose, with the argument names FLORIS users know:
