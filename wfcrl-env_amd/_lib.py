@@ -387,15 +387,30 @@ CALIB_ABI = {
     "wf_calib_last_error": (C.c_char_p, [_P]),
 }
 
+# every symbol include/wfpolicy.h declares (closed-loop rollouts of MLP policies): its own table
+POLICY_ABI = {
+    "wf_policy_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "wf_policy_destroy": (C.c_int, [_P]),
+    "wf_policy_config": (C.c_int, [_P, C.c_int, C.c_int]),
+    "wf_policy_set_network": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P]),
+    "wf_policy_run": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_double, C.c_int, _P,
+                                _P, _P, _P, _P, _P, _P, _P, _P, C.c_int]),
+    "wf_policy_set_timing": (C.c_int, [_P, C.c_int]),
+    "wf_policy_last_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "wf_policy_evaluator": (_P, [_P]),
+    "wf_policy_kernel_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "wf_policy_last_error": (C.c_char_p, [_P]),
+}
+
 _lib = None
 
 
 def build(force: bool = False) -> Path:
     """Compile csrc/ into libwfstep.so with hipcc for gfx950 (cross-compiles without a GPU)."""
     srcs = []
-    for d in ("", "ext", "modelset", "probe", "yawopt", "rose", "robust", "grad", "credit", "lookahead", "plan", "series", "rollout", "retgrad", "windgen", "scenario", "scenplan", "calib", "rollscen"):  # csrc/ itself, the extensions' shared layer, the extensions
+    for d in ("", "ext", "modelset", "probe", "yawopt", "rose", "robust", "grad", "credit", "lookahead", "plan", "series", "rollout", "retgrad", "windgen", "scenario", "scenplan", "calib", "policy", "rollscen"):  # csrc/ itself, the extensions' shared layer, the extensions
         srcs += sorted((PKG_DIR / "csrc" / d).glob("*.hip")) + sorted((PKG_DIR / "csrc" / d).glob("*.h"))
-    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfmodelset.h", "wfprobe.h", "wfyawopt.h", "wfrose.h", "wfrobust.h", "wfgrad.h", "wfcredit.h", "wflookahead.h", "wfplan.h", "wfseries.h", "wfrollout.h", "wfretgrad.h", "wfwindgen.h", "wfscenario.h", "wfscenplan.h", "wfcalib.h", "wfrollscen.h")]
+    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfmodelset.h", "wfprobe.h", "wfyawopt.h", "wfrose.h", "wfrobust.h", "wfgrad.h", "wfcredit.h", "wflookahead.h", "wfplan.h", "wfseries.h", "wfrollout.h", "wfretgrad.h", "wfwindgen.h", "wfscenario.h", "wfscenplan.h", "wfcalib.h", "wfpolicy.h", "wfrollscen.h")]
     stale = (not LIB_PATH.exists()) or any(s.stat().st_mtime > LIB_PATH.stat().st_mtime for s in srcs)
     if force or stale:
         subprocess.run(["make", "-j4", "-C", str(PKG_DIR / "csrc")] + (["-B"] if force else []), check=True)
@@ -426,7 +441,7 @@ def load() -> C.CDLL:
             build()
         _share_hip_runtime_with_torch()
         lib = C.CDLL(str(LIB_PATH))
-        for table in (ABI, MODELSET_ABI, PROBE_ABI, YAWOPT_ABI, ROSE_ABI, ROBUST_ABI, GRAD_ABI, CREDIT_ABI, LOOKAHEAD_ABI, PLAN_ABI, SERIES_ABI, ROLLOUT_ABI, RETGRAD_ABI, WINDGEN_ABI, SCENARIO_ABI, SCENPLAN_ABI, CALIB_ABI, ROLLSCEN_ABI):
+        for table in (ABI, MODELSET_ABI, PROBE_ABI, YAWOPT_ABI, ROSE_ABI, ROBUST_ABI, GRAD_ABI, CREDIT_ABI, LOOKAHEAD_ABI, PLAN_ABI, SERIES_ABI, ROLLOUT_ABI, RETGRAD_ABI, WINDGEN_ABI, SCENARIO_ABI, SCENPLAN_ABI, CALIB_ABI, POLICY_ABI, ROLLSCEN_ABI):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
                 fn.restype, fn.argtypes = res, args

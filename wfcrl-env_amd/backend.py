@@ -835,6 +835,54 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the lookahead kernels as the runtime reports them."""
         return self._lookahead().kernel_info()
 
+    # -- closed-loop rollouts of MLP policies (include/wfpolicy.h) ---------------------------------------
+    def _policy(self) -> "_Policy":
+        """The handle's policy object; created on first use, destroyed in close() before the handle."""
+        po = getattr(self, "_policy_obj", None)
+        if po is None:
+            po = self._policy_obj = _Policy(self)
+        return po
+
+    def policy_returns(self, params, spec, horizon, gamma=1.0, wind=None, farms=None, strict=False, max_eval_farms=65536,
+                       want=("returns", "best"), out=None):
+        """What each of K parameter vectors of one small MLP policy earns over the next `horizon` steps of the fused env, in
+        closed loop, from the env state the handle holds, which is read and never changed (include/wfpolicy.h; the project's
+        own definition, PARITY UNPINNED beyond the oracle).  The network observes what the env would show it — yaw, the
+        per-turbine local wind speed and direction of the last solve, the free wind —, so a run is ONE batched step per env
+        step, K rows per farm, with one glue kernel between two steps (reward, observation, network, transition) and no host
+        read.  Round 0 solves the current yaw under the current wind for observation 0; rewards and returns are those of
+        lookahead_returns: feeding "actions"[:, k] to it returns this call's rewards, returns and final_yaw bit for bit.
+          params     (K, P) float32, 1 <= K <= 64 — torch CUDA tensor or NumPy; the same K policies for every farm; a vector
+                     as torch.nn.utils.parameters_to_vector lays out an nn.Sequential of nn.Linear
+          spec       policy.mlp_spec(...) (policy.policy_from_torch returns both)
+          horizon    H, 1 <= H <= 256
+          gamma      discount in [0, 1]
+          wind       (n_farms, H, 2) float64 (speed, direction) the wind step h is solved under; None: the handle's current
+                     wind held over the horizon
+          farms      farm indices (any order), or None: every farm of the batch
+          strict     every row is solved in float64; otherwise the handle's own resolve mode
+          max_eval_farms  rows the evaluator handle may hold, K per farm: longer lists run in chunks
+          want       of "returns" (n, K) float64, "rewards" (n, K, H) float64, "farm_power" (n, K, H) float64 [W], "actions"
+                     (n, K, H, N) float32 — RAW, what env_step or lookahead_returns would be given —, "observations"
+                     (n, K, H, 3 N + 2) float32 — un-normalised, the central lay-out for both kinds —, "final_yaw" (n, K, N)
+                     float32, "gated" (n, K) int32 — (step, turbine) pairs with a closed budget gate —, "best" (n,) int32 —
+                     the lowest index among equal maxima
+          out        dict of tensors / arrays of those names to write into
+        The network's arithmetic is float64 in a fixed order (input i ascending, product and sum rounded separately): with
+        relu and softsign a NumPy loop reproduces the actions bit for bit, with tanh to one float32 ulp.  Step 0 is normalised
+        by the speed the next env_step would normalise by (env_set_prev_wind is read, not consumed).  Deterministic: no
+        floating-point atomics.  With torch tensors (params, wind or out) the call only enqueues work on torch's current
+        stream and returns torch CUDA tensors."""
+        return self._policy().run(params, spec, horizon, gamma, wind, farms, strict, max_eval_farms, want, out)
+
+    def policy_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last policy_returns {"total_ms", "step_ms", "glue_ms"}."""
+        return self._policy().timing(detail)
+
+    def policy_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the policy kernels as the runtime reports them."""
+        return self._policy().kernel_info()
+
     # -- scenario look-ahead: returns of action sequences over a wind ensemble (include/wfscenario.h) ------
     def _scenario(self) -> "_Scenario":
         """The handle's scenario object; created on first use, destroyed in close() before the handle."""
@@ -1501,10 +1549,10 @@ class WfStep:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h,
-            # wfcredit.h, wflookahead.h, wfplan.h, wfretgrad.h, wfrollout.h, wfrollscen.h, wfcalib.h — the rollout and the scenario-rollout
+            # wfcredit.h, wflookahead.h, wfpolicy.h, wfplan.h, wfretgrad.h, wfrollout.h, wfrollscen.h, wfcalib.h — the rollout and the scenario-rollout
             # object, created on the rose object, before it)
             for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rollout_obj", "_rollscen_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
-                         "_lookahead_obj", "_scenario_obj", "_plan_obj", "_scenplan_obj", "_retgrad_obj", "_calib_obj", "_windgen_obj"):
+                         "_lookahead_obj", "_policy_obj", "_scenario_obj", "_plan_obj", "_scenplan_obj", "_retgrad_obj", "_calib_obj", "_windgen_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
                     ext.close()
@@ -2020,6 +2068,83 @@ class _Lookahead(_Ext):
         self._call("run", actions.data_ptr() if on_device else actions.ctypes.data, K, H, wptr, float(gamma), n, fptr,
                    *[p.get(k) for k in self.OUTPUTS], int(on_device))
         return {k: out[k] for k in spec}
+
+
+class _Policy(_Ext):
+    """The `wf_policy` object of a WfStep handle (include/wfpolicy.h)."""
+
+    NAME = "policy"
+    KERNELS = ("transpose", "begin", "advance", "reduce")
+    OUTPUTS = ("returns", "rewards", "farm_power", "actions", "observations", "final_yaw", "gated", "best")
+
+    def _set_network(self, spec):
+        from . import policy as P
+
+        if not isinstance(spec, dict) or any(k not in spec for k in ("kind", "widths", "activation", "final", "out_scale", "shift", "scale")):
+            raise ValueError("spec must be what policy.mlp_spec returns")
+        if spec["kind"] not in P.KINDS or spec["activation"] not in P.ACTIVATIONS or spec["final"] not in P.FINALS:
+            raise ValueError("spec names an unknown kind or activation (policy.mlp_spec)")
+        widths = np.ascontiguousarray(spec["widths"], dtype=np.int32)
+        shift = np.ascontiguousarray(spec["shift"], dtype=np.float64)
+        scale = np.ascontiguousarray(spec["scale"], dtype=np.float64)
+        if shift.shape != (int(widths[0]),) or scale.shape != (int(widths[0]),):
+            raise ValueError("spec: shift and scale must hold one value per input")
+        self._call("set_network", P.KINDS[spec["kind"]], int(widths.size) - 1, widths.ctypes.data, P.ACTIVATIONS[spec["activation"]],
+                   P.FINALS[spec["final"]], int(bool(spec.get("use_freewind", False))), float(spec["out_scale"]),
+                   shift.ctypes.data, scale.ctypes.data)
+
+    def run(self, params, spec, horizon, gamma, wind, farms, strict, max_eval_farms, want, out):
+        w = self._w
+        N = w.num_turbines
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.OUTPUTS for k in want):
+            raise ValueError("want must name returns, rewards, farm_power, actions, observations, final_yaw, gated and / or best")
+        self._set_network(spec)
+        H = int(horizon)
+        self._call("config", int(bool(strict)), int(max_eval_farms or 0))
+        fa, n, fptr = self._farms(farms)
+        on_device = _is_torch(params) or _is_torch(wind) or (out is not None and any(_is_torch(v) for v in out.values()))
+        like = None
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            like = next(v for v in [params, wind] + list((out or {}).values()) if _is_torch(v))
+            if not _is_torch(params):
+                params = torch.as_tensor(np.array(params, np.float32), device=like.device)
+            assert params.is_cuda and params.dtype == torch.float32, "params"
+            params = params.contiguous()
+        else:
+            params = np.ascontiguousarray(params, dtype=np.float32)
+        if len(tuple(params.shape)) == 1:
+            params = params.reshape(1, -1)
+        if len(tuple(params.shape)) != 2:
+            raise ValueError("params must be (K, P): a parameter vector per policy")
+        K, P = int(params.shape[0]), int(params.shape[1])
+        wptr = None
+        if wind is not None:
+            if on_device:
+                if not _is_torch(wind):
+                    wind = torch.as_tensor(np.array(wind, np.float64), device=like.device)
+                assert wind.is_cuda and wind.dtype == torch.float64, "wind"
+                wind = wind.contiguous()
+            else:
+                wind = np.ascontiguousarray(wind, dtype=np.float64)
+            if tuple(wind.shape) != (n, H, 2):
+                raise ValueError("wind must be (n_farms, H, 2): the (speed, direction) every step of the horizon is solved under")
+            wptr = wind.data_ptr() if on_device else wind.ctypes.data
+        shapes = {"returns": ((n, K), np.float64), "rewards": ((n, K, H), np.float64), "farm_power": ((n, K, H), np.float64),
+                  "actions": ((n, K, H, N), np.float32), "observations": ((n, K, H, 3 * N + 2), np.float32),
+                  "final_yaw": ((n, K, N), np.float32), "gated": ((n, K), np.int32), "best": ((n,), np.int32)}
+        if not (1 <= H <= 256 and 1 <= K <= 64):  # (the library names the limit; no output is sized from a refused shape)
+            shapes = {k: ((0,), d) for k, (_, d) in shapes.items()}
+            out = None
+        spec_out = {k: shapes[k] for k in self.OUTPUTS if k in want}
+        out, ptrs = self._outputs(out, spec_out, on_device, like)
+        p = dict(zip(spec_out, ptrs))
+        self._call("run", params.data_ptr() if on_device else params.ctypes.data, K, P, H, wptr, float(gamma), n, fptr,
+                   *[p.get(k) for k in self.OUTPUTS], int(on_device))
+        return {k: out[k] for k in spec_out}
 
 
 class _Scenario(_Ext):

@@ -1,4 +1,4 @@
-// wf_ext.h — the host layer every extension object (probe/, yawopt/, rose/, robust/, grad/, credit/, lookahead/, plan/, rollout/, retgrad/) stands on: the base
+// wf_ext.h — the host layer every extension object (probe/, yawopt/, rose/, robust/, grad/, credit/, lookahead/, plan/, rollout/, retgrad/, policy/) stands on: the base
 // struct with the parent handle, the error text and the event pool; a grow-only device buffer that frees itself; the
 // evaluator — a further handle that follows the parent, configured through the public ABI of include/wfstep.h only; the
 // checks an extension asks of its parent and of a farm list; the staging of a host caller's arrays (staging); event
@@ -149,6 +149,7 @@ int kernel_info(ext_base* x, int n, hipError_t (*attributes)(int, hipFuncAttribu
 struct row_batch {
   dev_buf<float> d_yaw, d_pow, d_load;  // [E][N], [E][N], [E][N][4] (reserved for a policy with loads)
   dev_buf<double> d_wind;               // [2][E] speed, direction
+  dev_buf<float> d_lws, d_lwd;          // [E][N] each: the step's local wind speed and direction (reserved for a policy with local_wind)
   farm_list farms;
 };
 // What differs between the row runs.  Every hook returns a WF_* code (and has set the error text).
@@ -160,6 +161,7 @@ struct row_policy {
   bool by_farm = true;      // an item is a farm: n_items and farms are check_farms'.  Else: no list, *n_items as it is after check
   int strict = 0, max_eval = 65536;
   bool loads = false;         // the step also fills d_load
+  bool local_wind = false;    // the step also fills d_lws and d_lwd, its wind_speed / wind_dir outputs (policy/)
   bool split_always = false;  // four events per chunk on every run, not only under detail
   std::function<int()> check;  // the extension's own checks, after the parent's and the farm list's; may still set rows and *n_items
   std::function<int(int C, int E)> reserve;  // the extension's own buffers, for chunks of C items; names the caller's arrays to `st`
@@ -173,8 +175,10 @@ struct row_policy {
 };
 // The whole run on the parent's stream.  Chunks of C = max_eval / rows items (at most all *n_items), E = C rows evaluator
 // farms.  Per chunk: layout, then wf_set_wind_counts from b.d_wind and one wf_step from b.d_yaw into b.d_pow (and b.d_load),
-// then — under a policy of several rounds — advance and one more wf_step per further round, the wind set ONCE per chunk;
-// then reduce.  The caller's arrays go through `st`: begun after reserve, ended last.  Events: the run's first and last, or
+// then — under a policy of several rounds — advance and one more wf_step per further round; the driver sets the wind once per
+// chunk, and an advance hook that writes another wind into b.d_wind calls wf_set_wind_counts itself before it returns (policy/);
+// then reduce.  With local_wind every step also writes b.d_lws / b.d_lwd.  The caller's arrays go through `st`: begun after
+// reserve, ended last.  Events: the run's first and last, or
 // split per chunk e0 | lay-out e | wind + step e | advance e | step e | ... | reduce e (last_timing's per_chunk layout with
 // 2 rounds + 2: 4 for one round).
 int run_rows(ext_base* x, row_batch& b, evaluator& es, row_policy& k, staging& st, int* n_items, const int* farms);

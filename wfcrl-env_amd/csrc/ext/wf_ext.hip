@@ -170,6 +170,8 @@ int run_rows(ext_base* x, row_batch& b, evaluator& es, row_policy& k, staging& s
   rc = reserve(x, b.d_yaw, en);
   if (rc == WF_OK) rc = reserve(x, b.d_pow, en);
   if (rc == WF_OK && k.loads) rc = reserve(x, b.d_load, 4 * en);
+  if (rc == WF_OK && k.local_wind) rc = reserve(x, b.d_lws, en);
+  if (rc == WF_OK && k.local_wind) rc = reserve(x, b.d_lwd, en);
   if (rc == WF_OK) rc = reserve(x, b.d_wind, 2 * (size_t)E);
   if (rc == WF_OK && farms) rc = reserve(x, b.farms.d, (size_t)n);
   if (rc != WF_OK) return rc;
@@ -183,12 +185,14 @@ int run_rows(ext_base* x, row_batch& b, evaluator& es, row_policy& k, staging& s
     if ((rc = k.layout(sl, E)) != WF_OK) return rc;
     if (split) { rc = record(x); if (rc != WF_OK) return rc; }
     WFX_EV(x, es.ev, wf_set_wind_counts(es.ev, b.d_wind, E, b.d_wind + E, E, 1));
-    WFX_EV(x, es.ev, wf_step(es.ev, b.d_yaw, b.d_pow, nullptr, nullptr, k.loads ? b.d_load.p : nullptr, 1));
+    float* const lws = k.local_wind ? b.d_lws.p : nullptr;
+    float* const lwd = k.local_wind ? b.d_lwd.p : nullptr;
+    WFX_EV(x, es.ev, wf_step(es.ev, b.d_yaw, b.d_pow, lws, lwd, k.loads ? b.d_load.p : nullptr, 1));
     if (split) { rc = record(x); if (rc != WF_OK) return rc; }
-    for (int r = 1; r < k.rounds; ++r) {  // (the rows' wind stays what the lay-out wrote: set once per chunk)
+    for (int r = 1; r < k.rounds; ++r) {  // (the rows' wind stays what the lay-out wrote, unless the advance hook itself sets another)
       if ((rc = k.advance(sl, E, r)) != WF_OK) return rc;
       if (split) { rc = record(x); if (rc != WF_OK) return rc; }
-      WFX_EV(x, es.ev, wf_step(es.ev, b.d_yaw, b.d_pow, nullptr, nullptr, k.loads ? b.d_load.p : nullptr, 1));
+      WFX_EV(x, es.ev, wf_step(es.ev, b.d_yaw, b.d_pow, lws, lwd, k.loads ? b.d_load.p : nullptr, 1));
       if (split) { rc = record(x); if (rc != WF_OK) return rc; }
     }
     if ((rc = k.reduce(sl, E)) != WF_OK) return rc;

@@ -797,6 +797,49 @@ class VecWindFarmEnv:
                                             risk_weight=risk_weight, anchor=anchor, bounds=bounds, filter0=filter0, farms=farms,
                                             strict=strict, max_eval_farms=max_eval_farms, want=want, out=out)
 
+    def policy_returns(self, policy, horizon, gamma=1.0, wind=None, farms=None, strict=False, max_eval_farms=65536,
+                       want=("returns", "best"), kind=None, out_scale=1.0, shift=None, scale=None, use_freewind=False):
+        """What each of K MLP policies earns over the next `horizon` steps under the env's own actuator, in closed loop —
+        the network observing yaw, local wind and free wind after every step —, from the state the env is in: call it BEFORE
+        `step`; the env state is read and never changed (include/wfpolicy.h; backend.WfStep.policy_returns has the
+        arguments; the project's own definition).  `policy` is (params (K, P), spec) as policy.policy_from_torch returns
+        them, or an nn.Sequential (or a list of K of one architecture) of Linear / ReLU / Tanh / Softsign, converted with
+        `kind` ("central" / "shared"), out_scale, shift, scale and use_freewind (policy.policy_from_torch).  Returns the
+        outputs `want` names — "returns", "rewards", "farm_power", "actions", "observations", "final_yaw", "gated", "best" —,
+        torch CUDA tensors when the env returns torch; {"yaw": actions[:, k, h]} is what to give `step` to replay policy k.
+        One batched step per env step, K rows per farm, nothing read back in between.  On a time-series or generated episode
+        the wind of the coming steps is not the one the env holds: wind="series" passes the series' coming rows
+        (`wind_preview(horizon)`), or the caller passes wind=(n_farms, horizon, 2) itself."""
+        from . import policy as P
+
+        series = isinstance(wind, str) and wind == "series"
+        if series and not self._playing:
+            raise ValueError('wind="series" needs a time-series episode: this env has no wind_time_series')
+        if self._playing and wind is None:
+            raise NotImplementedError("policy_returns on a time-series episode needs wind=(n_farms, horizon, 2): the series "
+                                      "tick precedes the step, so the wind of the coming steps is not the one the env holds "
+                                      '(or wind="series": the series\' coming rows)')
+        if type(self.reward_shaper).__name__ != "DoNothingReward":
+            raise ValueError("policy_returns needs the plain reward (DoNothingReward): the return of a shaped reward is "
+                             "not defined here")
+        if isinstance(policy, tuple) and len(policy) == 2 and isinstance(policy[1], dict):
+            params, spec = policy
+        else:
+            if kind is None:
+                raise ValueError('a torch module needs kind="central" or kind="shared"')
+            params, spec = P.policy_from_torch(policy, kind, out_scale=out_scale, shift=shift, scale=scale, use_freewind=use_freewind)
+        if series:
+            wind = self.fi.wind_preview(int(horizon), first=1, farms=farms, as_torch=self.return_torch)[0]
+        if self.return_torch:
+            import torch
+
+            params = self._to_device(params)
+            if wind is not None:  # (float64 all the way: the rows' wind is not rounded to float32)
+                dev = f"cuda:{self.fi.device_id}"
+                wind = wind.to(device=dev, dtype=torch.float64) if isinstance(wind, torch.Tensor) else torch.as_tensor(np.asarray(wind, np.float64), device=dev)
+        return self.fi.policy_returns(params, spec, horizon, gamma=gamma, wind=wind, farms=farms, strict=strict,
+                                      max_eval_farms=max_eval_farms, want=want)
+
     def _series_keyword(self, name, wind, steps):
         """The wind keyword of counterfactual_rewards / lookahead_returns: None or "series"; a time-series episode needs
         "series", any other episode None."""
