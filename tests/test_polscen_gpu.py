@@ -1,0 +1,428 @@
+"""GPU: policy rollouts over a wind ensemble on the device (include/wfpolscen.h) against tests/polscen_ref.py's parts.
+
+A closed loop feeds every step's rounding back into the next observation, so a run is never compared with the reference's
+run and never bounded by the loop's sensitivity.  EACH LINK is checked against the device's OWN upstream values:
+  1. paths: wind_paths has scenario_ref.paths' bits, and scenario_returns on the same handle returns the same bits;
+  2. member m is policy_returns under path m, bit for bit, every output — policy_returns is held to the oracle and to NumPy by
+     tests/test_policy_gpu.py, and this one link carries all of that over;
+  3. the network link directly: policy_ref's network on the device's observations gives the device's actions;
+  4. statistics: scenario_ref.statistics of the device's member returns gives the device's mean, tail mean, score and choice;
+  5. one still member is policy_returns under the wind held;  6. a pending prev-wind speed is neither read nor consumed;
+  7. the same bits from two runs, any chunking, any farm list, host or device arrays;  8. refusals by name;  9. kernel_info;
+  10. the VecWindFarmEnv method.
+Every comparison is of bits, except the tanh cases of link 3: one float32 ulp, include/wfpolicy.h's stated property."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import policy_ref as pr
+import polscen_ref as sr
+import scenario_ref
+
+pytestmark = pytest.mark.gpu
+
+WANT = ("expected_returns", "cvar", "score", "member_returns", "rewards", "farm_power", "wind_paths", "actions", "observations",
+        "final_yaw", "gated", "first_action", "best")
+MEMBER = {"member_returns": "returns", "rewards": "rewards", "farm_power": "farm_power", "actions": "actions",
+          "observations": "observations", "final_yaw": "final_yaw", "gated": "gated"}  # ours[:, :, m] -> policy_returns'
+MODES = (True, False)
+KEYS = ("ws_revert", "ws_sigma", "wd_revert", "wd_sigma", "wd_ramp")
+PROCESS = dict(zip(KEYS, sr.PROCESS))
+STILL = dict(zip(KEYS, sr.STILL))
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
+
+
+def _same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def _handle(s, state=True):
+    from wfcrl_env_amd.backend import WfStep
+
+    c = s["c"]
+    w = WfStep(c["x"], c["y"], env_batch=c["B"])
+    w.set_wind(s["ws"], s["wd"])
+    w.env_config(load_coef=pr.LOAD_COEF, discrete=c["env"]["discrete"], dt=c["env"]["dt"])
+    if state:
+        w.env_reset()
+        w.env_set_state(c["state"])
+    return w
+
+
+def _run(w, s, strict, **kw):
+    c = s["c"]
+    kw.setdefault("want", WANT)
+    kw.setdefault("params", c["params"])
+    kw.setdefault("members", s["M"])
+    kw.setdefault("process", PROCESS)
+    kw.setdefault("tail", s["tail"])
+    kw.setdefault("risk_weight", s["lam"])
+    kw.setdefault("bounds", s["bounds"])
+    params, members, process = kw.pop("params"), kw.pop("members"), kw.pop("process")
+    return w.policy_scenarios(params, c["spec"], c["H"], members, process, seed=s["seed"], gamma=c["gamma"], strict=strict, **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def _device(name, strict):
+    """(the run; policy_returns under every member's path on the same handle; scenario_returns' wind_paths on the same handle;
+    the env state before and after the run)."""
+    s = sr.case(name)
+    c = s["c"]
+    w = _handle(s)
+    before = w.env_get_state()
+    kw = dict(max_eval_farms=32) if name == "ragged" else {}
+    got = _run(w, s, strict, **kw)
+    after = w.env_get_state()
+    members = [w.policy_returns(c["params"], c["spec"], c["H"], gamma=c["gamma"], wind=np.ascontiguousarray(got["wind_paths"][:, m]),
+                                strict=strict, want=tuple(MEMBER.values())) for m in range(s["M"])]
+    hold = np.zeros((c["B"], 1, c["H"], c["N"]), np.float32) + (1.0 if c["env"]["discrete"] else 0.0)
+    scen = w.scenario_returns(hold, s["M"], PROCESS, seed=s["seed"], gamma=c["gamma"], tail=s["tail"], risk_weight=s["lam"],
+                              bounds=s["bounds"], strict=strict, want=("wind_paths",))["wind_paths"]
+    w.close()
+    for v in got.values():
+        v.setflags(write=False)
+    return got, members, scen, before, after
+
+
+@pytest.mark.parametrize("strict", MODES)
+@pytest.mark.parametrize("name", sr.NAMES)
+def test_paths_are_the_scenario_extensions(name, strict):
+    """Check 1, and the shapes and dtypes of every output."""
+    s = sr.case(name)
+    got, _, scen, before, after = _device(name, strict)
+    B, N, K, M, H = s["B"], s["N"], s["K"], s["M"], s["H"]
+    f8, f4, i4 = np.float64, np.float32, np.int32
+    shapes = {"expected_returns": ((B, K), f8), "cvar": ((B, K), f8), "score": ((B, K), f8), "member_returns": ((B, K, M), f8),
+              "rewards": ((B, K, M, H), f8), "farm_power": ((B, K, M, H), f8), "wind_paths": ((B, M, H, 2), f8),
+              "actions": ((B, K, M, H, N), f4), "observations": ((B, K, M, H, 3 * N + 2), f4), "final_yaw": ((B, K, M, N), f4),
+              "gated": ((B, K, M), i4), "first_action": ((B, K, N), f4), "best": ((B,), i4)}
+    for k, (shape, d) in shapes.items():
+        assert got[k].shape == shape and got[k].dtype == d, k
+    assert np.array_equal(_bits(got["wind_paths"]), _bits(sr.reference(name)["wind_paths"]))
+    assert _same(got["wind_paths"], scen)
+    for k in before:  # the env state is read, never written
+        assert np.array_equal(before[k], after[k]), k
+
+
+@pytest.mark.parametrize("strict", MODES)
+def test_paths_under_an_anchor(strict):
+    s = sr.case("row3_central")
+    c = s["c"]
+    w = _handle(s)
+    got = _run(w, s, strict, anchor=s["anchor"], want=("wind_paths", "best"))["wind_paths"]
+    hold = np.zeros((c["B"], 1, c["H"], c["N"]), np.float32)
+    scen = w.scenario_returns(hold, s["M"], PROCESS, seed=s["seed"], tail=s["tail"], anchor=s["anchor"], bounds=s["bounds"], strict=strict,
+                              want=("wind_paths",))["wind_paths"]
+    w.close()
+    want = scenario_ref.paths(s["seed"], np.arange(c["B"]), s["M"], c["H"], sr.PROCESS, s["ws"], s["wd"], s["anchor"], s["bounds"])["wind"]
+    assert np.array_equal(_bits(got), _bits(want)) and _same(got, scen)
+    assert not np.array_equal(got, sr.reference("row3_central")["wind_paths"])  # (the anchor matters)
+
+
+@pytest.mark.parametrize("strict", MODES)
+@pytest.mark.parametrize("name", sr.NAMES)
+def test_member_m_is_policy_returns_under_path_m(name, strict):
+    """Check 2: every member of every case, every output, bit for bit."""
+    s = sr.case(name)
+    got, members = _device(name, strict)[:2]
+    for m in range(s["M"]):
+        for ours, theirs in MEMBER.items():
+            assert _same(np.ascontiguousarray(got[ours][:, :, m]), members[m][theirs]), (name, strict, m, ours)
+    if s["M"] > 1:
+        assert not _same(np.ascontiguousarray(got["rewards"][:, :, 0]), np.ascontiguousarray(got["rewards"][:, :, 1]))
+
+
+@pytest.mark.parametrize("strict", MODES)
+@pytest.mark.parametrize("name", sr.NAMES)
+def test_actions_are_the_network_of_the_observations(name, strict):
+    """Check 3: the network link, directly; first_action is step 0's action of every member."""
+    s = sr.case(name)
+    c = s["c"]
+    got = _device(name, strict)[0]
+    N = s["N"]
+    for k in range(s["K"]):
+        want, margin = pr.actions_from_observations(c["params"][k], c["spec"], got["observations"][:, k], N, c["env"]["discrete"])
+        dev = got["actions"][:, k]
+        if c["env"]["discrete"]:
+            assert (margin > 1e-9).all()
+            assert np.array_equal(dev, want)
+        elif "tanh" in (c["spec"]["activation"] if len(c["spec"]["widths"]) > 2 else None, c["spec"]["final"]):
+            ulp = np.spacing(np.abs(want)).astype(np.float32)
+            print(f"{name} policy {k}: actions that differ from the reference's by one float32 ulp: {(dev != want).sum()} of {dev.size}")
+            assert (np.abs(dev.astype(np.float64) - want.astype(np.float64)) <= ulp).all()
+        else:
+            assert np.array_equal(_bits(dev), _bits(want)), (name, k)
+    assert _same(got["first_action"], np.ascontiguousarray(got["actions"][:, :, 0, 0]))
+    for m in range(s["M"]):
+        assert _same(np.ascontiguousarray(got["actions"][:, :, m, 0]), got["first_action"]), m
+
+
+@pytest.mark.parametrize("strict", MODES)
+@pytest.mark.parametrize("name", sr.NAMES)
+def test_statistics_of_the_devices_member_returns(name, strict):
+    """Check 4 at the case's lam; the member return is the discounted sum of the device's own rewards (policy_returns' link)."""
+    s = sr.case(name)
+    got = _device(name, strict)[0]
+    st = scenario_ref.statistics(got["member_returns"], s["tail"], s["lam"])
+    for k in ("expected_returns", "cvar", "score"):
+        assert np.array_equal(_bits(got[k]), _bits(st[k])), (name, k)
+    assert np.array_equal(got["best"], st["best"])
+
+
+@pytest.mark.parametrize("strict", MODES)
+def test_statistics_at_every_risk_weight_and_ties(strict):
+    """Check 4: lam in {0, 0.5, 1}; and two identical parameter vectors at indices 0 and 2 score the same bits, the choice
+    never naming index 2 where they tie for the maximum."""
+    s = sr.case("row3_central")
+    c = s["c"]
+    params = np.ascontiguousarray(c["params"][[0, 1, 0]])
+    w = _handle(s)
+    runs = {lam: _run(w, s, strict, params=params, risk_weight=lam, want=("member_returns", "expected_returns", "cvar", "score", "best"))
+            for lam in (0.0, 0.5, 1.0)}
+    w.close()
+    for lam, got in runs.items():
+        st = scenario_ref.statistics(got["member_returns"], s["tail"], lam)
+        for k in ("expected_returns", "cvar", "score"):
+            assert np.array_equal(_bits(got[k]), _bits(st[k])), (lam, k)
+        assert np.array_equal(got["best"], st["best"])
+        assert _same(got["member_returns"], runs[0.0]["member_returns"])
+        assert np.array_equal(_bits(got["score"][:, 0]), _bits(got["score"][:, 2]))
+        assert (got["best"] != 2).all()
+        tie = got["score"][:, 0] >= got["score"][:, 1]
+        assert (got["best"][tie] == 0).all() and (got["best"][~tie] == 1).all()
+    assert np.array_equal(_bits(runs[0.0]["score"]), _bits(runs[0.0]["expected_returns"]))
+    assert np.array_equal(_bits(runs[1.0]["score"]), _bits(runs[1.0]["cvar"]))
+
+
+@pytest.mark.parametrize("strict", MODES)
+@pytest.mark.parametrize("base", ("row3_central", "row3_discrete", "abl_central"))
+def test_one_still_member_is_policy_returns_under_the_wind_held(base, strict):
+    """Check 5."""
+    s = sr.case(base)
+    c = s["c"]
+    w = _handle(s)
+    got = _run(w, s, strict, members=1, process=STILL, tail=1)
+    want = w.policy_returns(c["params"], c["spec"], c["H"], gamma=c["gamma"], wind=None, strict=strict, want=tuple(MEMBER.values()) + ("best",))
+    w.close()
+    for ours, theirs in MEMBER.items():
+        assert _same(np.ascontiguousarray(got[ours][:, :, 0]), want[theirs]), (base, ours)
+    for k in ("expected_returns", "cvar", "score"):
+        assert _same(got[k], want["returns"]), k
+    assert np.array_equal(got["best"], want["best"])
+    held = np.stack([s["ws"], s["wd"]], axis=1)[:, None, None]
+    assert np.array_equal(got["wind_paths"], np.broadcast_to(held, got["wind_paths"].shape))
+
+
+def test_pending_prev_wind_is_neither_read_nor_consumed():
+    """Check 6: with a speed left by env_set_prev_wind every output has the bits of the run without it, and the speed is still
+    pending afterwards: the env's next step pays the reward of a twin handle on which no run was made — normalised by the
+    pending speed —, not the reward of a twin without a pending speed."""
+    s = sr.case("abl_central")
+    c = s["c"]
+    wr = s["ws"] * 1.1
+    action = np.full((c["B"], c["N"]), 2.0, np.float32)
+    plain = _device("abl_central", False)[0]
+    w = _handle(s)
+    w.env_set_prev_wind(wr)
+    got = _run(w, s, False)
+    paid = w.env_step(action, want=("reward",))["reward"]
+    w.close()
+    for k in WANT:
+        assert _same(got[k], plain[k]), k
+    twin = _handle(s)
+    twin.env_set_prev_wind(wr)
+    pending = twin.env_step(action, want=("reward",))["reward"]
+    twin.close()
+    twin = _handle(s)
+    current = twin.env_step(action, want=("reward",))["reward"]
+    twin.close()
+    assert _same(paid, pending) and (paid != current).all()
+
+
+def test_same_bits_from_two_runs_chunks_farm_lists_and_device_arrays():
+    """Check 7, on the ragged case: 7 farms, K M = 15 rows per farm; max_eval_farms = 32 gives chunks of 2 farms with a last one
+    of 1 and M C = 10 rows of a policy (less than a tile); 300 gives one chunk, M C = 35 rows: three tiles, the last partial."""
+    import torch
+
+    s = sr.case("ragged")
+    c = s["c"]
+    for strict in MODES:
+        chunks = _device("ragged", strict)[0]
+        w = _handle(s)
+        before = w.env_get_state()
+        one = _run(w, s, strict, max_eval_farms=300)
+        again = _run(w, s, strict, max_eval_farms=300)
+        order = np.array([5, 0, 6, 2, 4, 1, 3])
+        listed = _run(w, s, strict, farms=order, max_eval_farms=47)  # chunks of 3, 3 and 1 farms
+        dev = _run(w, s, strict, params=torch.from_numpy(c["params"].copy()).cuda(), max_eval_farms=32)
+        after = w.env_get_state()
+        wind = w.get_wind() if hasattr(w, "get_wind") else None
+        w.close()
+        for k in WANT:
+            assert _same(one[k], chunks[k]) and _same(again[k], one[k]), (strict, k)
+            assert _same(listed[k], np.ascontiguousarray(one[k][order])), (strict, k)
+            assert dev[k].is_cuda and _same(dev[k].cpu().numpy(), one[k]), (strict, k)
+        for k in before:
+            assert np.array_equal(before[k], after[k]), k
+        if wind is not None:
+            assert np.array_equal(np.asarray(wind[0], np.float64).reshape(-1), s["ws"]) and np.array_equal(np.asarray(wind[1], np.float64).reshape(-1), s["wd"])
+
+
+def test_refusals_name_their_cause():
+    """Check 8: each refusal carries its code and a message, and nothing is launched: the handle still serves afterwards."""
+    from wfcrl_env_amd import _lib
+    from wfcrl_env_amd import environments as envs
+    from wfcrl_env_amd import policy as P
+    from wfcrl_env_amd.backend import WfStep
+    from yawopt_ref import ROW3
+
+    x, y = ROW3
+    N = 3
+    spec = P.mlp_spec("shared", (3, 5, 1), "relu")
+    vec = np.zeros((2, P.param_count((3, 5, 1))), np.float32)
+    run = lambda w, params=vec, spec=spec, H=2, M=3, process=PROCESS, **kw: w.policy_scenarios(params, spec, H, M, process, **kw)
+    w = WfStep(np.stack([x, x + 10.0]), np.stack([y, y]), env_batch=2)  # two layouts
+    w.set_wind(8.0, 270.0)
+    with pytest.raises(ValueError, match="WF_E_UNSUPPORTED.*several layouts"):
+        run(w)
+    w.close()
+    w = WfStep(x, y, env_batch=2)
+    w.set_turbine_types([{}, {"gen_eff": 0.9}], [0, 1, 0])
+    w.set_wind(8.0, 270.0)
+    with pytest.raises(ValueError, match="WF_E_UNSUPPORTED.*several turbine definitions"):
+        run(w)
+    w.close()
+    w = WfStep(x, y, env_batch=2)
+    with pytest.raises(ValueError, match="WF_E_INVALID.*no wind"):
+        run(w)
+    w.set_wind(8.0, 270.0)
+    with pytest.raises(ValueError, match="WF_E_INVALID.*no env state"):
+        run(w)
+    w.env_config()
+    w.env_reset()
+    w.set_model_sets([{}, {"ambient_ti": 0.1}], [0, 1])
+    with pytest.raises(ValueError, match="WF_E_UNSUPPORTED.*wake-model parameter sets"):
+        run(w)
+    w.set_model_sets([{}], [0, 0])
+    w.close()
+    w = WfStep(x, y, env_batch=2)
+    w.set_wind(8.0, 270.0)
+    w.env_config()
+    w.env_reset()
+    po = w._polscen()  # a new object holds no network: the C entry point itself, no output asked for
+    proc = _lib.WindProcess(**PROCESS)
+    with pytest.raises(ValueError, match="WF_E_INVALID.*no network: wf_polscen_set_network comes first"):
+        po._call("run", vec.ctypes.data, 2, vec.shape[1], 2, 3, C.byref(proc), 3.0, 28.0, C.c_ulonglong(0), 1.0, 3, 0.0, None, 2, None,
+                 *([None] * 13), 0)
+    with pytest.raises(ValueError, match="WF_E_INVALID.*parameter vector of the wrong length"):
+        run(w, params=vec[:, :-1])
+    with pytest.raises(ValueError, match="WF_E_INVALID.*H must be in 1..64"):
+        run(w, H=65)
+    with pytest.raises(ValueError, match="WF_E_INVALID.*H must be in 1..64"):
+        run(w, H=0)
+    with pytest.raises(ValueError, match="WF_E_INVALID.*K must be in 1..64"):
+        run(w, params=np.zeros((65, vec.shape[1]), np.float32))
+    for M in (0, 65):
+        with pytest.raises(ValueError, match="WF_E_INVALID.*M must be in 1..64"):
+            run(w, M=M)
+    for tail in (0, 4):
+        with pytest.raises(ValueError, match="WF_E_INVALID.*tail must be in 1..M"):
+            run(w, tail=tail)
+    for lam in (-0.1, 1.5, float("nan")):
+        with pytest.raises(ValueError, match="WF_E_INVALID.*risk_weight"):
+            run(w, risk_weight=lam)
+    with pytest.raises(ValueError, match="WF_E_INVALID.*gamma"):
+        run(w, gamma=1.5)
+    for bounds in ((8.0, 8.0), (9.0, 4.0), (0.0, 9.0)):
+        with pytest.raises(ValueError, match="WF_E_INVALID.*0 < ws_lo < ws_hi"):
+            run(w, bounds=bounds)
+    with pytest.raises(ValueError, match="WF_E_INVALID.*ws_revert and wd_revert"):
+        run(w, process=dict(PROCESS, ws_revert=1.5))
+    with pytest.raises(ValueError, match="WF_E_INVALID.*anchor's speed"):
+        run(w, anchor=np.array([[8.0, 270.0], [0.0, 270.0]]))
+    with pytest.raises(ValueError, match="WF_E_INVALID.*max_eval_farms must hold one farm's rows: at least K M"):
+        run(w, max_eval_farms=5)
+    with pytest.raises(ValueError, match="WF_E_INVALID.*output width does not match"):
+        run(w, params=np.zeros((2, P.param_count((3, 5, 3))), np.float32), spec=P.mlp_spec("shared", (3, 5, 3), "relu"))
+    with pytest.raises(ValueError, match="farm index out of range"):
+        run(w, farms=[0, 2])
+    with pytest.raises(ValueError, match="needs a wind process"):
+        run(w, process=None)
+    with pytest.raises(ValueError, match="want must name"):
+        run(w, want=("returns",))
+    with pytest.raises(ValueError, match="has not run yet"):
+        w.policy_scenarios_timing()
+    r = run(w, farms=[1], max_eval_farms=6, want=WANT)  # (the handle still serves)
+    assert r["score"].shape == (1, 2) and np.isfinite(r["score"]).all() and r["best"].tolist() == [0]
+    assert (r["actions"] == 0.0).all() and (r["final_yaw"] == 0.0).all()
+    assert w.step(np.zeros((2, N), np.float32))["power"].shape == (2, N)
+    w.close()
+    env = envs.make("Ablaincourt_Floris", env_batch=2, max_num_steps=5, return_torch=False)  # no wind_process
+    env.reset(seed=0)
+    net = (np.zeros((1, P.param_count((3, 1))), np.float32), P.mlp_spec("shared", (3, 1)))
+    with pytest.raises(ValueError, match="built without wind_process"):
+        env.policy_scenarios(net, 2)
+    assert env.policy_scenarios(net, 2, members=2, process=PROCESS)["best"].shape == (2,)
+    env.close()
+
+
+def test_kernel_info_shows_no_scratch_at_80_turbines():
+    """Check 9: no private segment in any kernel a run launches; every kernel's LDS is dynamic (0 static bytes) and a run at
+    N = 80 fits a block's 64 KiB: the library refuses a plan beyond it, and the case's runs above were launched."""
+    s = sr.case("horns_central")
+    w = _handle(s, state=False)
+    info = w.policy_scenarios_kernel_info()
+    w.close()
+    assert set(info) == {"paths", "returns", "stats", "transpose", "begin", "advance"}
+    for k, v in info.items():
+        assert v["scratch_bytes"] == 0 and v["vgprs"] > 0 and v["lds_bytes"] == 0, (k, v)
+    got = _device("horns_central", False)[0]
+    assert np.isfinite(got["score"]).all()
+
+
+def test_vec_env_method_returns_torch():
+    """Check 10: VecWindFarmEnv.policy_scenarios on a wind_process env that returns torch: CUDA tensors of the stated shapes
+    and dtypes, process and bounds taken from the env, an nn.Sequential taken through policy_from_torch; the bits of
+    WfStep.policy_scenarios given NumPy arrays on the same state; the env is left as it was."""
+    import torch
+    import torch.nn as nn
+
+    from wfcrl_env_amd import environments as envs
+    from wfcrl_env_amd import policy as P
+
+    B, H, M = 5, 3, 3
+    process = dict(ws_revert=0.1, ws_sigma=0.4, wd_revert=0.1, wd_sigma=3.0, wd_ramp=2.0, dist=dict(wd_mean=265.0, wd_std=10.0))
+    env = envs.make("Ablaincourt_Floris", env_batch=B, max_num_steps=12, load_coef=pr.LOAD_COEF, wind_process=process)
+    N = env.num_turbines
+    env.reset(seed=11)
+    env.step({"yaw": torch.full((B, N), 2.0).cuda()})
+    torch.manual_seed(2)
+    net = nn.Sequential(nn.Linear(3 * N + 2, 5), nn.Softsign(), nn.Linear(5, N), nn.Softsign())
+    kw = dict(kind="central", out_scale=5.0, scale=np.full(3 * N + 2, 0.01))
+    before = env.fi.env_get_state()
+    r = env.policy_scenarios(net, H, members=M, seed=5, gamma=0.95, tail=2, risk_weight=0.5, want=WANT, **kw)
+    after = env.fi.env_get_state()
+    params, spec = P.policy_from_torch(net, **kw)
+    proc = {k: process[k] for k in KEYS}
+    bounds = (float(env._wind_dist.get("ws_lo", 3.0)), float(env._wind_dist.get("ws_hi", 28.0))) if env._wind_dist is not None else (3.0, 28.0)
+    direct = env.fi.policy_scenarios(params, spec, H, M, proc, seed=5, gamma=0.95, tail=2, risk_weight=0.5, bounds=bounds, want=WANT)
+    env.close()
+    K = 1
+    f8, f4, i4 = torch.float64, torch.float32, torch.int32
+    shapes = {"expected_returns": ((B, K), f8), "cvar": ((B, K), f8), "score": ((B, K), f8), "member_returns": ((B, K, M), f8),
+              "rewards": ((B, K, M, H), f8), "farm_power": ((B, K, M, H), f8), "wind_paths": ((B, M, H, 2), f8),
+              "actions": ((B, K, M, H, N), f4), "observations": ((B, K, M, H, 3 * N + 2), f4), "final_yaw": ((B, K, M, N), f4),
+              "gated": ((B, K, M), i4), "first_action": ((B, K, N), f4), "best": ((B,), i4)}
+    for k, (shape, d) in shapes.items():
+        assert r[k].is_cuda and tuple(r[k].shape) == shape and r[k].dtype == d, k
+        assert _same(r[k].cpu().numpy(), direct[k]), k
+    for k in before:
+        assert np.array_equal(before[k], after[k]), k
+    assert (direct["actions"] != 0.0).any() and (direct["wind_paths"][:, 0] != direct["wind_paths"][:, 1]).any()

@@ -883,6 +883,51 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the policy kernels as the runtime reports them."""
         return self._policy().kernel_info()
 
+    # -- policy rollouts over a wind ensemble (include/wfpolscen.h) ---------------------------------------
+    def _polscen(self) -> "_PolScen":
+        """The handle's policy-scenario object; created on first use, destroyed in close() before the handle."""
+        po = getattr(self, "_polscen_obj", None)
+        if po is None:
+            po = self._polscen_obj = _PolScen(self)
+        return po
+
+    def policy_scenarios(self, params, spec, horizon, members, process, seed=0, gamma=1.0, tail=None, risk_weight=0.0, anchor=None,
+                         bounds=(3.0, 28.0), farms=None, strict=False, max_eval_farms=65536,
+                         want=("expected_returns", "cvar", "score", "best"), out=None) -> dict:
+        """What each of K parameter vectors of one small MLP policy earns over the next `horizon` steps of the fused env in
+        closed loop under each of `members` wind futures drawn from the wind process, from the wind and the env state the
+        handle holds, which are read and never changed (include/wfpolscen.h; the project's own definition, PARITY UNPINNED
+        beyond the oracle: tests/polscen_ref.py composes tests/scenario_ref.py and tests/policy_ref.py).  The network, the
+        observation and the transition are policy_returns'; the member paths, their seed keying and the statistics are
+        scenario_returns': `wind_paths` has the bits scenario_returns gives for the same (seed, members, horizon, process,
+        bounds, anchor), and member m's outputs have the bits of policy_returns(wind=wind_paths[:, m]) while no prev-wind
+        speed is pending (strict: always; default mode: where both evaluators' batches take the same step kernel).  Step 0 is normalised by the farm's current speed: a pending speed is neither used nor consumed.
+
+          params, spec   as policy_returns takes them: (K, P) float32, 1 <= K <= 64, and policy.mlp_spec(...)
+          horizon        H in 1..64;  members M in 1..64
+          process        dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp), missing keys 0
+          tail           q in 1..M (None: M, the tail mean is the mean in another summation order)
+          risk_weight    lam in [0, 1]: score = (1 - lam) mean + lam cvar
+          anchor         (n_farms, 2) float64 the paths revert to, or None = every farm's current wind
+          bounds         (ws_lo, ws_hi) the stored speeds are clipped to
+          farms, strict, max_eval_farms   as policy_returns; the evaluator holds K M rows per farm
+          want           of "expected_returns", "cvar", "score" (n, K), "member_returns" (n, K, M), "rewards", "farm_power"
+                         (n, K, M, H), "wind_paths" (n, M, H, 2), "actions" (n, K, M, H, N), "observations"
+                         (n, K, M, H, 3 N + 2), "final_yaw" (n, K, M, N), "gated" (n, K, M), "first_action" (n, K, N), "best" (n,)
+
+        One batched step per env step, K M rows per farm, nothing read back in between.  Torch CUDA tensors in (params,
+        anchor or `out`) give torch tensors out."""
+        return self._polscen().run(params, spec, horizon, members, process, seed, gamma, tail, risk_weight, anchor, bounds, farms,
+                                   strict, max_eval_farms, want, out)
+
+    def policy_scenarios_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last policy_scenarios {"total_ms", "step_ms", "glue_ms"}."""
+        return self._polscen().timing(detail)
+
+    def policy_scenarios_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the kernels a policy_scenarios run launches."""
+        return self._polscen().kernel_info()
+
     # -- scenario look-ahead: returns of action sequences over a wind ensemble (include/wfscenario.h) ------
     def _scenario(self) -> "_Scenario":
         """The handle's scenario object; created on first use, destroyed in close() before the handle."""
@@ -1552,7 +1597,7 @@ class WfStep:
             # wfcredit.h, wflookahead.h, wfpolicy.h, wfplan.h, wfretgrad.h, wfrollout.h, wfrollscen.h, wfcalib.h — the rollout and the scenario-rollout
             # object, created on the rose object, before it)
             for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rollout_obj", "_rollscen_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
-                         "_lookahead_obj", "_policy_obj", "_scenario_obj", "_plan_obj", "_scenplan_obj", "_retgrad_obj", "_calib_obj", "_windgen_obj"):
+                         "_lookahead_obj", "_policy_obj", "_polscen_obj", "_scenario_obj", "_plan_obj", "_scenplan_obj", "_retgrad_obj", "_calib_obj", "_windgen_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
                     ext.close()
@@ -2144,6 +2189,80 @@ class _Policy(_Ext):
         p = dict(zip(spec_out, ptrs))
         self._call("run", params.data_ptr() if on_device else params.ctypes.data, K, P, H, wptr, float(gamma), n, fptr,
                    *[p.get(k) for k in self.OUTPUTS], int(on_device))
+        return {k: out[k] for k in spec_out}
+
+
+class _PolScen(_Policy):
+    """The `wf_polscen` object of a WfStep handle (include/wfpolscen.h); the network is taken as the policy object takes it."""
+
+    NAME = "polscen"
+    KERNELS = ("paths", "returns", "stats", "transpose", "begin", "advance")
+    OUTPUTS = ("expected_returns", "cvar", "score", "member_returns", "rewards", "farm_power", "wind_paths", "actions",
+               "observations", "final_yaw", "gated", "first_action", "best")
+
+    def run(self, params, spec, horizon, members, process, seed, gamma, tail, risk_weight, anchor, bounds, farms, strict,
+            max_eval_farms, want, out):
+        w = self._w
+        N = w.num_turbines
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.OUTPUTS for k in want):
+            raise ValueError("want must name " + ", ".join(self.OUTPUTS[:-1]) + " and / or " + self.OUTPUTS[-1])
+        if process is None:
+            raise ValueError("policy_scenarios needs a wind process: dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp)")
+        unknown = set(process) - set(_Scenario.PROCESS)
+        if unknown:
+            raise ValueError(f"unknown wind process parameter(s): {sorted(unknown)}")
+        p = WindProcess(**{k: float(process.get(k, 0.0)) for k in _Scenario.PROCESS})
+        self._set_network(spec)
+        H, M = int(horizon), int(members)
+        q = M if tail is None else int(tail)
+        ws_lo, ws_hi = (float(v) for v in bounds)
+        self._call("config", int(bool(strict)), int(max_eval_farms or 0))
+        fa, n, fptr = self._farms(farms)
+        on_device = _is_torch(params) or _is_torch(anchor) or (out is not None and any(_is_torch(v) for v in out.values()))
+        like = None
+        if on_device:
+            import torch
+
+            w._follow_torch_stream()
+            like = next(v for v in [params, anchor] + list((out or {}).values()) if _is_torch(v))
+            if not _is_torch(params):
+                params = torch.as_tensor(np.array(params, np.float32), device=like.device)
+            assert params.is_cuda and params.dtype == torch.float32, "params"
+            params = params.contiguous()
+        else:
+            params = np.ascontiguousarray(params, dtype=np.float32)
+        if len(tuple(params.shape)) == 1:
+            params = params.reshape(1, -1)
+        if len(tuple(params.shape)) != 2:
+            raise ValueError("params must be (K, P): a parameter vector per policy")
+        K, P = int(params.shape[0]), int(params.shape[1])
+        aptr = None
+        if anchor is not None:
+            if on_device:
+                if not _is_torch(anchor):
+                    anchor = torch.as_tensor(np.asarray(anchor, np.float64), device=like.device)
+                assert anchor.is_cuda and anchor.dtype == torch.float64, "anchor"
+                anchor = anchor.contiguous()
+            else:
+                anchor = np.ascontiguousarray(anchor, dtype=np.float64)
+            if tuple(anchor.shape) != (n, 2):
+                raise ValueError("anchor must be (n_farms, 2): the (speed, direction) every listed farm's paths revert to")
+            aptr = anchor.data_ptr() if on_device else anchor.ctypes.data
+        f8, f4, i4 = np.float64, np.float32, np.int32
+        shapes = {"expected_returns": ((n, K), f8), "cvar": ((n, K), f8), "score": ((n, K), f8), "member_returns": ((n, K, M), f8),
+                  "rewards": ((n, K, M, H), f8), "farm_power": ((n, K, M, H), f8), "wind_paths": ((n, M, H, 2), f8),
+                  "actions": ((n, K, M, H, N), f4), "observations": ((n, K, M, H, 3 * N + 2), f4), "final_yaw": ((n, K, M, N), f4),
+                  "gated": ((n, K, M), i4), "first_action": ((n, K, N), f4), "best": ((n,), i4)}
+        if not (1 <= K <= 64 and 1 <= M <= 64 and 1 <= H <= 64):  # (the library names the limit; no output is sized from a refused shape)
+            shapes = {k: ((0,), d) for k, (_, d) in shapes.items()}
+            out = None
+        spec_out = {k: shapes[k] for k in self.OUTPUTS if k in want}
+        out, ptrs = self._outputs(out, spec_out, on_device, like)
+        ptr = dict(zip(spec_out, ptrs))
+        self._call("run", params.data_ptr() if on_device else params.ctypes.data, K, P, H, M, C.byref(p), ws_lo, ws_hi,
+                   C.c_ulonglong(int(seed) & (2**64 - 1)), float(gamma), q, float(risk_weight), aptr, n, fptr,
+                   *[ptr.get(k) for k in self.OUTPUTS], int(on_device))
         return {k: out[k] for k in spec_out}
 
 

@@ -113,7 +113,7 @@ inline WfSlots chunk_slots(const farm_list& fl, const int* farms, int base, int 
 // element type, lie end to end (16-byte aligned) in `buf`, in the order they were named: in() for what the kernels read,
 // out() for what they write; *d is the array's device pointer, null for a null array — a host caller's from begin() on.
 struct staging {
-  static constexpr int kMaxSegs = 13;  // the most arrays one call names (wf_retgrad_run: three inputs, ten outputs)
+  static constexpr int kMaxSegs = 15;  // the most arrays one call names (wf_polscen_run: two inputs, thirteen outputs)
   ext_base* x;
   dev_buf<char>& buf;
   bool host;

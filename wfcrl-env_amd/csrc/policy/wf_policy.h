@@ -2,7 +2,8 @@
 // see it, the block the four kernels of wf_policy_kernels.hip read their arguments from, the LDS plan of the advance kernel and the launchers,
 // called by wf_policy_abi.hip.
 //
-// Layout of a chunk of C farm SLOTS with K rows each: evaluator farm e = k C + slot, so the rows of ONE policy are contiguous:
+// Layout of a chunk of C farm SLOTS with K rows each (K M under an ensemble of M members: WfPolicyRun below): evaluator farm
+// e = k C + slot, so the rows of ONE policy are contiguous:
 // a workgroup of the advance kernel serves a TILE of T consecutive slots of one policy — it streams that policy's weights once
 // for its T rows, and its rows' power, load and local-wind blocks are contiguous [T][N] arrays.  Row (k, slot) holds, in round
 // 0, the farm's current yaw under its current wind and, in round h + 1, the yaw after step h of policy k under wind h.  Slots
@@ -68,6 +69,12 @@ struct WfPolicyRun {
   float *actions, *observations;           // [n][K][H][N], [n][K][H][3 N + 2]
   float* final_yaw;                        // [n][K][N]
   int *gated, *best;                       // [n][K], [n]
+  // Under an ENSEMBLE (include/wfpolscen.h; wf_policy_run: M = 1, paths and first_action null): a policy has M C rows, row
+  // j = m C + slot of policy k is evaluator farm k M C + j, the caller's blocks gain a member axis after K — [n][K][M]... —
+  // and row (m, slot) is solved under paths[slot][m] instead of `wind`.  A tile is T consecutive rows j of one policy.
+  int M;
+  const double* paths;    // [C][M][H][2] the chunk's member paths (speed, direction) of tick h + 1, or null
+  float* first_action;    // [n][K][N] step 0's raw action, written from member 0's rows, or null
 };
 
 // the advance kernel's tile for chunks of C slots: the rows one workgroup serves, from the LDS they need (56 KiB per block)

@@ -15,6 +15,7 @@
 #include "../../../include/wfpolicy.h"
 #include "../ext/wf_ext.h"
 #include "wf_policy.h"
+#include "wf_policy_host.h"
 
 using namespace wfi;
 
@@ -47,28 +48,11 @@ const char* const kNoEnv = "no env state: wf_env_config and wf_env_reset come fi
 
 }  // namespace
 
-extern "C" {
+// ---- what polscen/ shares (policy/wf_policy_host.h) ----
+namespace wfi {
 
-int wf_policy_create(wf_handle* h, wf_policy** out) { return ext_create(h, out); }
-
-int wf_policy_destroy(wf_policy* p) { return ext_destroy(p); }
-
-int wf_policy_config(wf_policy* p, int strict, int max_eval_farms) {
-  if (!p) return WF_E_INVALID;
-  if (max_eval_farms <= 0) max_eval_farms = 65536;
-  p->strict = strict != 0; p->max_eval = max_eval_farms;
-  return WF_OK;
-}
-
-int wf_policy_set_timing(wf_policy* p, int detail) {
-  if (!p) return WF_E_INVALID;
-  p->detail = detail != 0;
-  return WF_OK;
-}
-
-int wf_policy_set_network(wf_policy* p, int kind, int n_layers, const int* widths, int activation, int final, int use_freewind,
-                          double out_scale, const double* shift, const double* scale) {
-  if (!p) return WF_E_INVALID;
+int policy_network(ext_base* p, int kind, int n_layers, const int* widths, int activation, int final, int use_freewind, double out_scale,
+                   const double* shift, const double* scale, WfPolicyNet* net, std::vector<double>* norm) {
   if (kind != WF_POLICY_CENTRAL && kind != WF_POLICY_SHARED)
     return ext_fail(p, WF_E_INVALID, "unknown policy kind: WF_POLICY_CENTRAL or WF_POLICY_SHARED");
   if (n_layers < 1 || n_layers > WF_POLICY_MAX_LAYERS) return ext_fail(p, WF_E_INVALID, "the number of layers L must be in 1..4");
@@ -97,14 +81,64 @@ int wf_policy_set_network(wf_policy* p, int kind, int n_layers, const int* width
     n.boff[l] = off; off += widths[l + 1];
   }
   n.P = off;
-  p->net = n;
-  p->norm.assign(2 * (size_t)D, 0.0);
+  *net = n;
+  norm->assign(2 * (size_t)D, 0.0);
   for (int i = 0; i < D; ++i) {
-    p->norm[i] = shift ? shift[i] : 0.0;
-    p->norm[D + i] = scale ? scale[i] : 1.0;
+    (*norm)[i] = shift ? shift[i] : 0.0;
+    (*norm)[D + i] = scale ? scale[i] : 1.0;
   }
-  p->has_net = true;
   return WF_OK;
+}
+
+int policy_network_fits(ext_base* p, const wf_handle* h, WfPolicyNet& net, int P) {
+  const int N = h->N;
+  const int D = net.kind == WF_POLICY_CENTRAL ? 3 * N + 2 : (net.use_freewind ? 5 : 3);
+  if (net.width[0] != D)
+    return ext_fail(p, WF_E_INVALID, "the network's input width does not match its kind: 3 N + 2 (central), 3 or 5 (shared)");
+  const int per = h->env.discrete ? 3 : 1, want = net.kind == WF_POLICY_CENTRAL ? per * N : per;
+  if (net.width[net.L] != want)
+    return ext_fail(p, WF_E_INVALID, "the network's output width does not match the env's action encoding: N or 3 N (central), 1 or 3 (shared)");
+  if (P != net.P)
+    return ext_fail(p, WF_E_INVALID, "a parameter vector of the wrong length: P must be sum_l (in_l + 1) out_l, " + std::to_string(net.P) + " for this network");
+  net.discrete = h->env.discrete;
+  return WF_OK;
+}
+
+WfEnvView policy_env_view(const wf_handle* h) {
+  WfEnvView e{};
+  e.yaw = h->d_env_yaw; e.acc = h->d_env_acc; e.moves = h->d_env_moves;
+  e.lo = h->env.yaw_lo; e.hi = h->env.yaw_hi; e.step = h->env.yaw_step;
+  e.rate = h->env.actuator_rate; e.dt = h->env.dt; e.budget = h->env.budget; e.discrete = h->env.discrete;
+  return e;
+}
+
+}  // namespace wfi
+
+extern "C" {
+
+int wf_policy_create(wf_handle* h, wf_policy** out) { return ext_create(h, out); }
+
+int wf_policy_destroy(wf_policy* p) { return ext_destroy(p); }
+
+int wf_policy_config(wf_policy* p, int strict, int max_eval_farms) {
+  if (!p) return WF_E_INVALID;
+  if (max_eval_farms <= 0) max_eval_farms = 65536;
+  p->strict = strict != 0; p->max_eval = max_eval_farms;
+  return WF_OK;
+}
+
+int wf_policy_set_timing(wf_policy* p, int detail) {
+  if (!p) return WF_E_INVALID;
+  p->detail = detail != 0;
+  return WF_OK;
+}
+
+int wf_policy_set_network(wf_policy* p, int kind, int n_layers, const int* widths, int activation, int final, int use_freewind,
+                          double out_scale, const double* shift, const double* scale) {
+  if (!p) return WF_E_INVALID;
+  const int rc = policy_network(p, kind, n_layers, widths, activation, final, use_freewind, out_scale, shift, scale, &p->net, &p->norm);
+  if (rc == WF_OK) p->has_net = true;
+  return rc;
 }
 
 int wf_policy_run(wf_policy* p, const float* params, int K, int P, int H, const double* wind, double gamma, int n_farms,
@@ -134,15 +168,8 @@ int wf_policy_run(wf_policy* p, const float* params, int K, int P, int H, const 
     if (!std::isfinite(gamma) || gamma < 0.0 || gamma > 1.0) return ext_fail(p, WF_E_INVALID, "gamma must be finite and in [0, 1]");
     if (!params) return ext_fail(p, WF_E_INVALID, "wf_policy_run: params is NULL");
     if (!h->d_env_yaw || !h->d_env_acc || !h->d_env_moves) return ext_fail(p, WF_E_INVALID, kNoEnv);
-    const int D = net.kind == WF_POLICY_CENTRAL ? 3 * N + 2 : (net.use_freewind ? 5 : 3);
-    if (net.width[0] != D)
-      return ext_fail(p, WF_E_INVALID, "the network's input width does not match its kind: 3 N + 2 (central), 3 or 5 (shared)");
-    const int per = h->env.discrete ? 3 : 1, want = net.kind == WF_POLICY_CENTRAL ? per * N : per;
-    if (net.width[net.L] != want)
-      return ext_fail(p, WF_E_INVALID, "the network's output width does not match the env's action encoding: N or 3 N (central), 1 or 3 (shared)");
-    if (P != net.P)
-      return ext_fail(p, WF_E_INVALID, "a parameter vector of the wrong length: P must be sum_l (in_l + 1) out_l, " + std::to_string(net.P) + " for this network");
-    net.discrete = h->env.discrete;
+    const int rc = policy_network_fits(p, h, net, P);
+    if (rc != WF_OK) return rc;
     k.rows = K; k.rounds = H + 1;
     return WF_OK;
   };
@@ -175,10 +202,8 @@ int wf_policy_run(wf_policy* p, const float* params, int K, int P, int H, const 
     WfPolicyRun& r = p->run;
     r = WfPolicyRun{};
     r.net = net; r.pl = plan;
-    r.N = N; r.K = K; r.H = H;
-    r.env.yaw = h->d_env_yaw; r.env.acc = h->d_env_acc; r.env.moves = h->d_env_moves;
-    r.env.lo = h->env.yaw_lo; r.env.hi = h->env.yaw_hi; r.env.step = h->env.yaw_step;
-    r.env.rate = h->env.actuator_rate; r.env.dt = h->env.dt; r.env.budget = h->env.budget; r.env.discrete = h->env.discrete;
+    r.N = N; r.K = K; r.H = H; r.M = 1;  // (no ensemble: paths and first_action stay null)
+    r.env = policy_env_view(h);
     r.ws = h->d_ws; r.wd = h->d_wd; r.wind_stride = h->wind_count == 1 ? 0 : 1;
     r.ws_prev = (h->ws_prev_valid && h->d_ws_prev) ? h->d_ws_prev : nullptr;  // read, not consumed
     r.load_coef = h->env.load_coef; r.gamma = gamma;

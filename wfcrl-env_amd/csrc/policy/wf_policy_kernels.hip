@@ -29,6 +29,10 @@
 //                               slot s over k ascending from the returns kept in LDS: strictly greater wins, so the lowest
 //                               index among equal maxima.
 //
+// UNDER AN ENSEMBLE of M wind futures (include/wfpolscen.h; polscen/ launches the transpose, begin and advance kernels of THIS
+// file, so the five phases exist once) a policy has M C rows, row j = m C + slot, each solved under its member's path
+// (WfPolicyRun: M, paths); wf_policy_run sets M = 1 and no paths: then j is the slot and every index below is what it was.
+//
 // No floating-point atomics (the gate count is an integer sum in LDS), no order that depends on scheduling.  Trip counts are
 // run-time values and nothing is indexed by a run-time value in registers: no private segment at any N (tests/test_policy.py
 // reads the metadata); every barrier sits in block-uniform control flow.  The library is built with -ffp-contract=off: the
@@ -53,7 +57,14 @@ __device__ __forceinline__ double policy_act(int kind, double z) {
 // the speed step h >= 0 is solved under / the direction
 __device__ __forceinline__ double wind_of(const double* wind, int h, int c, double held) { return wind ? wind[2 * h + c] : held; }
 
-// The reward of step hp of a tile's nt rows (evaluator rows e0 .., slots s0 ..): thread r leaves the speed row r is normalised
+// the (speed, direction) rows [H][2] row (m, slot) is solved under: its member path of the chunk (an ensemble), else the
+// caller's wind of the slot's block `in`, else null = the parent's wind held
+__device__ __forceinline__ const double* policy_row_wind(const WfPolicyRun& a, size_t in, int slot, int m) {
+  if (a.paths) return a.paths + ((size_t)slot * a.M + m) * a.H * 2;
+  return a.wind ? a.wind + in * a.H * 2 : nullptr;
+}
+
+// The reward of step hp of a tile's nt rows (evaluator rows e0 .., rows s0 .. of their policy — slots, where M = 1): thread r leaves the speed row r is normalised
 // by in wrl[r] — step 0's is the parent's (the pending prev-wind speed, else the current speed), step hp >= 1's the speed of
 // wind hp - 1 —, then the tile of wf_staged_row_rewards; its hooks touch LDS only (what a hook holds in scalar registers stays
 // live across the staged sums, which take nearly all of them).  Afterwards thread r < nt finds row r's reward in rwl[r] and its
@@ -62,12 +73,12 @@ __device__ __forceinline__ void policy_tile_rewards(const WfPolicyRun& a, const 
                                                     int sl, double* wrl, double* rwl, double* psl, float* pw, float* ld) {
   const int tid = threadIdx.x, N = a.N;
   if (tid < nt) {
-    const int slot = s0 + tid, b = wf_slot_farm(sl_, slot);
+    const int j = s0 + tid, m = j / sl_.C, slot = j - m * sl_.C, b = wf_slot_farm(sl_, slot);  // (M = 1: m = 0, slot = j)
     const size_t in = (size_t)sl_.base + (slot < sl_.n_slots ? slot : 0);
     const double held = a.ws[(size_t)b * a.wind_stride];
     double wr;
     if (hp == 0) wr = a.ws_prev ? a.ws_prev[b] : held;
-    else wr = wind_of(a.wind ? a.wind + in * a.H * 2 : nullptr, hp - 1, 0, held);
+    else wr = wind_of(policy_row_wind(a, in, slot, m), hp - 1, 0, held);
     wrl[tid] = wr;
   }
   wf_staged_row_rewards(
@@ -101,7 +112,7 @@ __global__ __launch_bounds__(256) void wf_policy_transpose_kernel(const WfPolicy
 __global__ __launch_bounds__(256) void wf_policy_begin_kernel(const WfPolicyRun* __restrict__ run, const WfSlots sl_) {
   const WfPolicyRun& a = *run;
   const int N = a.N, C = sl_.C;
-  const size_t E = (size_t)a.K * C, n = E * N;
+  const size_t E = (size_t)a.K * a.M * C, n = E * N;  // (e = (k M + m) C + slot: e % C is the slot under an ensemble too)
   for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (size_t)gridDim.x * blockDim.x) {
     const size_t e = q / N;
     const int t = (int)(q - e * N), slot = (int)(e % C);
@@ -124,11 +135,11 @@ __global__ __launch_bounds__(256) void wf_policy_advance_kernel(const WfPolicyRu
   extern __shared__ double po_lds[];
   const WfPolicyRun& a = *run;
   const int tid = threadIdx.x, nth = blockDim.x;
-  const int C = sl_.C, T = a.pl.T;
+  const int C = sl_.C, T = a.pl.T, R = a.M * C;          // R: the rows of one policy (M = 1: its slots)
   const int k = blockIdx.y, s0 = blockIdx.x * T;
-  int nt = C - s0;
+  int nt = R - s0;
   nt = nt > T ? T : nt;                                  // rows of this tile (block-uniform)
-  const size_t e0 = (size_t)k * C + s0;                  // its first evaluator row
+  const size_t e0 = (size_t)k * R + s0;                  // its first evaluator row
   const int h = round - 1;                               // the step whose action this launch issues
   // the LDS: the reward tile first, so that phase 1 needs nothing of what the later phases hold
   double* const wrl = po_lds;                            // [T] the rows' normalisers, ...
@@ -142,12 +153,12 @@ __global__ __launch_bounds__(256) void wf_policy_advance_kernel(const WfPolicyRu
     policy_tile_rewards(a, sl_, e0, s0, nt, h - 1, sp, sl, wrl, rwl, psl, pw, pw + (size_t)T * sp);  // (... and load values [T][sl])
     if (tid < nt) {
       const size_t e = e0 + tid;
-      const int slot = s0 + tid;
+      const int j = s0 + tid, m = j / C, slot = j - m * C;
       const double g = a.st.disc[e];
       a.st.ret[e] = a.st.ret[e] + g * rwl[tid];
       a.st.disc[e] = g * a.gamma;
       if (slot < sl_.n_slots) {
-        const size_t o = ((size_t)(sl_.base + slot) * a.K + k) * a.H + (h - 1);
+        const size_t o = (((size_t)(sl_.base + slot) * a.K + k) * a.M + m) * a.H + (h - 1);
         if (a.rewards) a.rewards[o] = rwl[tid];
         if (a.farm_power) a.farm_power[o] = psl[tid];
       }
@@ -173,8 +184,9 @@ __global__ __launch_bounds__(256) void wf_policy_advance_kernel(const WfPolicyRu
     else if (i < 3 * N) v = a.lwd[e * N + (i - 2 * N)];
     else v = (float)(i == 3 * N ? a.ews[e] : a.ewd[e]);
     obs[r * ds + i] = v;
-    const int slot = s0 + r;
-    if (a.observations && slot < sl_.n_slots) a.observations[(((size_t)(sl_.base + slot) * K + k) * H + h) * D0 + i] = v;
+    const int j = s0 + r, m = j / C, slot = j - m * C;
+    if (a.observations && slot < sl_.n_slots)
+      a.observations[((((size_t)(sl_.base + slot) * K + k) * a.M + m) * H + h) * D0 + i] = v;
   }
   __syncthreads();
 
@@ -259,7 +271,7 @@ __global__ __launch_bounds__(256) void wf_policy_advance_kernel(const WfPolicyRu
   for (int q = tid; q < nt * N; q += nth) {
     const int r = q / N, t = q - r * N;
     const size_t e = e0 + r;
-    const int slot = s0 + r, b = wf_slot_farm(sl_, slot);
+    const int j = s0 + r, m = j / C, slot = j - m * C, b = wf_slot_farm(sl_, slot);
     const int moves_new = a.env.moves[b] + moves_new_base;
     const float raw = actf[q], y = obs[r * ds + t], acc = a.st.acc[e * N + t];
     if (wf_env_gate_closed(a.env, acc, moves_new)) atomicAdd(&ng[r], 1);  // (an integer sum in LDS: any order gives the same value)
@@ -267,17 +279,21 @@ __global__ __launch_bounds__(256) void wf_policy_advance_kernel(const WfPolicyRu
     const float yn = wf_env_transition(a.env, y, raw, acc, moves_new, da);
     a.st.acc[e * N + t] = acc + fabsf(da);
     a.yaw[e * N + t] = yn;
-    if (a.actions && slot < sl_.n_slots) a.actions[(((size_t)(sl_.base + slot) * K + k) * H + h) * N + t] = raw;
+    if (slot < sl_.n_slots) {
+      const size_t f = (size_t)(sl_.base + slot) * K + k;
+      if (a.actions) a.actions[((f * a.M + m) * H + h) * N + t] = raw;
+      if (a.first_action && h == 0 && m == 0) a.first_action[f * N + t] = raw;  // (observation 0 is the same for every member)
+    }
   }
   __syncthreads();
   if (tid < nt) {
     const size_t e = e0 + tid;
     a.st.gated[e] += ng[tid];
-    if (a.wind) {  // the wind step h is solved under
-      const int slot = s0 + tid;
-      const size_t in = (size_t)sl_.base + (slot < sl_.n_slots ? slot : 0);
-      a.ews[e] = a.wind[(in * H + h) * 2];
-      a.ewd[e] = a.wind[(in * H + h) * 2 + 1];
+    if (a.wind || a.paths) {  // the wind step h is solved under
+      const int j = s0 + tid, m = j / C, slot = j - m * C;
+      const double* w = policy_row_wind(a, (size_t)sl_.base + (slot < sl_.n_slots ? slot : 0), slot, m);
+      a.ews[e] = w[2 * h];
+      a.ewd[e] = w[2 * h + 1];
     }
   }
 }
@@ -374,13 +390,13 @@ extern "C" hipError_t wfk_launch_policy_transpose(const WfPolicyRun* host, const
   return hipGetLastError();
 }
 extern "C" hipError_t wfk_launch_policy_begin(const WfPolicyRun* host, const WfPolicyRun* dev, const WfSlots* sl, hipStream_t s) {
-  const size_t n = (size_t)host->K * sl->C * host->N;
+  const size_t n = (size_t)host->K * host->M * sl->C * host->N;
   const int blocks = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
   hipLaunchKernelGGL(wf_policy_begin_kernel, dim3(blocks), dim3(256), 0, s, dev, *sl);
   return hipGetLastError();
 }
 extern "C" hipError_t wfk_launch_policy_advance(const WfPolicyRun* host, const WfPolicyRun* dev, const WfSlots* sl, int round, hipStream_t s) {
-  const int tiles = (sl->C + host->pl.T - 1) / host->pl.T;
+  const int tiles = (host->M * sl->C + host->pl.T - 1) / host->pl.T;
   hipLaunchKernelGGL(wf_policy_advance_kernel, dim3(tiles, host->K), dim3(host->pl.threads), host->pl.lds_bytes, s, dev, *sl, round);
   return hipGetLastError();
 }

@@ -840,6 +840,50 @@ class VecWindFarmEnv:
         return self.fi.policy_returns(params, spec, horizon, gamma=gamma, wind=wind, farms=farms, strict=strict,
                                       max_eval_farms=max_eval_farms, want=want)
 
+    def policy_scenarios(self, policy, horizon, members=8, process=None, seed=0, gamma=1.0, tail=None, risk_weight=0.0, anchor=None,
+                         bounds=None, farms=None, strict=False, max_eval_farms=65536,
+                         want=("expected_returns", "cvar", "score", "best"), kind=None, out_scale=1.0, shift=None, scale=None,
+                         use_freewind=False):
+        """What each of K MLP policies earns over the next `horizon` steps in closed loop under each of `members` wind futures
+        drawn from the wind process, from the state the env is in — call it BEFORE `step`: per policy the mean over the
+        members ("expected_returns"), the tail mean of the `tail` lowest member returns ("cvar"), score = (1 - risk_weight)
+        mean + risk_weight cvar, and "best", the policy of the largest score; `want` may also name "member_returns",
+        "rewards", "farm_power", "wind_paths", "actions", "observations", "final_yaw", "gated" and "first_action"
+        (include/wfpolscen.h; backend.WfStep.policy_scenarios has the arguments; the project's own definition).  `policy` is
+        taken as policy_returns takes it: (params (K, P), spec), an nn.Sequential or a list of K of one architecture, with
+        `kind`, out_scale, shift, scale and use_freewind.  process=None takes the env's wind_process and its distribution's
+        speed bounds, exactly as controller_scenarios does; an env without wind_process must be given `process` (and may be
+        given `bounds`, default 3 to 28 m/s).  {"yaw": actions[:, k, m, h]} is what to give `step` to replay policy k under
+        member m.  Works on any episode kind (held wind, file series, generated): only the current wind is read.  Returns
+        torch CUDA tensors when the env returns torch; the env's yaw state, accumulators, wind and buffers are read, never
+        changed."""
+        from . import policy as P
+
+        if type(self.reward_shaper).__name__ != "DoNothingReward":
+            raise ValueError("policy_scenarios needs the plain reward (DoNothingReward): the return of a shaped reward is "
+                             "not defined here")
+        if process is None:
+            if self._wind_process is None:
+                raise ValueError("policy_scenarios needs a wind process: this env was built without wind_process, so pass "
+                                 "process=dict(ws_revert=, ws_sigma=, wd_revert=, wd_sigma=, wd_ramp=)")
+            process = self._wind_process
+            if bounds is None and self._wind_dist is not None:
+                bounds = (float(self._wind_dist.get("ws_lo", 3.0)), float(self._wind_dist.get("ws_hi", 28.0)))
+        if bounds is None:
+            bounds = (3.0, 28.0)
+        if isinstance(policy, tuple) and len(policy) == 2 and isinstance(policy[1], dict):
+            params, spec = policy
+        else:
+            if kind is None:
+                raise ValueError('a torch module needs kind="central" or kind="shared"')
+            params, spec = P.policy_from_torch(policy, kind, out_scale=out_scale, shift=shift, scale=scale, use_freewind=use_freewind)
+        if self.return_torch:
+            params = self._to_device(params)
+            anchor = None if anchor is None else self._to_device(anchor).double()
+        return self.fi.policy_scenarios(params, spec, horizon, members, process, seed=seed, gamma=gamma, tail=tail,
+                                        risk_weight=risk_weight, anchor=anchor, bounds=bounds, farms=farms, strict=strict,
+                                        max_eval_farms=max_eval_farms, want=want)
+
     def _series_keyword(self, name, wind, steps):
         """The wind keyword of counterfactual_rewards / lookahead_returns: None or "series"; a time-series episode needs
         "series", any other episode None."""
