@@ -165,15 +165,17 @@ def _freeze(d):
     return d
 
 
-@functools.lru_cache(maxsize=None)
-def case(name):
-    """The inputs of a case: layout, winds, env state (some turbines at the upper yaw bound, accumulators on both sides of the
-    budget gate), the K parameter vectors (uniform, scaled by 1 / sqrt(in)), the spec with a normalisation that brings every
-    input to order one, and — where the case has one — a wind per step whose direction crosses 0 / 360."""
+def build(name, row, inputs=None):
+    """The inputs of the case `row` describes (a row of CASES, or one of another module's table in the same format): layout,
+    winds, env state (some turbines at the upper yaw bound, accumulators on both sides of the budget gate), the K parameter
+    vectors (uniform, scaled by 1 / sqrt(in)), the spec with a normalisation that brings every input to order one, and — where
+    the case has one — a wind per step whose direction crosses 0 / 360.  `inputs` = (x, y, ws, wd) replaces
+    yawopt_ref.gpu_input(layout) where the row's layout is not one of its names."""
     from wfcrl_env_amd import policy as P
 
-    layout, B, kind, hidden, act, final, fw, discrete, K, H, per_step, seed = CASES[name]
-    x, y, ws, wd = yawopt_ref.gpu_input(layout)
+    layout, B, kind, hidden, act, final, fw, discrete, K, H, per_step, seed = row
+    x, y, ws, wd = yawopt_ref.gpu_input(layout) if inputs is None else inputs
+    assert len(ws) >= B and len(wd) >= B, "fewer winds than farms"
     ws, wd = np.array(ws[:B], np.float64), np.array(wd[:B], np.float64)
     N = len(x)
     rng = np.random.default_rng(seed)
@@ -209,7 +211,17 @@ def case(name):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name):
-    c = case(name)
+def case(name):
+    """The inputs of a case of CASES: `build` of its row."""
+    return build(name, CASES[name])
+
+
+def reference_of(c):
+    """The reference rollout of a case `build` made, frozen."""
     return _freeze(rollout(c["x"], c["y"], c["ws"], c["wd"], c["state"], c["params"], c["spec"], c["H"], c["env"], c["gamma"], LOAD_COEF,
                            wind=c["wind"]))
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    return reference_of(case(name))

@@ -46,14 +46,11 @@ def rollouts(c, ws, wd, M, tail, lam, process, seed, anchor=None, bounds=(3.0, 2
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def case(name):
-    """The inputs of a case: the policy case (layout, env state, K parameter vectors, spec, H), and the ensemble's: the current
-    wind — the policy case's, with the last two farms turned to 359.5 and 0.5 degrees, so that their paths cross 0 / 360 —,
-    bounds whose lower one lies 0.05 m/s below the slowest farm's current speed, so that a stored speed of it is clipped, and
-    an anchor per farm for the runs that take one."""
-    base, members, tail = CASES[name]
-    c = policy_ref.case(base)
+def build(name, c, members, tail, process=PROCESS):
+    """The inputs of an ensemble case over the policy case `c` (policy_ref.build's dict: layout, env state, K parameter vectors,
+    spec, H), and the ensemble's: the current wind — the policy case's, with the last two farms turned to 359.5 and 0.5 degrees,
+    so that their paths cross 0 / 360 —, bounds whose lower one lies 0.05 m/s below the slowest farm's current speed, so that a
+    stored speed of it is clipped, and an anchor per farm for the runs that take one."""
     ws, wd = np.array(c["ws"]), np.array(c["wd"])
     wd[-2:] = (359.5, 0.5)
     bounds = (float(ws.min()) - 0.05, 28.0)
@@ -61,11 +58,22 @@ def case(name):
     anchor = np.stack([ws * rng.uniform(0.9, 1.1, ws.size), wd + rng.uniform(-5.0, 5.0, ws.size)], axis=1)
     for a in (ws, wd, anchor):
         a.setflags(write=False)
-    return dict(name=name, c=c, ws=ws, wd=wd, M=members, tail=tail, lam=LAM, process=PROCESS, seed=SEED, bounds=bounds, anchor=anchor,
+    return dict(name=name, c=c, ws=ws, wd=wd, M=members, tail=tail, lam=LAM, process=process, seed=SEED, bounds=bounds, anchor=anchor,
                 B=c["B"], N=c["N"], K=c["K"], H=c["H"])
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name):
-    s = case(name)
+def case(name):
+    """The inputs of a case of CASES: `build` over its policy_ref case."""
+    base, members, tail = CASES[name]
+    return build(name, policy_ref.case(base), members, tail)
+
+
+def reference_of(s):
+    """The reference of a case `build` made, frozen."""
     return policy_ref._freeze(rollouts(s["c"], s["ws"], s["wd"], s["M"], s["tail"], s["lam"], s["process"], s["seed"], None, s["bounds"]))
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    return reference_of(case(name))

@@ -21,23 +21,15 @@ import pytest
 import credit_ref
 import lookahead_ref
 import parity
+import policy_links as links
 import policy_ref as pr
 
 pytestmark = pytest.mark.gpu
 
 WANT = ("returns", "rewards", "farm_power", "actions", "observations", "final_yaw", "gated", "best")
-LA_WANT = ("returns", "rewards", "farm_power", "final_yaw")
+LA_WANT = links.LA_WANT
 MODES = (True, False)
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+_bits, _same = links.bits, links.same  # (the link checks themselves are tests/policy_links.py's, shared with the wide cases)
 
 
 def _handle(c, state=True, discrete=None):
@@ -86,19 +78,7 @@ def test_actions_are_the_network_of_the_observations(name, strict):
               "final_yaw": ((B, K, N), np.float32), "gated": ((B, K), np.int32), "best": ((B,), np.int32)}
     for k, (s, d) in shapes.items():
         assert got[k].shape == s and got[k].dtype == d, k
-    for k in range(K):
-        want, margin = pr.actions_from_observations(c["params"][k], c["spec"], got["observations"][:, k], N, c["env"]["discrete"])
-        dev = got["actions"][:, k]
-        if c["env"]["discrete"]:
-            print(f"{name} policy {k}: smallest gap between a turbine's two best outputs {margin.min():.3e}")
-            assert (margin > 1e-9).all()
-            assert np.array_equal(dev, want)
-        elif "tanh" in (c["spec"]["activation"] if len(c["spec"]["widths"]) > 2 else None, c["spec"]["final"]):
-            ulp = np.spacing(np.abs(want)).astype(np.float32)
-            print(f"{name} policy {k}: actions that differ from the reference's by one float32 ulp: {(dev != want).sum()} of {dev.size}")
-            assert (np.abs(dev.astype(np.float64) - want.astype(np.float64)) <= ulp).all()
-        else:
-            assert np.array_equal(_bits(dev), _bits(want)), (name, k, np.abs(dev - want).max())
+    links.network_link(c, name, got["observations"], got["actions"])
     assert (got["actions"] != (1.0 if c["env"]["discrete"] else 0.0)).mean() > (0.25 if c["env"]["discrete"] else 0.5)  # (the policies move)
 
 
@@ -110,18 +90,9 @@ def test_yaw_and_gates_are_the_walk_of_the_actions(name, strict):
     wind the row was solved under.  The env state is unchanged by the call."""
     c = pr.case(name)
     got, _, before, after = _device(name, strict)
-    N, K = c["N"], c["K"]
-    yaw, gated, final = lookahead_ref.trajectories(c["state"], got["actions"], c["env"])
-    assert np.array_equal(_bits(got["final_yaw"]), _bits(final["yaw"]))
-    prev = np.concatenate([np.broadcast_to(c["state"]["yaw"][:, None, None], yaw[:, :, :1].shape), yaw[:, :, :-1]], axis=2)
-    assert np.array_equal(_bits(got["observations"][..., :N]), _bits(prev))
-    assert np.array_equal(got["gated"], gated.sum(axis=(2, 3)))
+    gated = links.walk_link(c, got)
     if c["H"] > 1 and name != "row3_shared":
         assert (gated[:, :, 1:] & ~gated[:, :, :-1]).any()  # a gate closes inside the horizon
-    held = np.stack([c["ws"], c["wd"]], axis=1)[:, None]
-    wind = np.repeat(held, c["H"], axis=1) if c["wind"] is None else c["wind"]
-    seen = np.concatenate([held, wind[:, :-1]], axis=1).astype(np.float32)  # (B, H, 2): observation h holds wind h - 1
-    assert np.array_equal(got["observations"][..., 3 * N:], np.broadcast_to(seen[:, None], got["observations"][..., 3 * N:].shape))
     for k in before:
         assert np.array_equal(before[k], after[k]), k
 
@@ -134,11 +105,9 @@ def test_lookahead_of_the_actions_gives_the_same_bits(name, strict):
     among equals; the return is the discounted sum of the device's own rewards."""
     c = pr.case(name)
     got, la = _device(name, strict)[:2]
-    for k in range(c["K"]):
-        for key in LA_WANT:
-            assert _same(got[key][:, k:k + 1], la[k][key]), (name, strict, k, key)
-    assert np.array_equal(got["best"], np.argmax(got["returns"], axis=1))
-    assert np.array_equal(got["returns"], lookahead_ref.discounted(got["rewards"], c["gamma"]))
+    assert len(la) == c["K"]
+    links.lookahead_link(name, got, dict(enumerate(la)), strict)
+    links.returns_link(c, got)
 
 
 @pytest.mark.parametrize("name", pr.NAMES)
@@ -146,29 +115,7 @@ def test_strict_local_wind_and_rewards_against_the_oracle(name):
     """Link 4: every float64 solve within the step's contract of the oracle at the device's yaw of that step — the local wind
     blocks of the observations under parity.TOL_F64's wind_speed / wind_dir tolerances, every reward and farm power under
     the bound that follows from it."""
-    from oracle import c_oracle
-
-    c = pr.case(name)
-    got = _device(name, True)[0]
-    B, N, K, H = c["B"], c["N"], c["K"], c["H"]
-    ref = lookahead_ref.lookahead(c["x"], c["y"], c["ws"], c["wd"], c["state"], got["actions"], c["env"], c["gamma"], pr.LOAD_COEF, wind=c["wind"])
-    shape = ref["rewards"].shape
-    b = credit_ref.bound(ref["out"], ref["wr_rows"], pr.LOAD_COEF, parity.TOL_F64).reshape(shape)
-    pb = credit_ref.power_bound(ref["out"], parity.TOL_F64).reshape(shape)
-    er, ep = np.abs(got["rewards"] - ref["rewards"]), np.abs(got["farm_power"] - ref["farm_power"])
-    print(f"{name}: largest error / bound: reward {(er / b).max():.3f}, farm power {(ep / pb).max():.3f}")
-    assert (er <= b).all() and (ep <= pb).all()
-    # the local wind of observation h: the solve of the yaw it holds, under the wind it holds (in float64: not the float32 copy)
-    obs = got["observations"]
-    held = np.stack([c["ws"], c["wd"]], axis=1)[:, None]
-    wind = np.repeat(held, H, axis=1) if c["wind"] is None else c["wind"]
-    seen = np.repeat(np.concatenate([held, wind[:, :-1]], axis=1)[:, None], K, axis=1).reshape(-1, 2)
-    out = c_oracle.farm_step_batch(c["x"], c["y"], seen[:, 0], seen[:, 1], obs[..., :N].reshape(-1, N).astype(np.float64), None)
-    rws, rwd = np.asarray(out["wind_speed"], np.float64), np.asarray(out["wind_direction"], np.float64)
-    ews = np.abs(obs[..., N:2 * N].reshape(-1, N) - rws) / parity._ws_scale(rws, rws.shape[0])
-    ewd = np.abs(obs[..., 2 * N:3 * N].reshape(-1, N) - rwd)
-    print(f"{name}: largest local wind error / tolerance: speed {ews.max() / parity.TOL_F64['ws']:.3f}, direction {ewd.max() / parity.TOL_F64['wd']:.3f}")
-    assert (ews <= parity.TOL_F64["ws"]).all() and (ewd <= parity.TOL_F64["wd"]).all()
+    links.oracle_link(pr.case(name), name, _device(name, True)[0])
 
 
 @pytest.mark.parametrize("discrete", [False, True])

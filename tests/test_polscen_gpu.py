@@ -17,6 +17,7 @@ import functools
 import numpy as np
 import pytest
 
+import policy_links as links
 import policy_ref as pr
 import polscen_ref as sr
 import scenario_ref
@@ -33,14 +34,7 @@ PROCESS = dict(zip(KEYS, sr.PROCESS))
 STILL = dict(zip(KEYS, sr.STILL))
 
 
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+_bits, _same = links.bits, links.same  # (the network link itself is tests/policy_links.py's, shared with test_policy_gpu.py)
 
 
 def _handle(s, state=True):
@@ -146,19 +140,7 @@ def test_actions_are_the_network_of_the_observations(name, strict):
     s = sr.case(name)
     c = s["c"]
     got = _device(name, strict)[0]
-    N = s["N"]
-    for k in range(s["K"]):
-        want, margin = pr.actions_from_observations(c["params"][k], c["spec"], got["observations"][:, k], N, c["env"]["discrete"])
-        dev = got["actions"][:, k]
-        if c["env"]["discrete"]:
-            assert (margin > 1e-9).all()
-            assert np.array_equal(dev, want)
-        elif "tanh" in (c["spec"]["activation"] if len(c["spec"]["widths"]) > 2 else None, c["spec"]["final"]):
-            ulp = np.spacing(np.abs(want)).astype(np.float32)
-            print(f"{name} policy {k}: actions that differ from the reference's by one float32 ulp: {(dev != want).sum()} of {dev.size}")
-            assert (np.abs(dev.astype(np.float64) - want.astype(np.float64)) <= ulp).all()
-        else:
-            assert np.array_equal(_bits(dev), _bits(want)), (name, k)
+    links.network_link(c, name, got["observations"], got["actions"])
     assert _same(got["first_action"], np.ascontiguousarray(got["actions"][:, :, 0, 0]))
     for m in range(s["M"]):
         assert _same(np.ascontiguousarray(got["actions"][:, :, m, 0]), got["first_action"]), m
