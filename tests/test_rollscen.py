@@ -72,8 +72,10 @@ def test_rollscen_kernels_have_no_private_segment(tmp_path):
     assert "wf_scenario_reduce.h" in src and "wf_scenario_statistics(a," in src
     scen = open(os.path.join(csrc, "scenario", "wf_scenario_kernels.hip")).read()
     assert "wf_scenario_reduce.h" in scen and "wf_scenario_statistics(a," in scen and "rank +=" not in scen and "rank +=" not in src
+    ens = open(os.path.join(csrc, "ensemble", "wf_ensemble.h")).read()  # (the path walk is the ensemble's: the streams are named there)
+    assert "wf_ensemble_tiles(" in src and "wf_ensemble_tiles(" in scen and "ensemble/wf_ensemble.h" in mk
     for stream in (S.STREAM_RATE, S.STREAM_WS, S.STREAM_WD):
-        assert re.search(r"\b%du\b" % stream, src), stream
+        assert re.search(r"\b%du\b" % stream, ens) and not re.search(r"\b%du\b" % stream, src), stream
 
 
 def test_one_still_member_is_the_rollout_under_the_held_wind():

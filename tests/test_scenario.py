@@ -41,19 +41,24 @@ def test_scenario_header_is_bound_and_exported():
 
 def test_scenario_kernels_have_no_private_segment(tmp_path):
     """The two glue kernels, compiled with the Makefile's flags: exactly these two, no private segment, no spilled
-    register, no out-of-line call.  Metadata only.  The streams they draw from are named by no other kernel file."""
+    register, no out-of-line call.  Metadata only.  The streams they draw from are named by the ensemble's header, which the
+    kernel file takes through its own (tests/test_ensemble.py: by no other file)."""
     mk = makefile()
     assert "SCENARIOOBJ = scenario/wf_scenario_kernels.o scenario/wf_scenario_abi.o" in mk and "$(SCENARIOOBJ): %.o: %.hip" in mk
     assert re.search(r"^\$\(OUT\):.*\$\(SCENARIOOBJ\)", mk, flags=re.M) and re.search(r"^\trm -f .*scenario/\*\.o", mk, flags=re.M)
     seen, text = compile_kernels("scenario/wf_scenario_kernels.hip", tmp_path)
     assert_no_private_segment(seen, KERNELS)
     assert "s_swappc_b64" not in text
-    src = open(os.path.join(ROOT, "wfcrl-env_amd", "csrc", "scenario", "wf_scenario_kernels.hip")).read()
+    csrc = os.path.join(ROOT, "wfcrl-env_amd", "csrc")
+    src = open(os.path.join(csrc, "scenario", "wf_scenario_kernels.hip")).read()
+    ens = open(os.path.join(csrc, "ensemble", "wf_ensemble.h")).read()
     for stream in (S.STREAM_RATE, S.STREAM_WS, S.STREAM_WD):
-        assert re.search(r"\b%du\b" % stream, src), stream
-    for header in ("../wf_philox.h", "../ext/wf_deviate.h", "wf_scenario.h"):
-        assert '#include "%s"' % header in src, header
-    assert '#include "../ext/wf_ext_kernels.h"' in open(os.path.join(ROOT, "wfcrl-env_amd", "csrc", "scenario", "wf_scenario.h")).read()
+        assert re.search(r"\b%du\b" % stream, ens) and not re.search(r"\b%du\b" % stream, src), stream
+    for header in ("../wf_philox.h", "../ext/wf_deviate.h", "../ext/wf_ext_kernels.h"):
+        assert '#include "%s"' % header in ens, header
+    assert '#include "wf_scenario.h"' in src and "wf_ensemble_tiles(" in src
+    own = open(os.path.join(csrc, "scenario", "wf_scenario.h")).read()
+    assert '#include "../ext/wf_ext_kernels.h"' in own and '#include "../ensemble/wf_ensemble.h"' in own
 
 
 def test_zero_sigmas_and_zero_ramp_are_the_held_wind_in_every_member():

@@ -17,6 +17,20 @@ def _is_torch(a) -> bool:
     return type(a).__module__.startswith("torch")
 
 
+PROCESS = ("ws_revert", "ws_sigma", "wd_revert", "wd_sigma", "wd_ramp")  # the keys of a wind process dict (include/wfwindgen.h)
+
+
+def _wind_process(process, who=None) -> WindProcess:
+    """A wind process dict as the library takes it (missing keys: 0).  `who`: the public method that needs one and names itself
+    in the refusal of None (generate_wind's process is not optional: no name)."""
+    if process is None and who:
+        raise ValueError(f"{who} needs a wind process: dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp)")
+    unknown = set(process) - set(PROCESS)
+    if unknown:
+        raise ValueError(f"unknown wind process parameter(s): {sorted(unknown)}")
+    return WindProcess(**{k: float(process.get(k, 0.0)) for k in PROCESS})
+
+
 def _is_series(wind) -> bool:
     """wind="series": the series-ahead mode of lookahead, plan and credit (include/wfseries.h)."""
     return isinstance(wind, str) and wind == "series"
@@ -408,11 +422,7 @@ class WfStep:
           kernel    None: the library's choice; "serial" (a thread per farm) or "tiled" — the same bits, for measurements"""
         if kernel not in (None, "serial", "tiled"):
             raise ValueError('kernel must be None, "serial" or "tiled"')
-        keys = ("ws_revert", "ws_sigma", "wd_revert", "wd_sigma", "wd_ramp")
-        unknown = set(process) - set(keys)
-        if unknown:
-            raise ValueError(f"unknown wind process parameter(s): {sorted(unknown)}")
-        p = WindProcess(**{k: float(process.get(k, 0.0)) for k in keys})
+        p = _wind_process(process)
         d = None
         if dist is not None:
             base = dict(ws_scale=8.0, ws_shape=8.0, ws_lo=3.0, ws_hi=28.0, wd_mean=270.0, wd_std=20.0, wd_lo=0.0, wd_hi=360.0)
@@ -1686,6 +1696,37 @@ class _Ext:
         return a, a.ctypes.data
 
     @staticmethod
+    def _members_tail_bounds(members, tail, bounds):
+        """(M, the tail q — all M members when `tail` is None —, ws_lo, ws_hi) of a wind ensemble's arguments."""
+        M = int(members)
+        q = M if tail is None else int(tail)
+        ws_lo, ws_hi = (float(v) for v in bounds)
+        return M, q, ws_lo, ws_hi
+
+    @staticmethod
+    def _f64(a, shape, name, what, on_device, like):
+        """(the array kept alive, its pointer) of a float64 input of `shape`, or (None, None): a torch CUDA tensor (made on
+        the device of `like` from anything else) on the device path, a NumPy array else.  `what` ends the refusal of a shape."""
+        if a is None:
+            return None, None
+        if on_device:
+            import torch
+
+            if not _is_torch(a):
+                a = torch.as_tensor(np.asarray(a, np.float64), device=like.device)
+            assert a.is_cuda and a.dtype == torch.float64, name
+            a = a.contiguous()
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+        if tuple(a.shape) != shape:
+            raise ValueError(f"{name} must be {what}")
+        return a, (a.data_ptr() if on_device else a.ctypes.data)
+
+    def _anchor(self, anchor, n, on_device, like):
+        """... of the (n, 2) anchor of a wind ensemble."""
+        return self._f64(anchor, (n, 2), "anchor", "(n_farms, 2): the (speed, direction) every listed farm's paths revert to", on_device, like)
+
+    @staticmethod
     def _outputs(out, spec, on_device, like=None):
         """The outputs `spec` = {name: (shape, NumPy dtype)} names, and their pointers in spec's order: `out` checked against
         it, or allocated when None — torch CUDA tensors (on the device of `like`) on the device path, NumPy arrays else."""
@@ -2207,16 +2248,10 @@ class _PolScen(_Policy):
         want = (want,) if isinstance(want, str) else tuple(want)
         if not want or any(k not in self.OUTPUTS for k in want):
             raise ValueError("want must name " + ", ".join(self.OUTPUTS[:-1]) + " and / or " + self.OUTPUTS[-1])
-        if process is None:
-            raise ValueError("policy_scenarios needs a wind process: dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp)")
-        unknown = set(process) - set(_Scenario.PROCESS)
-        if unknown:
-            raise ValueError(f"unknown wind process parameter(s): {sorted(unknown)}")
-        p = WindProcess(**{k: float(process.get(k, 0.0)) for k in _Scenario.PROCESS})
+        p = _wind_process(process, "policy_scenarios")
         self._set_network(spec)
-        H, M = int(horizon), int(members)
-        q = M if tail is None else int(tail)
-        ws_lo, ws_hi = (float(v) for v in bounds)
+        H = int(horizon)
+        M, q, ws_lo, ws_hi = self._members_tail_bounds(members, tail, bounds)
         self._call("config", int(bool(strict)), int(max_eval_farms or 0))
         fa, n, fptr = self._farms(farms)
         on_device = _is_torch(params) or _is_torch(anchor) or (out is not None and any(_is_torch(v) for v in out.values()))
@@ -2237,18 +2272,7 @@ class _PolScen(_Policy):
         if len(tuple(params.shape)) != 2:
             raise ValueError("params must be (K, P): a parameter vector per policy")
         K, P = int(params.shape[0]), int(params.shape[1])
-        aptr = None
-        if anchor is not None:
-            if on_device:
-                if not _is_torch(anchor):
-                    anchor = torch.as_tensor(np.asarray(anchor, np.float64), device=like.device)
-                assert anchor.is_cuda and anchor.dtype == torch.float64, "anchor"
-                anchor = anchor.contiguous()
-            else:
-                anchor = np.ascontiguousarray(anchor, dtype=np.float64)
-            if tuple(anchor.shape) != (n, 2):
-                raise ValueError("anchor must be (n_farms, 2): the (speed, direction) every listed farm's paths revert to")
-            aptr = anchor.data_ptr() if on_device else anchor.ctypes.data
+        anchor, aptr = self._anchor(anchor, n, on_device, like)
         f8, f4, i4 = np.float64, np.float32, np.int32
         shapes = {"expected_returns": ((n, K), f8), "cvar": ((n, K), f8), "score": ((n, K), f8), "member_returns": ((n, K, M), f8),
                   "rewards": ((n, K, M, H), f8), "farm_power": ((n, K, M, H), f8), "wind_paths": ((n, M, H, 2), f8),
@@ -2272,7 +2296,6 @@ class _Scenario(_Ext):
     NAME = "scenario"
     KERNELS = ("layout", "reduce")
     OUTPUTS = ("expected_returns", "cvar", "score", "member_returns", "rewards", "wind_paths", "final_yaw", "best")
-    PROCESS = ("ws_revert", "ws_sigma", "wd_revert", "wd_sigma", "wd_ramp")
 
     def run(self, actions, members, process, seed, gamma, tail, risk_weight, anchor, bounds, farms, strict, max_eval_farms, want, out):
         w = self._w
@@ -2280,15 +2303,8 @@ class _Scenario(_Ext):
         want = (want,) if isinstance(want, str) else tuple(want)
         if not want or any(k not in self.OUTPUTS for k in want):
             raise ValueError("want must name expected_returns, cvar, score, member_returns, rewards, wind_paths, final_yaw and / or best")
-        if process is None:
-            raise ValueError("scenario_returns needs a wind process: dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp)")
-        unknown = set(process) - set(self.PROCESS)
-        if unknown:
-            raise ValueError(f"unknown wind process parameter(s): {sorted(unknown)}")
-        p = WindProcess(**{k: float(process.get(k, 0.0)) for k in self.PROCESS})
-        M = int(members)
-        q = M if tail is None else int(tail)
-        ws_lo, ws_hi = (float(v) for v in bounds)
+        p = _wind_process(process, "scenario_returns")
+        M, q, ws_lo, ws_hi = self._members_tail_bounds(members, tail, bounds)
         self._call("config", int(bool(strict)), int(max_eval_farms or 0))
         fa, n, fptr = self._farms(farms)
         on_device = _is_torch(actions)
@@ -2304,18 +2320,7 @@ class _Scenario(_Ext):
         if len(shape) != 4 or shape[0] != n or shape[3] != N:
             raise ValueError("actions must be (n_farms, K, H, num_turbines): K sequences of H joint actions per listed farm")
         K, H = int(shape[1]), int(shape[2])
-        aptr = None
-        if anchor is not None:
-            if on_device:
-                if not _is_torch(anchor):
-                    anchor = torch.as_tensor(np.array(anchor, np.float64), device=actions.device)
-                assert anchor.is_cuda and anchor.dtype == torch.float64, "anchor"
-                anchor = anchor.contiguous()
-            else:
-                anchor = np.ascontiguousarray(anchor, dtype=np.float64)
-            if tuple(anchor.shape) != (n, 2):
-                raise ValueError("anchor must be (n_farms, 2): the (speed, direction) every listed farm's paths revert to")
-            aptr = anchor.data_ptr() if on_device else anchor.ctypes.data
+        anchor, aptr = self._anchor(anchor, n, on_device, actions)
         shapes = {"expected_returns": ((n, K), np.float64), "cvar": ((n, K), np.float64), "score": ((n, K), np.float64),
                   "member_returns": ((n, K, M), np.float64), "rewards": ((n, K, M, H), np.float64),
                   "wind_paths": ((n, M, H, 2), np.float64), "final_yaw": ((n, K, N), np.float32), "best": ((n,), np.int32)}
@@ -2486,42 +2491,20 @@ class _RollScen(_Rollout):
         want = (want,) if isinstance(want, str) else tuple(want)
         if not want or any(k not in self.OUTPUTS for k in want):
             raise ValueError("want must name " + ", ".join(self.OUTPUTS[:-1]) + " and / or " + self.OUTPUTS[-1])
-        if process is None:
-            raise ValueError("controller_scenarios needs a wind process: dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp)")
-        unknown = set(process) - set(_Scenario.PROCESS)
-        if unknown:
-            raise ValueError(f"unknown wind process parameter(s): {sorted(unknown)}")
-        p = WindProcess(**{k: float(process.get(k, 0.0)) for k in _Scenario.PROCESS})
+        p = _wind_process(process, "controller_scenarios")
         ctl, K = self._controllers(controllers)
-        H, M = int(horizon), int(members)
-        q = M if tail is None else int(tail)
-        ws_lo, ws_hi = (float(v) for v in bounds)
+        H = int(horizon)
+        M, q, ws_lo, ws_hi = self._members_tail_bounds(members, tail, bounds)
         self._call("config", int(bool(strict)), int(max_eval_farms or 0))
         fa, n, fptr = self._farms(farms)
         on_device = _is_torch(anchor) or _is_torch(filter0) or (out is not None and any(_is_torch(v) for v in out.values()))
         like = None
         if on_device:
-            import torch
-
             w._follow_torch_stream()
             like = next(v for v in [anchor, filter0] + list((out or {}).values()) if _is_torch(v))
-
-        def f64(a, shape, name, what):
-            if a is None:
-                return None, None
-            if on_device:
-                if not _is_torch(a):
-                    a = torch.as_tensor(np.asarray(a, np.float64), device=like.device)
-                assert a.is_cuda and a.dtype == torch.float64, name
-                a = a.contiguous()
-            else:
-                a = np.ascontiguousarray(a, dtype=np.float64)
-            if tuple(a.shape) != shape:
-                raise ValueError(f"{name} must be {what}")
-            return a, (a.data_ptr() if on_device else a.ctypes.data)
-
-        anchor, aptr = f64(anchor, (n, 2), "anchor", "(n_farms, 2): the (speed, direction) every listed farm's paths revert to")
-        filter0, f0ptr = f64(filter0, (n, K, 2), "filter0", "(n_farms, K, 2): the (speed, direction) every controller's filter starts from")
+        anchor, aptr = self._anchor(anchor, n, on_device, like)
+        filter0, f0ptr = self._f64(filter0, (n, K, 2), "filter0", "(n_farms, K, 2): the (speed, direction) every controller's filter starts from",
+                                   on_device, like)
         f8, f4, i4 = np.float64, np.float32, np.int32
         shapes = {"expected_returns": ((n, K), f8), "cvar": ((n, K), f8), "score": ((n, K), f8), "member_returns": ((n, K, M), f8),
                   "rewards": ((n, K, M, H), f8), "wind_paths": ((n, M, H, 2), f8), "actions": ((n, K, M, H, N), f4),
@@ -2760,15 +2743,9 @@ class _ScenPlan(_Ext):
         want = (want,) if isinstance(want, str) else tuple(want)
         if not want or any(k not in self.OUTPUTS for k in want):
             raise ValueError("want must name " + ", ".join(self.OUTPUTS[:-1]) + " and / or " + self.OUTPUTS[-1])
-        if process is None:
-            raise ValueError("plan_scenarios needs a wind process: dict(ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp)")
-        unknown = set(process) - set(_Scenario.PROCESS)
-        if unknown:
-            raise ValueError(f"unknown wind process parameter(s): {sorted(unknown)}")
-        proc = WindProcess(**{k: float(process.get(k, 0.0)) for k in _Scenario.PROCESS})
-        H, K, E, M = int(horizon), int(candidates), int(elites), int(members)
-        q = M if tail is None else int(tail)
-        ws_lo, ws_hi = (float(v) for v in bounds)
+        proc = _wind_process(process, "plan_scenarios")
+        H, K, E = int(horizon), int(candidates), int(elites)
+        M, q, ws_lo, ws_hi = self._members_tail_bounds(members, tail, bounds)
         if sigma is None:
             step = getattr(w, "_env_yaw_step", 5.0)
             sigma = (step, 0.5 * step, 0.25 * step)
@@ -2782,18 +2759,8 @@ class _ScenPlan(_Ext):
 
             w._follow_torch_stream()
             like = next(v for v in [anchor, mean] + list((out or {}).values()) if _is_torch(v))
-        aptr = mptr = None
-        if anchor is not None:
-            if on_device:
-                if not _is_torch(anchor):
-                    anchor = torch.as_tensor(np.array(anchor, np.float64), device=like.device)
-                assert anchor.is_cuda and anchor.dtype == torch.float64, "anchor"
-                anchor = anchor.contiguous()
-            else:
-                anchor = np.ascontiguousarray(anchor, dtype=np.float64)
-            if tuple(anchor.shape) != (n, 2):
-                raise ValueError("anchor must be (n_farms, 2): the (speed, direction) every listed farm's paths revert to")
-            aptr = anchor.data_ptr() if on_device else anchor.ctypes.data
+        anchor, aptr = self._anchor(anchor, n, on_device, like)
+        mptr = None
         if mean is not None:
             if on_device:
                 if not _is_torch(mean):

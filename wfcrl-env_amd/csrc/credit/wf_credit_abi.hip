@@ -76,10 +76,7 @@ int wf_credit_run(wf_credit* c, int base_kind, const float* base, int alt_kind, 
   const float *d_base = nullptr, *d_alt = nullptr;
   double *d_rew = nullptr, *d_fp = nullptr, *d_dif = nullptr;
   staging st(c, c->d_stage, on_device);
-  WfCreditEnv env{};
-  env.yaw = h->d_env_yaw; env.acc = h->d_env_acc; env.moves = h->d_env_moves;
-  env.lo = h->env.yaw_lo; env.hi = h->env.yaw_hi; env.step = h->env.yaw_step;
-  env.rate = h->env.actuator_rate; env.dt = h->env.dt; env.budget = h->env.budget; env.discrete = h->env.discrete;
+  const WfCreditEnv env = env_view(h);
   row_policy k;
   k.what = "counterfactual rewards serve"; k.name = "wf_credit_run";
   k.rows_msg = kRowsMsg; k.loads = true;

@@ -9,6 +9,7 @@
 // A new extension starts here: derive its object from ext_base, declare its buffers as dev_buf, and call these.
 #pragma once
 #include <cassert>
+#include <cmath>
 #include <functional>
 
 #include "../wf_handle.h"
@@ -95,6 +96,10 @@ struct farm_list {
   std::vector<int> host;
 };
 
+// what the checks of a wind process and of the ensemble's statistics (windgen/, ensemble/wf_ensemble_host.h) ask of a number
+inline bool in_unit(double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; }
+inline bool non_negative(double v) { return std::isfinite(v) && v >= 0.0; }
+
 // What a call asks of the parent: layout and batch, ONE layout, one turbine definition and, with `call`, a wind.  `what` is
 // the extension's phrase with its verb ("yaw optimisation serves"), `call` the entry point's name (null: no wind needed).
 int check_parent(ext_base* x, const char* what, const char* call);
@@ -135,6 +140,15 @@ struct staging {
   int begin();  // reserves the buffer once, gives every array its place in it and enqueues the inputs' copies
   int end();    // after the run: a host caller's outputs come back, and the stream is drained
 };
+
+// the parent's fused env as the kernels see it: parameters by value, state by (read-only) pointer
+inline WfEnvView env_view(const wf_handle* h) {
+  WfEnvView e{};
+  e.yaw = h->d_env_yaw; e.acc = h->d_env_acc; e.moves = h->d_env_moves;
+  e.lo = h->env.yaw_lo; e.hi = h->env.yaw_hi; e.step = h->env.yaw_step;
+  e.rate = h->env.actuator_rate; e.dt = h->env.dt; e.budget = h->env.budget; e.discrete = h->env.discrete;
+  return e;
+}
 
 // an event on the parent's stream, from the pool
 int record(ext_base* x);

@@ -10,6 +10,10 @@
 
 #include "../wf_f64_math.h"
 
+// The value is held in a vector register from here on.  For block-uniform values that, held in scalar registers across a
+// register-hungry stretch (the Philox rounds of a draw, the staged row rewards), would not fit: spilled scalar registers.
+#define WF_IN_VGPR(v) asm volatile("" : "+v"(v))
+
 // which farm a slot works on: farms[base + s] (or base + s without a list), s = slot for the chunk's own slots, 0 beyond
 struct WfSlots {
   const int* farms;  // device copy of the caller's list, or null

@@ -79,10 +79,7 @@ int wf_lookahead_run(wf_lookahead* l, const float* actions, int K, int H, const 
   float* d_fy = nullptr;
   int* d_best = nullptr;
   staging st(l, l->d_stage, on_device);
-  WfEnvView env{};
-  env.yaw = h->d_env_yaw; env.acc = h->d_env_acc; env.moves = h->d_env_moves;
-  env.lo = h->env.yaw_lo; env.hi = h->env.yaw_hi; env.step = h->env.yaw_step;
-  env.rate = h->env.actuator_rate; env.dt = h->env.dt; env.budget = h->env.budget; env.discrete = h->env.discrete;
+  const WfEnvView env = env_view(h);
   row_policy k;
   k.what = "look-ahead returns serve"; k.name = "wf_lookahead_run";
   k.rows_msg = kRowsMsg; k.loads = true;

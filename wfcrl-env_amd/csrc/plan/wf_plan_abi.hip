@@ -141,9 +141,7 @@ int wf_plan_run(wf_plan* p, int H, int K, int E, int I, const double* sigma, uns
     r.load_coef = h->env.load_coef; r.gamma = gamma; r.seed = seed;
     r.ws = h->d_ws; r.wd = h->d_wd;
     r.ws_prev = (!ahead && h->ws_prev_valid && h->d_ws_prev) ? h->d_ws_prev : nullptr;  // read, not consumed; series-ahead: the current speed
-    r.env.yaw = h->d_env_yaw; r.env.acc = h->d_env_acc; r.env.moves = h->d_env_moves;
-    r.env.lo = h->env.yaw_lo; r.env.hi = h->env.yaw_hi; r.env.step = h->env.yaw_step;
-    r.env.rate = h->env.actuator_rate; r.env.dt = h->env.dt; r.env.budget = h->env.budget; r.env.discrete = 0;
+    r.env = env_view(h); r.env.discrete = 0;
     r.yaw = b.d_yaw; r.ews = b.d_wind; r.ewd = b.d_wind + Ev;
     r.power_ev = b.d_pow; r.load_ev = b.d_load;
     r.cand = p->d_cand; r.best = p->d_best; r.mu = p->d_mu;

@@ -104,14 +104,6 @@ int policy_network_fits(ext_base* p, const wf_handle* h, WfPolicyNet& net, int P
   return WF_OK;
 }
 
-WfEnvView policy_env_view(const wf_handle* h) {
-  WfEnvView e{};
-  e.yaw = h->d_env_yaw; e.acc = h->d_env_acc; e.moves = h->d_env_moves;
-  e.lo = h->env.yaw_lo; e.hi = h->env.yaw_hi; e.step = h->env.yaw_step;
-  e.rate = h->env.actuator_rate; e.dt = h->env.dt; e.budget = h->env.budget; e.discrete = h->env.discrete;
-  return e;
-}
-
 }  // namespace wfi
 
 extern "C" {
@@ -203,7 +195,7 @@ int wf_policy_run(wf_policy* p, const float* params, int K, int P, int H, const 
     r = WfPolicyRun{};
     r.net = net; r.pl = plan;
     r.N = N; r.K = K; r.H = H; r.M = 1;  // (no ensemble: paths and first_action stay null)
-    r.env = policy_env_view(h);
+    r.env = env_view(h);
     r.ws = h->d_ws; r.wd = h->d_wd; r.wind_stride = h->wind_count == 1 ? 0 : 1;
     r.ws_prev = (h->ws_prev_valid && h->d_ws_prev) ? h->d_ws_prev : nullptr;  // read, not consumed
     r.load_coef = h->env.load_coef; r.gamma = gamma;

@@ -1,7 +1,7 @@
 // wf_policy_host.h — the host-side checks of a network that the policy extension (wf_policy_abi.hip) and the extension that
 // runs the same network over a wind ensemble (polscen/wf_polscen_abi.hip) share, so that neither restates the other's:
-// what wf_policy_set_network validates and lays out, what a run checks of the network against its parent, and the parent's env
-// as the kernels see it.  Defined in wf_policy_abi.hip.
+// what wf_policy_set_network validates and lays out, and what a run checks of the network against its parent.  Defined in
+// wf_policy_abi.hip.
 #pragma once
 #include <vector>
 
@@ -18,8 +18,5 @@ int policy_network(ext_base* x, int kind, int n_layers, const int* widths, int a
 // what a run checks of a network against its parent h: the input width of its kind, the output width of the env's action
 // encoding, the parameter count P; sets net.discrete
 int policy_network_fits(ext_base* x, const wf_handle* h, WfPolicyNet& net, int P);
-
-// the parent's env: parameters by value, state by (read-only) pointer
-WfEnvView policy_env_view(const wf_handle* h);
 
 }  // namespace wfi

@@ -10,18 +10,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../../../include/wfpolscen.h"
+#include "../ensemble/wf_ensemble.h"
 #include "../ext/wf_ext_kernels.h"
 #include "../policy/wf_policy.h"
 
 struct WfPolscenPathsArgs {
   WfSlots sl;
-  const double *ws, *wd;  // the parent's wind: (S_c, D_c)
-  int wind_stride;        // 0 shared, 1 per farm
-  int M, H;
-  unsigned long long seed;
-  double ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp;
-  double ws_lo, ws_hi;
-  const double* anchor;   // [n_slots][2] (speed, direction) of this chunk, or null = the farm's current wind
+  WfEnsemble ens;         // the paths: seed, process, bounds, anchor, the parent's wind, M, H
   double* paths;          // [C][M][H][2] the chunk's paths: what the advance kernel reads
   double* wind_paths;     // [n_slots][M][H][2] of this chunk, or null
 };

@@ -15,6 +15,7 @@
 #include "../../../include/wfpolscen.h"
 #include "../../../include/wflookahead.h"
 #include "../../../include/wfscenario.h"
+#include "../ensemble/wf_ensemble_host.h"
 #include "../ext/wf_ext.h"
 #include "../policy/wf_policy_host.h"
 #include "wf_polscen.h"
@@ -54,9 +55,6 @@ namespace {
 
 const char* const kRowsMsg = "max_eval_farms must hold one farm's rows: at least K M";
 const char* const kNoEnv = "no env state: wf_env_config and wf_env_reset come first (the rollouts start at the fused env's state)";
-
-bool in_unit(double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; }
-bool non_negative(double v) { return std::isfinite(v) && v >= 0.0; }
 
 }  // namespace
 
@@ -114,23 +112,14 @@ int wf_polscen_run(wf_polscen* p, const float* params, int K, int P, int H, int 
     if (H < 1 || H > WF_POLSCEN_MAX_H) return ext_fail(p, WF_E_INVALID, "the horizon H must be in 1..64");
     if (K < 1 || K > WF_POLSCEN_MAX_K) return ext_fail(p, WF_E_INVALID, "the number of policies K must be in 1..64");
     if (M < 1 || M > WF_POLSCEN_MAX_MEMBERS) return ext_fail(p, WF_E_INVALID, "the number of members M must be in 1..64");
-    if (tail < 1 || tail > M) return ext_fail(p, WF_E_INVALID, "tail must be in 1..M: the number of lowest member returns the tail mean is over");
-    if (!in_unit(risk_weight)) return ext_fail(p, WF_E_INVALID, "risk_weight must be finite and in [0, 1]");
-    if (!in_unit(gamma)) return ext_fail(p, WF_E_INVALID, "gamma must be finite and in [0, 1]");
+    int rc = check_ensemble_statistics(p, M, tail, risk_weight, gamma);
+    if (rc != WF_OK) return rc;
     if (!params) return ext_fail(p, WF_E_INVALID, "wf_polscen_run: params is NULL");
-    if (!process) return ext_fail(p, WF_E_INVALID, "wf_polscen_run: process is NULL");
-    const wf_wind_process& w = *process;
-    if (!in_unit(w.ws_revert) || !in_unit(w.wd_revert)) return ext_fail(p, WF_E_INVALID, "ws_revert and wd_revert must be in [0, 1]");
-    if (!non_negative(w.ws_sigma) || !non_negative(w.wd_sigma) || !non_negative(w.wd_ramp))
-      return ext_fail(p, WF_E_INVALID, "ws_sigma, wd_sigma and wd_ramp must be finite and >= 0");
-    if (!std::isfinite(ws_lo) || !std::isfinite(ws_hi) || !(ws_lo > 0.0) || !(ws_lo < ws_hi))
-      return ext_fail(p, WF_E_INVALID, "the speed bounds must be finite with 0 < ws_lo < ws_hi");
+    rc = check_ensemble_process(p, "wf_polscen_run", process, ws_lo, ws_hi);
+    if (rc != WF_OK) return rc;
     if (!h->d_env_yaw || !h->d_env_acc || !h->d_env_moves) return ext_fail(p, WF_E_INVALID, kNoEnv);
-    if (anchor && !on_device)
-      for (int i = 0; i < n_farms; ++i)
-        if (!(anchor[2 * i] > 0.0) || !std::isfinite(anchor[2 * i]) || !std::isfinite(anchor[2 * i + 1]))
-          return ext_fail(p, WF_E_INVALID, "the anchor's speed must be > 0 and its direction finite");
-    const int rc = policy_network_fits(p, h, net, P);
+    rc = check_ensemble_anchor(p, anchor, n_farms, on_device);
+    if (rc == WF_OK) rc = policy_network_fits(p, h, net, P);
     if (rc != WF_OK) return rc;
     k.rows = K * M; k.rounds = H + 1;
     return WF_OK;
@@ -170,7 +159,7 @@ int wf_polscen_run(wf_polscen* p, const float* params, int K, int P, int H, int 
     r = WfPolicyRun{};
     r.net = net; r.pl = plan;
     r.N = N; r.K = K; r.H = H; r.M = M;
-    r.env = policy_env_view(h);
+    r.env = env_view(h);
     r.ws = h->d_ws; r.wd = h->d_wd; r.wind_stride = wind_stride;
     r.ws_prev = nullptr;  // step 0 is normalised by the current speed: a pending speed is neither used nor consumed
     r.load_coef = h->env.load_coef; r.gamma = gamma;
@@ -193,14 +182,9 @@ int wf_polscen_run(wf_polscen* p, const float* params, int K, int P, int H, int 
       if (rc != WF_OK) return rc;
     }
     const size_t first = (size_t)sl.base;
-    const wf_wind_process& w = *process;
     WfPolscenPathsArgs pa{};
     pa.sl = sl;
-    pa.ws = h->d_ws; pa.wd = h->d_wd; pa.wind_stride = wind_stride; pa.M = M; pa.H = H;
-    pa.seed = seed;
-    pa.ws_revert = w.ws_revert; pa.ws_sigma = w.ws_sigma; pa.wd_revert = w.wd_revert; pa.wd_sigma = w.wd_sigma; pa.wd_ramp = w.wd_ramp;
-    pa.ws_lo = ws_lo; pa.ws_hi = ws_hi;
-    pa.anchor = d_anchor ? d_anchor + first * 2 : nullptr;
+    pa.ens = ensemble_args(h, M, H, *process, ws_lo, ws_hi, seed, d_anchor, first);
     pa.paths = p->d_paths;
     pa.wind_paths = d_wp ? d_wp + first * M * H * 2 : nullptr;
     WFX_HIP(p, wfk_launch_polscen_paths(&pa, h->stream));

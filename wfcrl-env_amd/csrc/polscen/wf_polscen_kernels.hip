@@ -6,8 +6,8 @@
 // adds, per chunk of C slots, evaluator farm e = (k M + m) C + slot:
 //
 //   wf_polscen_paths_kernel    once, before the begin kernel, A THREAD PER (slot, member): it draws the member's ramp rate
-//                              (stream 16) and walks its H ticks, two deviates per tick (streams 17 and 18), with
-//                              include/wfscenario.h's recursion, clip and wrap in its order of operations, and stores (speed,
+//                              and walks its H ticks, two deviates per tick, with the ensemble's scalar pieces
+//                              (ensemble/wf_ensemble.h: wf_ensemble_rate, wf_ensemble_deviates, wf_ensemble_tick), and stores (speed,
 //                              direction) of tick h + 1 to the chunk's path buffer [C][M][H][2] and to wind_paths.  No LDS:
 //                              M H reaches 4096 pairs of doubles per slot.  A thread's stores are H pairs apart from its
 //                              neighbour's; the kernel runs once per chunk against H + 1 steps.
@@ -17,57 +17,41 @@
 //                              current speed), the member return ret + g r as the policy extension's reduce forms it, kept per
 //                              row for the statistics; rewards and farm_power of the last step, member_returns, gated,
 //                              final_yaw.
-//   wf_polscen_stats_kernel    once, A WORKGROUP PER SLOT: the slot's K M member returns -> LDS; then the scenario reduce's
-//                              statistics in its order (scenario/wf_scenario_reduce.h), in passes of nth / M whole policies:
-//                              thread (k, m) counts its rank — (return, m) ascending — and scatters its return to
-//                              sorted[k][rank]; thread k adds the mean in ascending m and the tail in ascending rank and
-//                              leaves the score in LDS; thread 0 takes the argmax over k ascending, strictly greater wins: the
+//   wf_polscen_stats_kernel    once, A WORKGROUP PER SLOT: the slot's K M member returns -> LDS; then the ensemble's
+//                              statistics (wf_member_statistics over the returns at stride 1), which emit to the outputs and
+//                              leave the score in LDS; thread 0 takes the argmax over k ascending, strictly greater wins: the
 //                              lowest index among equal maxima.
 //
 // No floating-point atomics, no order that depends on scheduling.  Trip counts are run-time values and nothing is indexed by a
 // run-time value in registers: no private segment at any N (tests/test_polscen.py reads the metadata); every barrier sits in
 // block-uniform control flow.  The library is built with -ffp-contract=off: every product and sum of the paths, the return and
 // the statistics is one rounding, as in tests/scenario_ref.py.
-//
-// KNOWN SECOND COPIES: the path walk restates scenario/wf_scenario_kernels.hip's (a third time, after scenplan/),
-// and the rank-and-tail passes wf_scenario_reduce.h's, whose body is tied to rows (k, m, h) of ONE step; those files are left
-// as they were.
 #include <hip/hip_runtime.h>
 
-#include "../ext/wf_deviate.h"
-#include "../wf_philox.h"
 #include "wf_polscen.h"
 
 __global__ __launch_bounds__(256) void wf_polscen_paths_kernel(const WfPolscenPathsArgs a) {
-  const int M = a.M, H = a.H;
+  const int M = a.ens.M, H = a.ens.H;
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= a.sl.C * M) return;
   const int slot = q / M, m = q - slot * M;
   const int b = wf_slot_farm(a.sl, slot);
   const bool writes = slot < a.sl.n_slots;
   const size_t in = writes ? slot : 0;  // the slot's input block
-  const double Sc = a.ws[(size_t)b * a.wind_stride], Dc = a.wd[(size_t)b * a.wind_stride];
-  const double Sa = a.anchor ? a.anchor[in * 2] : Sc, Da = a.anchor ? a.anchor[in * 2 + 1] : Dc;
-  const unsigned long long hi = (unsigned long long)b << 32;
-  unsigned r[4];
-  philox4x32_10(a.seed, hi | (unsigned)m, 16u, r);
-  const double rate = a.wd_ramp * (2.0 * u01(r[0], r[1]) - 1.0);
-  double x = Sc, y = Dc;
+  const WfEnsembleWalk w = wf_ensemble_walk<false>(a.ens, b, in);  // (a thread per member: nothing to pin)
+  const double rate = wf_ensemble_rate(a.ens, b, m);
+  double x = w.Sc, y = w.Dc;
   double* __restrict__ buf = a.paths + (size_t)q * H * 2;
   double* __restrict__ out = (writes && a.wind_paths) ? a.wind_paths + (in * M + m) * H * 2 : nullptr;
   for (int j = 0; j < H; ++j) {
-    const unsigned long long ctr = hi | (unsigned)(m * 64 + j);
-    x = (x + a.ws_revert * (Sa - x)) + a.ws_sigma * wf_deviate(a.seed, ctr, 17u);
-    const double mu = Da + rate * (double)(j + 1);
-    y = (y + a.wd_revert * (mu - y)) + a.wd_sigma * wf_deviate(a.seed, ctr, 18u);
-    double w = fmod(y, 360.0);
-    if (w < 0.0) w += 360.0;
-    const double s = fmin(fmax(x, a.ws_lo), a.ws_hi);
+    double z17, z18, s, d;
+    wf_ensemble_deviates(a.ens, b, m, j, z17, z18);
+    wf_ensemble_tick(w, rate, j, z17, z18, x, y, s, d);
     buf[2 * j] = s;
-    buf[2 * j + 1] = w;
+    buf[2 * j + 1] = d;
     if (out) {
       out[2 * j] = s;
-      out[2 * j + 1] = w;
+      out[2 * j + 1] = d;
     }
   }
 }
@@ -133,40 +117,13 @@ __global__ __launch_bounds__(256) void wf_polscen_stats_kernel(const WfPolicyRun
   const int slot = blockIdx.x;     // (< n_slots: the launch has a workgroup per farm of the chunk)
   for (int i = tid; i < KM; i += nth) rets[i] = x.mret[(size_t)i * C + slot];  // (row (k, m) is evaluator farm (k M + m) C + slot)
   __syncthreads();
-  const int spp = nth / M;         // whole policies per pass (M <= 64 <= nth)
-  const int kk = tid / M, m = tid - kk * M;
-  const int q = x.q;
-  const double lam = x.lam;
-  for (int k0 = 0; k0 < K; k0 += spp) {  // (block-uniform)
-    const bool member = kk < spp && k0 + kk < K;
-    double v = 0.0;
-    int rank = 0;
-    if (member) {
-      const double* s = rets + (size_t)(k0 + kk) * M;
-      v = s[m];
-      for (int j = 0; j < M; ++j) {
-        const double vj = s[j];
-        rank += (vj < v) || (vj == v && j < m);
-      }
-    }
-    __syncthreads();  // (the previous pass's tails have been added)
-    if (member) srt[kk * M + rank] = v;
-    __syncthreads();
-    if (tid < spp && k0 + tid < K) {
-      const int k = k0 + tid;
-      const double* s = rets + (size_t)k * M;
-      double sum = 0.0, tail = 0.0;
-      for (int j = 0; j < M; ++j) sum += s[j];
-      for (int j = 0; j < q; ++j) tail += srt[tid * M + j];
-      const double mean = sum / (double)M, cvar = tail / (double)q;
-      const double score = ((1.0 - lam) * mean) + (lam * cvar);
-      const size_t o = (size_t)(sl_.base + slot) * K + k;
-      if (x.expected) x.expected[o] = mean;
-      if (x.cvar) x.cvar[o] = cvar;
-      if (x.score) x.score[o] = score;
-      sc[k] = score;
-    }
-  }
+  const size_t o0 = (size_t)(sl_.base + slot) * K;
+  wf_member_statistics(rets, 1, K, M, x.q, x.lam, srt, [&x, o0, sc](int k, double mean, double cvar, double score) {
+    if (x.expected) x.expected[o0 + k] = mean;
+    if (x.cvar) x.cvar[o0 + k] = cvar;
+    if (x.score) x.score[o0 + k] = score;
+    sc[k] = score;
+  });
   __syncthreads();
   if (tid == 0 && x.best) {
     double bv = sc[0];
@@ -195,7 +152,7 @@ WfPolscenTile wf_polscen_tile(int N, int rows) {
 }
 
 extern "C" hipError_t wfk_launch_polscen_paths(const WfPolscenPathsArgs* a, hipStream_t s) {
-  const int n = a->sl.C * a->M;
+  const int n = a->sl.C * a->ens.M;
   hipLaunchKernelGGL(wf_polscen_paths_kernel, dim3((n + 63) / 64), dim3(64), 0, s, *a);
   return hipGetLastError();
 }

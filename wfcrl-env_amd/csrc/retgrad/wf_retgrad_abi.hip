@@ -84,10 +84,7 @@ int wf_retgrad_run(wf_retgrad* r, const float* actions, int K, int H, const doub
   int* d_best = nullptr;
   unsigned char* d_mask = nullptr;
   staging st(r, r->d_stage, on_device);
-  WfEnvView env{};
-  env.yaw = h->d_env_yaw; env.acc = h->d_env_acc; env.moves = h->d_env_moves;
-  env.lo = h->env.yaw_lo; env.hi = h->env.yaw_hi; env.step = h->env.yaw_step;
-  env.rate = h->env.actuator_rate; env.dt = h->env.dt; env.budget = h->env.budget; env.discrete = h->env.discrete;
+  const WfEnvView env = env_view(h);
   row_policy k;
   k.what = "return gradients serve"; k.name = "wf_retgrad_run";
   k.rows_msg = kRowsMsg; k.loads = true;

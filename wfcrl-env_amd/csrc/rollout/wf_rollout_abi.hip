@@ -97,10 +97,7 @@ int wf_rollout_run(wf_rollout* r, int K, const int* slot, const double* alpha, c
   float *d_act = nullptr, *d_fy = nullptr;
   int *d_gated = nullptr, *d_best = nullptr;
   staging st(r, r->d_stage, on_device);
-  WfEnvView env{};
-  env.yaw = h->d_env_yaw; env.acc = h->d_env_acc; env.moves = h->d_env_moves;
-  env.lo = h->env.yaw_lo; env.hi = h->env.yaw_hi; env.step = h->env.yaw_step;
-  env.rate = h->env.actuator_rate; env.dt = h->env.dt; env.budget = h->env.budget; env.discrete = h->env.discrete;
+  const WfEnvView env = env_view(h);
   row_policy k;
   k.what = "controller rollouts serve"; k.name = "wf_rollout_run";
   k.rows_msg = kRowsMsg; k.loads = true;

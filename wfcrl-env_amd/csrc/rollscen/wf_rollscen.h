@@ -23,19 +23,14 @@ struct WfRollscenBracket {
 
 struct WfRollscenLayoutArgs {
   WfSlots sl;
-  const double *ws, *wd;   // the parent's wind: (S_c, D_c)
-  int wind_stride;         // 0 shared, 1 per farm
-  int N, K, M, H;
+  WfEnsemble ens;          // the paths: seed, process, bounds, anchor, the parent's wind, M, H
+  int N, K;
   WfEnvView env;           // the parent's env: the state is read, never written
-  unsigned long long seed;
-  double ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp;
-  double ws_lo, ws_hi;
   WfRoseTable tab[WF_ROSE_SLOTS];  // the rose object's tables
   const int* c_slot;       // [K] the controllers (device copies)
   const double* c_alpha;   // [K]
   const float* c_deadband; // [K]
   const int* c_lead;       // [K]
-  const double* anchor;    // [n_slots][2] (speed, direction) of this chunk, or null = the farm's current wind
   const double* filter0;   // [n_slots][K][2] of this chunk, or null = the farm's current wind
   int spill;               // the brackets go through brk, not LDS
   WfRollscenBracket* brk;  // [C][R] scratch (spill), or null

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../../include/wfrollscen.h"
+#include "../ensemble/wf_ensemble_host.h"
 #include "../ext/wf_ext.h"
 #include "wf_rollscen.h"
 
@@ -42,9 +43,6 @@ namespace {
 
 const char* const kRowsMsg = "max_eval_farms must hold one farm's rows: at least K M H";
 const char* const kNoEnv = "no env state: wf_env_config and wf_env_reset come first (the controllers start at the fused env's state)";
-
-bool in_unit(double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; }
-bool non_negative(double v) { return std::isfinite(v) && v >= 0.0; }
 
 }  // namespace
 
@@ -91,10 +89,7 @@ int wf_rollscen_run(wf_rollscen* r, int K, const int* slot, const double* alpha,
   int *d_gated = nullptr, *d_best = nullptr;
   bool spill = false;
   staging st(r, r->d_stage, on_device);
-  WfEnvView env{};
-  env.yaw = h->d_env_yaw; env.acc = h->d_env_acc; env.moves = h->d_env_moves;
-  env.lo = h->env.yaw_lo; env.hi = h->env.yaw_hi; env.step = h->env.yaw_step;
-  env.rate = h->env.actuator_rate; env.dt = h->env.dt; env.budget = h->env.budget; env.discrete = h->env.discrete;
+  const WfEnvView env = env_view(h);
   row_policy k;
   k.what = "scenario rollouts serve"; k.name = "wf_rollscen_run";
   k.rows_msg = kRowsMsg; k.loads = true;
@@ -114,21 +109,11 @@ int wf_rollscen_run(wf_rollscen* r, int K, const int* slot, const double* alpha,
       if (!std::isfinite(deadband[c]) || deadband[c] < 0.0f) return ext_fail(r, WF_E_INVALID, "a controller's deadband must be finite and >= 0");
       if (lead[c] < 0 || lead[c] > WF_ROLLOUT_MAX_LEAD) return ext_fail(r, WF_E_INVALID, "a controller's lead must be in 0..16");
     }
-    if (tail < 1 || tail > M) return ext_fail(r, WF_E_INVALID, "tail must be in 1..M: the number of lowest member returns the tail mean is over");
-    if (!in_unit(risk_weight)) return ext_fail(r, WF_E_INVALID, "risk_weight must be finite and in [0, 1]");
-    if (!in_unit(gamma)) return ext_fail(r, WF_E_INVALID, "gamma must be finite and in [0, 1]");
-    if (!process) return ext_fail(r, WF_E_INVALID, "wf_rollscen_run: process is NULL");
-    const wf_wind_process& p = *process;
-    if (!in_unit(p.ws_revert) || !in_unit(p.wd_revert)) return ext_fail(r, WF_E_INVALID, "ws_revert and wd_revert must be in [0, 1]");
-    if (!non_negative(p.ws_sigma) || !non_negative(p.wd_sigma) || !non_negative(p.wd_ramp))
-      return ext_fail(r, WF_E_INVALID, "ws_sigma, wd_sigma and wd_ramp must be finite and >= 0");
-    if (!std::isfinite(ws_lo) || !std::isfinite(ws_hi) || !(ws_lo > 0.0) || !(ws_lo < ws_hi))
-      return ext_fail(r, WF_E_INVALID, "the speed bounds must be finite with 0 < ws_lo < ws_hi");
+    int rc = check_ensemble(r, "wf_rollscen_run", M, tail, risk_weight, gamma, process, ws_lo, ws_hi);
+    if (rc != WF_OK) return rc;
     if (!h->d_env_yaw || !h->d_env_acc || !h->d_env_moves) return ext_fail(r, WF_E_INVALID, kNoEnv);
-    if (anchor && !on_device)
-      for (int i = 0; i < n_farms; ++i)
-        if (!(anchor[2 * i] > 0.0) || !std::isfinite(anchor[2 * i]) || !std::isfinite(anchor[2 * i + 1]))
-          return ext_fail(r, WF_E_INVALID, "the anchor's speed must be > 0 and its direction finite");
+    rc = check_ensemble_anchor(r, anchor, n_farms, on_device);
+    if (rc != WF_OK) return rc;
     k.rows = K * M * H;
     spill = k.rows > WF_ROLLSCEN_LDS_RECORDS;
     return WF_OK;
@@ -161,17 +146,13 @@ int wf_rollscen_run(wf_rollscen* r, int K, const int* slot, const double* alpha,
   };
   k.layout = [&](const WfSlots& sl, int E) -> int {
     const size_t first = (size_t)sl.base;
-    const wf_wind_process& p = *process;
     WfRollscenLayoutArgs la{};
     la.sl = sl;
-    la.ws = h->d_ws; la.wd = h->d_wd; la.wind_stride = wind_stride; la.N = N; la.K = K; la.M = M; la.H = H;
+    la.ens = ensemble_args(h, M, H, *process, ws_lo, ws_hi, seed, d_anchor, first);
+    la.N = N; la.K = K;
     la.env = env;
-    la.seed = seed;
-    la.ws_revert = p.ws_revert; la.ws_sigma = p.ws_sigma; la.wd_revert = p.wd_revert; la.wd_sigma = p.wd_sigma; la.wd_ramp = p.wd_ramp;
-    la.ws_lo = ws_lo; la.ws_hi = ws_hi;
     for (int i = 0; i < WF_ROSE_SLOTS; ++i) la.tab[i] = rose_device_table(r->tables, i, nullptr);
     la.c_slot = r->d_cint; la.c_lead = r->d_cint + K; la.c_alpha = r->d_calpha; la.c_deadband = r->d_cband;
-    la.anchor = d_anchor ? d_anchor + first * 2 : nullptr;
     la.filter0 = d_f0 ? d_f0 + first * K * 2 : nullptr;
     la.spill = spill ? 1 : 0;
     la.brk = spill ? r->d_brk.p : nullptr;

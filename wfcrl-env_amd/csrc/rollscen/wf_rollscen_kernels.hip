@@ -3,13 +3,9 @@
 // the glue, so that a whole run — the ensemble's draws included — is enqueued without a host read:
 //
 //   wf_rollscen_layout_kernel  once per chunk, ONE WORKGROUP PER SLOT, three phases.
-//                              PHASE 1 — the member paths, the scenario lay-out's scheme (scenario/wf_scenario_kernels.hip) and
-//                              its arithmetic, operation for operation: TILES of Ht ticks, two [M][Hs] arrays of doubles in
-//                              LDS; every thread draws the deviates of its (member, tick) pairs, streams 17 and 18, into the
-//                              tile; thread m < M, which keeps member m's latents and ramp rate in registers across the tiles,
-//                              walks the tile's ticks in place; after the barrier the threads fill every row's evaluator wind,
-//                              thread r on row r, and wind_paths from LDS.  The observations of phase 2 are the wind of rows
-//                              (0, m, .) — what this block has just written, behind a block barrier.
+//                              PHASE 1 — the member paths, every row's evaluator wind and wind_paths: the ensemble's tiled body
+//                              (ensemble/wf_ensemble.h: wf_ensemble_tiles), in tiles of 2048 / M ticks.  The observations of
+//                              phase 2 are the wind of rows (0, m, .) — what this block has just written, behind a block barrier.
 //                              PHASE 2 — filter and bracket depend on (k, m, h), not on the turbine: thread (k, m) walks
 //                              h = 0 .. H - 1 ONCE — observation obs[min(h + lead, H)], the float64 filter, then steps 1-3 of
 //                              the table look-up (rose/wf_rose_lookup.h: rose_bracket, the rose extension's own device
@@ -39,15 +35,11 @@
 // and the statistics is one rounding, in the headers' order.
 #include <hip/hip_runtime.h>
 
-#include "../ext/wf_deviate.h"
 #include "../rose/wf_rose_lookup.h"
 #include "../scenario/wf_scenario_reduce.h"
-#include "../wf_philox.h"
 #include "wf_rollscen.h"
 
-#define WF_ROLLSCEN_TILE 2048  // (member, tick) pairs of a lay-out tile: the scenario lay-out's
 #define WF_ROLLSCEN_WIDE 1024  // trajectories per slot (K M N) from which the lay-out kernel runs 1024 threads
-#define WF_ROLLSCEN_IN_VGPR(v) WF_SCENARIO_IN_VGPR(v)
 
 static_assert(sizeof(WfRollscenBracket) == 32 && sizeof(RoseBracket) == sizeof(WfRollscenBracket), "a bracket is 32 bytes");
 static_assert(WF_ROLLSCEN_LDS_RECORDS * sizeof(WfRollscenBracket) <= 32 * 1024, "the records in LDS take at most 32 KiB");
@@ -58,83 +50,15 @@ template <bool SPILL>
 __global__ __launch_bounds__(1024) void wf_rollscen_layout_kernel(const WfRollscenLayoutArgs a, int Ht, int Hs, int A8) {
   extern __shared__ double rs_lds[];
   const int tid = threadIdx.x, nth = blockDim.x;
-  const int N = a.N, K = a.K, M = a.M, H = a.H, MH = M * H, R = K * MH;
-  double* sp = rs_lds;      // [M][Hs] deviates of stream 17, then the stored speeds
-  double* dr = sp + M * Hs; // [M][Hs] ... of stream 18, then the stored directions
+  const int N = a.N, K = a.K, M = a.ens.M, H = a.ens.H, R = K * M * H;
   const int slot = blockIdx.x;
   const int b = wf_slot_farm(a.sl, slot);
-  const bool writes = slot < a.sl.n_slots;
-  const size_t in = writes ? slot : 0;  // the slot's input block
-  // ---- phase 1: the member paths (the scenario lay-out's, operation for operation) ----
-  {
-    double Sc = a.ws[(size_t)b * a.wind_stride], Dc = a.wd[(size_t)b * a.wind_stride];
-    WF_ROLLSCEN_IN_VGPR(Sc); WF_ROLLSCEN_IN_VGPR(Dc);
-    double Sa = a.anchor ? a.anchor[in * 2] : Sc, Da = a.anchor ? a.anchor[in * 2 + 1] : Dc;
-    // the walk's parameters live in vector registers: block-uniform values held in scalar ones across the Philox rounds of the
-    // draws would not fit (spilled scalar registers)
-    double ws_revert = a.ws_revert, ws_sigma = a.ws_sigma, wd_revert = a.wd_revert, wd_sigma = a.wd_sigma;
-    double ws_lo = a.ws_lo, ws_hi = a.ws_hi;
-    WF_ROLLSCEN_IN_VGPR(Sa); WF_ROLLSCEN_IN_VGPR(Da);
-    WF_ROLLSCEN_IN_VGPR(ws_revert); WF_ROLLSCEN_IN_VGPR(ws_sigma); WF_ROLLSCEN_IN_VGPR(wd_revert); WF_ROLLSCEN_IN_VGPR(wd_sigma);
-    WF_ROLLSCEN_IN_VGPR(ws_lo); WF_ROLLSCEN_IN_VGPR(ws_hi);
-    const unsigned long long hi = (unsigned long long)b << 32;
-    const bool walker = tid < M;  // (blocks have at least 64 threads): thread m keeps member m's state
-    double x = Sc, y = Dc, rate = 0.0;
-    if (walker) {
-      unsigned r[4];
-      philox4x32_10(a.seed, hi | (unsigned)tid, 16u, r);
-      rate = a.wd_ramp * (2.0 * u01(r[0], r[1]) - 1.0);
-    }
-    double* __restrict__ ews = a.ews + (size_t)slot * R;
-    double* __restrict__ ewd = a.ewd + (size_t)slot * R;
-    double* __restrict__ paths = (writes && a.wind_paths) ? a.wind_paths + in * MH * 2 : nullptr;
-    for (int h0 = 0; h0 < H; h0 += Ht) {  // (block-uniform)
-      const int nt = H - h0 < Ht ? H - h0 : Ht;
-      const int n = M * nt;
-      for (int i = tid; i < n; i += nth) {
-        const int m = i / nt, j = i - m * nt;
-        const unsigned long long ctr = hi | (unsigned)(m * 64 + h0 + j);
-        sp[m * Hs + j] = wf_deviate(a.seed, ctr, 17u);
-        dr[m * Hs + j] = wf_deviate(a.seed, ctr, 18u);
-      }
-      __syncthreads();
-      if (walker) {
-        double* s = sp + tid * Hs;
-        double* d = dr + tid * Hs;
-        for (int j = 0; j < nt; ++j) {
-          x = (x + ws_revert * (Sa - x)) + ws_sigma * s[j];
-          const double mu = Da + rate * (double)(h0 + j + 1);
-          y = (y + wd_revert * (mu - y)) + wd_sigma * d[j];
-          double w = fmod(y, 360.0);
-          if (w < 0.0) w += 360.0;
-          s[j] = fmin(fmax(x, ws_lo), ws_hi);
-          d[j] = w;
-        }
-      }
-      __syncthreads();
-      for (int r = tid; r < R; r += nth) {
-        const int km = r / H, h = r - km * H, j = h - h0;
-        if (j >= 0 && j < nt) {
-          const int m = km % M;
-          ews[r] = sp[m * Hs + j];
-          ewd[r] = dr[m * Hs + j];
-        }
-      }
-      if (paths) {
-        for (int i = tid; i < n; i += nth) {
-          const int m = i / nt, j = i - m * nt;
-          const size_t e = ((size_t)m * H + h0 + j) * 2;
-          paths[e] = sp[m * Hs + j];
-          paths[e + 1] = dr[m * Hs + j];
-        }
-      }
-      __syncthreads();  // (the next tile's draws, then the records, overwrite sp / dr; the rows' wind is visible to the block)
-    }
-  }
+  // ---- phase 1: the member paths ----
+  wf_ensemble_tiles(a.ens, a.sl, K, Ht, Hs, rs_lds, a.ews, a.ewd, a.wind_paths);
   // what addresses the rest is formed HERE, from the slot and the farm in vector registers — formed at the top and held in
   // scalar registers across the draws it would not fit (spilled scalar registers)
   int slot_v = slot, b_v = b;
-  WF_ROLLSCEN_IN_VGPR(slot_v); WF_ROLLSCEN_IN_VGPR(b_v);
+  WF_IN_VGPR(slot_v); WF_IN_VGPR(b_v);
   const bool writes_v = slot_v < a.sl.n_slots;
   const size_t in_v = writes_v ? slot_v : 0, st0 = (size_t)b_v * N;
   const int KM = K * M;
@@ -142,7 +66,7 @@ __global__ __launch_bounds__(1024) void wf_rollscen_layout_kernel(const WfRollsc
   WfRollscenBracket* rec = SPILL ? a.brk + (size_t)slot_v * R : reinterpret_cast<WfRollscenBracket*>(rs_lds);  // [R]
   // ---- phase 2: the filter and the bracket of every (k, m, h), once per (controller, member): a recurrence over h ----
   {
-    const double ws0 = a.ws[(size_t)b_v * a.wind_stride], wd0 = a.wd[(size_t)b_v * a.wind_stride];
+    const double ws0 = a.ens.ws[(size_t)b_v * a.ens.wind_stride], wd0 = a.ens.wd[(size_t)b_v * a.ens.wind_stride];
     const double* ews0 = a.ews + (size_t)slot_v * R;  // rows (0, m, .): member m's winds, written in phase 1 by this block
     const double* ewd0 = a.ewd + (size_t)slot_v * R;
     for (int km = tid; km < KM; km += nth) {
@@ -224,14 +148,13 @@ __global__ __launch_bounds__(1024) void wf_rollscen_reduce_kernel(const WfRollsc
 }
 
 extern "C" hipError_t wfk_launch_rollscen_layout(const WfRollscenLayoutArgs* a, hipStream_t s) {
-  const int KM = a->K * a->M, R = KM * a->H;
+  const int KM = a->K * a->ens.M, R = KM * a->ens.H;
   // a few short rollouts of a small farm: one wave.  From WF_ROLLSCEN_WIDE trajectories per slot on, 1024 threads: a trajectory
   // is a chain of dependent loads (record, table entries) and float32 steps, H long, and a slot has one workgroup to hide them
   const int threads = (R <= 128 && KM * a->N <= 64) ? 64 : (KM * a->N >= WF_ROLLSCEN_WIDE ? 1024 : 256);
-  int Ht = WF_ROLLSCEN_TILE / a->M;
-  Ht = Ht > a->H ? a->H : Ht;
-  const int Hs = Ht | 1;
-  const int tile8 = 2 * a->M * Hs, rec8 = a->spill ? 0 : 4 * R;  // doubles: the tile, the records that follow it in the same bytes
+  const WfEnsembleTile t = wf_ensemble_tile(a->ens.M, a->ens.H);
+  const int Ht = t.Ht, Hs = t.Hs;
+  const int tile8 = 2 * a->ens.M * Hs, rec8 = a->spill ? 0 : 4 * R;  // doubles: the tile, the records that follow it in the same bytes
   const int A8 = tile8 > rec8 ? tile8 : rec8;
   const size_t lds = sizeof(double) * (size_t)A8 + sizeof(int) * (size_t)KM;
   if (a->spill) hipLaunchKernelGGL(wf_rollscen_layout_kernel<true>, dim3(a->sl.C), dim3(threads), lds, s, *a, Ht, Hs, A8);

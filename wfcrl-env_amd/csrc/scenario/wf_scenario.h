@@ -10,19 +10,15 @@
 #include <hip/hip_runtime.h>
 
 #include "../../../include/wfscenario.h"
+#include "../ensemble/wf_ensemble.h"
 #include "../ext/wf_ext_kernels.h"
 
 struct WfScenarioLayoutArgs {
   WfSlots sl;
-  const double *ws, *wd;  // the parent's wind: (S_c, D_c)
-  int wind_stride;        // 0 shared, 1 per farm
-  int N, K, M, H;
+  WfEnsemble ens;         // the paths: seed, process, bounds, anchor, the parent's wind, M, H
+  int N, K;
   WfEnvView env;          // the parent's env: the state is read, never written
-  unsigned long long seed;
-  double ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp;
-  double ws_lo, ws_hi;
   const float* actions;   // [n_slots][K][H][N] blocks of this chunk
-  const double* anchor;   // [n_slots][2] (speed, direction) of this chunk, or null = the farm's current wind
   float* yaw;             // [C][R][N] the evaluator's input
   double *ews, *ewd;      // [C R] every row's wind
   double* wind_paths;     // [n_slots][M][H][2] of this chunk, or null

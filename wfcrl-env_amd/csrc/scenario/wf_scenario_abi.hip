@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../../include/wfscenario.h"
+#include "../ensemble/wf_ensemble_host.h"
 #include "../ext/wf_ext.h"
 #include "wf_scenario.h"
 
@@ -29,9 +30,6 @@ namespace {
 
 const char* const kRowsMsg = "max_eval_farms must hold one farm's rows: at least K M H";
 const char* const kNoEnv = "no env state: wf_env_config and wf_env_reset come first (the sequences start at the fused env's state)";
-
-bool in_unit(double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; }
-bool non_negative(double v) { return std::isfinite(v) && v >= 0.0; }
 
 }  // namespace
 
@@ -68,10 +66,7 @@ int wf_scenario_run(wf_scenario* s, const float* actions, int K, int H, int M, c
   float* d_fy = nullptr;
   int* d_best = nullptr;
   staging st(s, s->d_stage, on_device);
-  WfEnvView env{};
-  env.yaw = h->d_env_yaw; env.acc = h->d_env_acc; env.moves = h->d_env_moves;
-  env.lo = h->env.yaw_lo; env.hi = h->env.yaw_hi; env.step = h->env.yaw_step;
-  env.rate = h->env.actuator_rate; env.dt = h->env.dt; env.budget = h->env.budget; env.discrete = h->env.discrete;
+  const WfEnvView env = env_view(h);
   row_policy k;
   k.what = "scenario returns serve"; k.name = "wf_scenario_run";
   k.rows_msg = kRowsMsg; k.loads = true;
@@ -81,22 +76,12 @@ int wf_scenario_run(wf_scenario* s, const float* actions, int K, int H, int M, c
     if (M < 1 || M > WF_SCENARIO_MAX_MEMBERS) return ext_fail(s, WF_E_INVALID, "the number of members M must be in 1..64");
     if (K < 1 || K > WF_SCENARIO_MAX_ROWS / (M * H))
       return ext_fail(s, WF_E_INVALID, "the number of sequences K must be >= 1 with K M H <= 4096");
-    if (tail < 1 || tail > M) return ext_fail(s, WF_E_INVALID, "tail must be in 1..M: the number of lowest member returns the tail mean is over");
-    if (!in_unit(risk_weight)) return ext_fail(s, WF_E_INVALID, "risk_weight must be finite and in [0, 1]");
-    if (!in_unit(gamma)) return ext_fail(s, WF_E_INVALID, "gamma must be finite and in [0, 1]");
-    if (!process) return ext_fail(s, WF_E_INVALID, "wf_scenario_run: process is NULL");
-    const wf_wind_process& p = *process;
-    if (!in_unit(p.ws_revert) || !in_unit(p.wd_revert)) return ext_fail(s, WF_E_INVALID, "ws_revert and wd_revert must be in [0, 1]");
-    if (!non_negative(p.ws_sigma) || !non_negative(p.wd_sigma) || !non_negative(p.wd_ramp))
-      return ext_fail(s, WF_E_INVALID, "ws_sigma, wd_sigma and wd_ramp must be finite and >= 0");
-    if (!std::isfinite(ws_lo) || !std::isfinite(ws_hi) || !(ws_lo > 0.0) || !(ws_lo < ws_hi))
-      return ext_fail(s, WF_E_INVALID, "the speed bounds must be finite with 0 < ws_lo < ws_hi");
+    int rc = check_ensemble(s, "wf_scenario_run", M, tail, risk_weight, gamma, process, ws_lo, ws_hi);
+    if (rc != WF_OK) return rc;
     if (!actions) return ext_fail(s, WF_E_INVALID, "wf_scenario_run: actions is NULL");
     if (!h->d_env_yaw || !h->d_env_acc || !h->d_env_moves) return ext_fail(s, WF_E_INVALID, kNoEnv);
-    if (anchor && !on_device)
-      for (int i = 0; i < n_farms; ++i)
-        if (!(anchor[2 * i] > 0.0) || !std::isfinite(anchor[2 * i]) || !std::isfinite(anchor[2 * i + 1]))
-          return ext_fail(s, WF_E_INVALID, "the anchor's speed must be > 0 and its direction finite");
+    rc = check_ensemble_anchor(s, anchor, n_farms, on_device);
+    if (rc != WF_OK) return rc;
     k.rows = K * M * H;
     return WF_OK;
   };
@@ -110,16 +95,12 @@ int wf_scenario_run(wf_scenario* s, const float* actions, int K, int H, int M, c
   };
   k.layout = [&](const WfSlots& sl, int E) -> int {
     const size_t first = (size_t)sl.base;
-    const wf_wind_process& p = *process;
     WfScenarioLayoutArgs la{};
     la.sl = sl;
-    la.ws = h->d_ws; la.wd = h->d_wd; la.wind_stride = wind_stride; la.N = N; la.K = K; la.M = M; la.H = H;
+    la.ens = ensemble_args(h, M, H, *process, ws_lo, ws_hi, seed, d_anchor, first);
+    la.N = N; la.K = K;
     la.env = env;
-    la.seed = seed;
-    la.ws_revert = p.ws_revert; la.ws_sigma = p.ws_sigma; la.wd_revert = p.wd_revert; la.wd_sigma = p.wd_sigma; la.wd_ramp = p.wd_ramp;
-    la.ws_lo = ws_lo; la.ws_hi = ws_hi;
     la.actions = d_act + first * K * H * N;
-    la.anchor = d_anchor ? d_anchor + first * 2 : nullptr;
     la.yaw = b.d_yaw; la.ews = b.d_wind; la.ewd = b.d_wind + E;
     la.wind_paths = d_paths ? d_paths + first * M * H * 2 : nullptr;
     la.final_yaw = d_fy ? d_fy + first * K * N : nullptr;

@@ -2,18 +2,12 @@
 // (include/wfscenario.h).  The farm solve is the existing wf_step on the object's evaluator handle; these two kernels are the
 // glue, so that a whole run — the ensemble's draws included — is enqueued without a host read:
 //
-//   wf_scenario_layout_kernel  once per chunk, ONE WORKGROUP PER SLOT.  The M member paths of the slot's farm go by in TILES
-//                              of Ht ticks (all H of them where M H <= 2048), two [M][Hs] arrays of doubles in LDS, Hs = Ht | 1:
-//                              (1) every thread draws the deviates of its (member, tick) pairs, streams 17 and 18, into the
-//                              tile — the draws are not serial, the recursion is —; (2) thread m < M, which keeps member m's
-//                              latents and ramp rate in registers across the tiles, walks the tile's ticks and leaves the
-//                              stored speed and direction in place; (3) after the barrier the threads fill every row's
-//                              evaluator wind, thread r on row r — consecutive lanes read consecutive doubles of a member's
-//                              LDS row and write consecutive doubles —, and wind_paths, consecutive lanes on consecutive
-//                              (speed, direction) pairs.  Then thread (k, t), t fastest, keeps the yaw and the accumulator
-//                              of turbine t in registers and walks sequence k's steps with the env's transition
-//                              (wf_env_transition, ext/wf_ext_kernels.h), as wf_lookahead_layout_kernel does, and stores
-//                              each yaw to the M member rows of that step: consecutive lanes write consecutive floats.
+//   wf_scenario_layout_kernel  once per chunk, ONE WORKGROUP PER SLOT.  The M member paths of the slot's farm, every row's
+//                              evaluator wind and wind_paths are the ensemble's tiled body (ensemble/wf_ensemble.h:
+//                              wf_ensemble_tiles), in tiles of 2048 / M ticks.  Then thread (k, t), t fastest, keeps the yaw
+//                              and the accumulator of turbine t in registers and walks sequence k's steps with the env's
+//                              transition (wf_env_transition, ext/wf_ext_kernels.h), as wf_lookahead_layout_kernel does, and
+//                              stores each yaw to the M member rows of that step: consecutive lanes write consecutive floats.
 //   wf_scenario_reduce_kernel  once per chunk, after the step, ONE WORKGROUP PER SLOT: row rewards, member returns, the statistics
 //                              and the choice — the body of wf_scenario_reduce.h (wf_scenario_statistics), which the
 //                              scenario-rollout extension instantiates too.
@@ -27,91 +21,20 @@
 // built with -ffp-contract=off: every product and sum of the paths and the statistics is one rounding, in the header's order.
 #include <hip/hip_runtime.h>
 
-#include "../ext/wf_deviate.h"
-#include "../wf_philox.h"
 #include "wf_scenario.h"
 #include "wf_scenario_reduce.h"
-
-#define WF_SCENARIO_TILE 2048  // (member, tick) pairs of a lay-out tile
 
 __global__ __launch_bounds__(256) void wf_scenario_layout_kernel(const WfScenarioLayoutArgs a, int Ht, int Hs) {
   extern __shared__ double sc_tile[];
   const int tid = threadIdx.x, nth = blockDim.x;
-  const int N = a.N, K = a.K, M = a.M, H = a.H, MH = M * H, R = K * MH;
-  double* sp = sc_tile;     // [M][Hs] deviates of stream 17, then the stored speeds
-  double* dr = sp + M * Hs; // [M][Hs] ... of stream 18, then the stored directions
+  const int N = a.N, K = a.K, M = a.ens.M, H = a.ens.H, MH = M * H, R = K * MH;
   const int slot = blockIdx.x;
   const int b = wf_slot_farm(a.sl, slot);
-  const bool writes = slot < a.sl.n_slots;
-  const size_t in = writes ? slot : 0;  // the slot's input block
-  double Sc = a.ws[(size_t)b * a.wind_stride], Dc = a.wd[(size_t)b * a.wind_stride];
-  WF_SCENARIO_IN_VGPR(Sc); WF_SCENARIO_IN_VGPR(Dc);
-  double Sa = a.anchor ? a.anchor[in * 2] : Sc, Da = a.anchor ? a.anchor[in * 2 + 1] : Dc;
-  // the walk's parameters live in vector registers: block-uniform values held in scalar ones across the Philox rounds of the
-  // draws would not fit (spilled scalar registers; tests/test_scenario.py reads the metadata)
-  double ws_revert = a.ws_revert, ws_sigma = a.ws_sigma, wd_revert = a.wd_revert, wd_sigma = a.wd_sigma;
-  double ws_lo = a.ws_lo, ws_hi = a.ws_hi;
-  WF_SCENARIO_IN_VGPR(Sa); WF_SCENARIO_IN_VGPR(Da);
-  WF_SCENARIO_IN_VGPR(ws_revert); WF_SCENARIO_IN_VGPR(ws_sigma); WF_SCENARIO_IN_VGPR(wd_revert); WF_SCENARIO_IN_VGPR(wd_sigma);
-  WF_SCENARIO_IN_VGPR(ws_lo); WF_SCENARIO_IN_VGPR(ws_hi);
-  const unsigned long long hi = (unsigned long long)b << 32;
-  // the walkers: thread m keeps member m's state
-  const bool walker = tid < M;
-  double x = Sc, y = Dc, rate = 0.0;
-  if (walker) {
-    unsigned r[4];
-    philox4x32_10(a.seed, hi | (unsigned)tid, 16u, r);
-    rate = a.wd_ramp * (2.0 * u01(r[0], r[1]) - 1.0);
-  }
-  double* __restrict__ ews = a.ews + (size_t)slot * R;
-  double* __restrict__ ewd = a.ewd + (size_t)slot * R;
-  double* __restrict__ paths = (writes && a.wind_paths) ? a.wind_paths + in * MH * 2 : nullptr;
-  for (int h0 = 0; h0 < H; h0 += Ht) {  // (block-uniform)
-    const int nt = H - h0 < Ht ? H - h0 : Ht;
-    const int n = M * nt;
-    for (int i = tid; i < n; i += nth) {
-      const int m = i / nt, j = i - m * nt;
-      const unsigned long long ctr = hi | (unsigned)(m * 64 + h0 + j);
-      sp[m * Hs + j] = wf_deviate(a.seed, ctr, 17u);
-      dr[m * Hs + j] = wf_deviate(a.seed, ctr, 18u);
-    }
-    __syncthreads();
-    if (walker) {
-      double* s = sp + tid * Hs;
-      double* d = dr + tid * Hs;
-      for (int j = 0; j < nt; ++j) {
-        x = (x + ws_revert * (Sa - x)) + ws_sigma * s[j];
-        const double mu = Da + rate * (double)(h0 + j + 1);
-        y = (y + wd_revert * (mu - y)) + wd_sigma * d[j];
-        double w = fmod(y, 360.0);
-        if (w < 0.0) w += 360.0;
-        s[j] = fmin(fmax(x, ws_lo), ws_hi);
-        d[j] = w;
-      }
-    }
-    __syncthreads();
-    for (int r = tid; r < R; r += nth) {
-      const int km = r / H, h = r - km * H, j = h - h0;
-      if (j >= 0 && j < nt) {
-        const int m = km % M;
-        ews[r] = sp[m * Hs + j];
-        ewd[r] = dr[m * Hs + j];
-      }
-    }
-    if (paths) {
-      for (int i = tid; i < n; i += nth) {
-        const int m = i / nt, j = i - m * nt;
-        const size_t e = ((size_t)m * H + h0 + j) * 2;
-        paths[e] = sp[m * Hs + j];
-        paths[e + 1] = dr[m * Hs + j];
-      }
-    }
-    __syncthreads();  // (the next tile's draws overwrite sp / dr)
-  }
+  wf_ensemble_tiles(a.ens, a.sl, K, Ht, Hs, sc_tile, a.ews, a.ewd, a.wind_paths);
   // the trajectories: what addresses them is formed HERE, from the slot and the farm in vector registers — formed at the top
   // and held in scalar registers across the draws it would not fit (spilled scalar registers)
   int slot_v = slot, b_v = b;
-  WF_SCENARIO_IN_VGPR(slot_v); WF_SCENARIO_IN_VGPR(b_v);
+  WF_IN_VGPR(slot_v); WF_IN_VGPR(b_v);
   const bool writes_v = slot_v < a.sl.n_slots;
   const size_t in_v = writes_v ? slot_v : 0, st0 = (size_t)b_v * N;
   const int moves0 = a.env.moves[b_v];
@@ -141,13 +64,11 @@ __global__ __launch_bounds__(1024) void wf_scenario_reduce_kernel(const WfScenar
 }
 
 extern "C" hipError_t wfk_launch_scenario_layout(const WfScenarioLayoutArgs* a, hipStream_t s) {
-  const int R = a->K * a->M * a->H;
+  const int R = a->K * a->ens.M * a->ens.H;
   const int threads = (R <= 128 && a->K * a->N <= 64) ? 64 : 256;  // a few short sequences of a small farm: one wave
-  int Ht = WF_SCENARIO_TILE / a->M;
-  Ht = Ht > a->H ? a->H : Ht;
-  const int Hs = Ht | 1;
-  const size_t lds = sizeof(double) * 2 * (size_t)a->M * Hs;
-  hipLaunchKernelGGL(wf_scenario_layout_kernel, dim3(a->sl.C), dim3(threads), lds, s, *a, Ht, Hs);
+  const WfEnsembleTile t = wf_ensemble_tile(a->ens.M, a->ens.H);
+  const size_t lds = sizeof(double) * 2 * (size_t)a->ens.M * t.Hs;
+  hipLaunchKernelGGL(wf_scenario_layout_kernel, dim3(a->sl.C), dim3(threads), lds, s, *a, t.Ht, t.Hs);
   return hipGetLastError();
 }
 extern "C" hipError_t wfk_launch_scenario_reduce(const WfScenarioReduceArgs* a, hipStream_t s) {

@@ -5,11 +5,9 @@
 //
 // ONE WORKGROUP PER SLOT.  The slot's R = K M H rows go by in the shared reward tile (wf_staged_row_rewards); the thread of a
 // tile's row leaves the row's reward in LDS ([K M][Hs] doubles) and writes rewards.  Thread (k, m) forms its discounted return
-// in ascending h, as wf_sequence_returns does, and leaves it in its row's first entry.  The statistics run in PASSES of nth / M
-// whole sequences: thread (k, m) counts its rank over the M members of its sequence in LDS — (return, m) ascending, a count —
-// and scatters its return to sorted[k][rank] (a pass's [nth] doubles); thread k adds the mean in ascending m and the tail in
-// ascending rank, forms the score and keeps its argmax, ascending k.  A fixed-order tree over the threads follows: the larger
-// score and among equal ones the lower index.
+// in ascending h, as wf_sequence_returns does, and leaves it in its row's first entry.  The statistics and the choice are the ensemble's
+// (ensemble/wf_ensemble.h: wf_member_statistics over the returns at stride Hs, which emits to the three output arrays, then
+// wf_argmax_tree).
 //
 // The row normalisers: step 0's is the farm's CURRENT speed (a pending prev-wind speed is not read), step h >= 1's the speed
 // of row (k, m, h - 1), read from the evaluator's wind block.  LDS is laid out as wf_lookahead_reduce_kernel's with K M
@@ -22,7 +20,6 @@
 #include "wf_scenario.h"
 
 #define WF_SCENARIO_WIDE 8192  // floats of power per slot (R N) from which the reduce kernel runs 1024 threads
-#define WF_SCENARIO_IN_VGPR(v) asm volatile("" : "+v"(v))  // the value is held in a vector register from here on
 
 // `sc_red` is the block's dynamic LDS: [K M][Hs] + [nth] doubles (bv), [nth] ints (bi), then the tile's [T][sp] + [T][sl] floats
 __device__ __forceinline__ void wf_scenario_statistics(const WfScenarioReduceArgs& a, int T, int sp, int sl, int Hs, double* sc_red) {
@@ -34,7 +31,7 @@ __device__ __forceinline__ void wf_scenario_statistics(const WfScenarioReduceArg
   const int slot = blockIdx.x;
   const int b = wf_slot_farm(a.sl, slot);
   double wr0 = a.ws[(size_t)b * a.wind_stride];
-  WF_SCENARIO_IN_VGPR(wr0);  // (as the lay-out's parameters: no spilled scalar register)
+  WF_IN_VGPR(wr0);  // (as the lay-out's parameters: no spilled scalar register)
   const double* __restrict__ ews = a.ews + (size_t)slot * R;
   const float* __restrict__ pblk = a.power_ev + (size_t)slot * R * N;
   const float* __restrict__ lblk = a.load_ev + (size_t)slot * R * 4 * N;
@@ -48,11 +45,11 @@ __device__ __forceinline__ void wf_scenario_statistics(const WfScenarioReduceArg
         if (rewards) rewards[row] = r;
       });
   int after = KM * Hs;  // (formed again, in a vector register, and not held in scalar ones across the tiles)
-  WF_SCENARIO_IN_VGPR(after);
+  WF_IN_VGPR(after);
   double* bv = rw + after;                     // [nth] a pass's sorted returns, then the argmax tree: scores ...
   int* bi = reinterpret_cast<int*>(bv + nth);  // [nth] ... and their sequences
   double gamma = a.gamma;
-  WF_SCENARIO_IN_VGPR(gamma);
+  WF_IN_VGPR(gamma);
   for (int km = tid; km < KM; km += nth) {
     double* r = rw + km * Hs;
     double g = 1.0, ret = 0.0;
@@ -64,56 +61,14 @@ __device__ __forceinline__ void wf_scenario_statistics(const WfScenarioReduceArg
     if (a.member_returns) a.member_returns[(size_t)slot * KM + km] = ret;
   }
   __syncthreads();
-  const int spp = nth / M;  // whole sequences per pass (M <= 64 <= nth)
-  const int kk = tid / M, m = tid - kk * M;
-  const int q = a.q;
-  double lam = a.lam;
-  WF_SCENARIO_IN_VGPR(lam);
-  double best_v = -HUGE_VAL;
-  int best_k = INT_MAX;
-  for (int k0 = 0; k0 < K; k0 += spp) {  // (block-uniform)
-    const bool member = kk < spp && k0 + kk < K;
-    double v = 0.0;
-    int rank = 0;
-    if (member) {
-      const double* s = rw + (size_t)(k0 + kk) * M * Hs;
-      v = s[m * Hs];
-      for (int j = 0; j < M; ++j) {
-        const double vj = s[j * Hs];
-        rank += (vj < v) || (vj == v && j < m);
-      }
-    }
-    __syncthreads();  // (the previous pass's tails have been added)
-    if (member) bv[kk * M + rank] = v;
-    __syncthreads();
-    if (tid < spp && k0 + tid < K) {
-      const int k = k0 + tid;
-      const double* s = rw + (size_t)k * M * Hs;
-      double sum = 0.0, tail = 0.0;
-      for (int j = 0; j < M; ++j) sum += s[j * Hs];
-      for (int j = 0; j < q; ++j) tail += bv[tid * M + j];
-      const double mean = sum / (double)M, cvar = tail / (double)q;
-      const double score = ((1.0 - lam) * mean) + (lam * cvar);
-      const size_t o = (size_t)slot * K + k;
-      if (a.expected) a.expected[o] = mean;
-      if (a.cvar) a.cvar[o] = cvar;
-      if (a.score) a.score[o] = score;
-      if (score > best_v || (score == best_v && k < best_k)) { best_v = score; best_k = k; }
-    }
-  }
-  __syncthreads();  // (the last pass's tails have been added: bv becomes the tree)
-  bv[tid] = best_v;
-  bi[tid] = best_k;
-  __syncthreads();
-  for (int s = nth >> 1; s > 0; s >>= 1) {  // (block-uniform)
-    if (tid < s) {
-      const double v = bv[tid + s];
-      const int k = bi[tid + s];
-      if (v > bv[tid] || (v == bv[tid] && k < bi[tid])) { bv[tid] = v; bi[tid] = k; }
-    }
-    __syncthreads();
-  }
-  if (tid == 0 && a.best) a.best[slot] = bi[0] == INT_MAX ? 0 : bi[0];
+  const size_t o0 = (size_t)slot * K;
+  const WfBest best = wf_member_statistics(rw, Hs, K, M, a.q, a.lam, bv, [&a, o0](int k, double mean, double cvar, double score) {
+    if (a.expected) a.expected[o0 + k] = mean;
+    if (a.cvar) a.cvar[o0 + k] = cvar;
+    if (a.score) a.score[o0 + k] = score;
+  });
+  wf_argmax_tree(best, bv, bi);
+  if (tid == 0 && a.best) a.best[slot] = wf_argmax_winner(bi);
 }
 
 // Its launch: wf_returns_launch's choices with K M sequences — one wave for a few short rows, the odd stride where it fits in

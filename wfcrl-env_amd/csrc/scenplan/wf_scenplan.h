@@ -11,18 +11,14 @@
 #include <hip/hip_runtime.h>
 
 #include "../../../include/wfscenplan.h"
+#include "../ensemble/wf_ensemble.h"
 #include "../ext/wf_ext_kernels.h"
 
 // the paths kernel's arguments, by value: once per chunk
 struct WfScenPlanPathsArgs {
   WfSlots sl;
-  const double *ws, *wd;  // the parent's wind: (S_c, D_c)
-  int wind_stride;        // 0 shared, 1 per farm
-  int K, M, H;
-  unsigned long long seed;  // scenario_seed
-  double ws_revert, ws_sigma, wd_revert, wd_sigma, wd_ramp;
-  double ws_lo, ws_hi;
-  const double* anchor;   // [n_slots][2] (speed, direction) of this chunk, or null = the farm's current wind
+  WfEnsemble ens;         // the paths: scenario_seed, process, bounds, anchor, the parent's wind, M, H
+  int K;
   double *ews, *ewd;      // [C R] every row's wind
   double* wind_paths;     // [n_slots][M][H][2] of this chunk, or null
 };

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../../include/wfscenplan.h"
+#include "../ensemble/wf_ensemble_host.h"
 #include "../ext/wf_ext.h"
 #include "wf_scenplan.h"
 
@@ -42,9 +43,6 @@ namespace {
 
 const char* const kRowsMsg = "max_eval_farms must hold one farm's rows: at least K M H";
 const char* const kNoEnv = "no env state: wf_env_config and wf_env_reset come first (the plans start at the fused env's state)";
-
-bool in_unit(double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; }
-bool non_negative(double v) { return std::isfinite(v) && v >= 0.0; }
 
 }  // namespace
 
@@ -98,24 +96,14 @@ int wf_scenplan_run(wf_scenplan* p, int H, int K, int E, int I, const double* si
     if (!sigma) return ext_fail(p, WF_E_INVALID, "wf_scenplan_run: sigma is NULL");
     for (int i = 0; i < I; ++i)
       if (!std::isfinite(sigma[i]) || sigma[i] < 0.0) return ext_fail(p, WF_E_INVALID, "every sigma must be finite and non-negative");
-    if (tail < 1 || tail > M) return ext_fail(p, WF_E_INVALID, "tail must be in 1..M: the number of lowest member returns the tail mean is over");
-    if (!in_unit(risk_weight)) return ext_fail(p, WF_E_INVALID, "risk_weight must be finite and in [0, 1]");
-    if (!in_unit(gamma)) return ext_fail(p, WF_E_INVALID, "gamma must be finite and in [0, 1]");
-    if (!process) return ext_fail(p, WF_E_INVALID, "wf_scenplan_run: process is NULL");
-    const wf_wind_process& w = *process;
-    if (!in_unit(w.ws_revert) || !in_unit(w.wd_revert)) return ext_fail(p, WF_E_INVALID, "ws_revert and wd_revert must be in [0, 1]");
-    if (!non_negative(w.ws_sigma) || !non_negative(w.wd_sigma) || !non_negative(w.wd_ramp))
-      return ext_fail(p, WF_E_INVALID, "ws_sigma, wd_sigma and wd_ramp must be finite and >= 0");
-    if (!std::isfinite(ws_lo) || !std::isfinite(ws_hi) || !(ws_lo > 0.0) || !(ws_lo < ws_hi))
-      return ext_fail(p, WF_E_INVALID, "the speed bounds must be finite with 0 < ws_lo < ws_hi");
+    int rc = check_ensemble(p, "wf_scenplan_run", M, tail, risk_weight, gamma, process, ws_lo, ws_hi);
+    if (rc != WF_OK) return rc;
     if (!h->d_env_yaw || !h->d_env_acc || !h->d_env_moves) return ext_fail(p, WF_E_INVALID, kNoEnv);
     if (h->env.discrete)
       return ext_fail(p, WF_E_UNSUPPORTED,
                       "scenario planning serves the continuous action encoding: this handle is configured discrete (wf_env_config)");
-    if (anchor && !on_device)
-      for (int i = 0; i < n_farms; ++i)
-        if (!(anchor[2 * i] > 0.0) || !std::isfinite(anchor[2 * i]) || !std::isfinite(anchor[2 * i + 1]))
-          return ext_fail(p, WF_E_INVALID, "the anchor's speed must be > 0 and its direction finite");
+    rc = check_ensemble_anchor(p, anchor, n_farms, on_device);
+    if (rc != WF_OK) return rc;
     sg.assign(sigma, sigma + I);
     k.rows = K * M * H; k.rounds = I;
     return WF_OK;
@@ -146,9 +134,7 @@ int wf_scenplan_run(wf_scenplan* p, int H, int K, int E, int I, const double* si
     r.wind_stride = wind_stride;
     r.load_coef = h->env.load_coef; r.gamma = gamma; r.lam = risk_weight; r.seed = seed;
     r.ws = h->d_ws;
-    r.env.yaw = h->d_env_yaw; r.env.acc = h->d_env_acc; r.env.moves = h->d_env_moves;
-    r.env.lo = h->env.yaw_lo; r.env.hi = h->env.yaw_hi; r.env.step = h->env.yaw_step;
-    r.env.rate = h->env.actuator_rate; r.env.dt = h->env.dt; r.env.budget = h->env.budget; r.env.discrete = 0;
+    r.env = env_view(h); r.env.discrete = 0;
     r.yaw = b.d_yaw; r.ews = b.d_wind;
     r.power_ev = b.d_pow; r.load_ev = b.d_load;
     r.cand = p->d_cand; r.best = p->d_best; r.mu = p->d_mu; r.mret = p->d_mret; r.stat = p->d_stat;
@@ -171,14 +157,10 @@ int wf_scenplan_run(wf_scenplan* p, int H, int K, int E, int I, const double* si
   };
   k.layout = [&](const WfSlots& sl, int Ev) -> int {
     const size_t first = (size_t)sl.base;
-    const wf_wind_process& w = *process;
     WfScenPlanPathsArgs pa{};
     pa.sl = sl;
-    pa.ws = h->d_ws; pa.wd = h->d_wd; pa.wind_stride = wind_stride; pa.K = K; pa.M = M; pa.H = H;
-    pa.seed = scenario_seed;
-    pa.ws_revert = w.ws_revert; pa.ws_sigma = w.ws_sigma; pa.wd_revert = w.wd_revert; pa.wd_sigma = w.wd_sigma; pa.wd_ramp = w.wd_ramp;
-    pa.ws_lo = ws_lo; pa.ws_hi = ws_hi;
-    pa.anchor = d_anchor ? d_anchor + first * 2 : nullptr;
+    pa.ens = ensemble_args(h, M, H, *process, ws_lo, ws_hi, scenario_seed, d_anchor, first);
+    pa.K = K;
     pa.ews = b.d_wind; pa.ewd = b.d_wind + Ev;
     pa.wind_paths = d_paths ? d_paths + first * M * H * 2 : nullptr;
     WFX_HIP(p, wfk_launch_scenplan_paths(&pa, h->stream));

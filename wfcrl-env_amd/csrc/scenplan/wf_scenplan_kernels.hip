@@ -3,21 +3,17 @@
 // futures).  The farm solve is the existing wf_step on the object's evaluator handle; these kernels are the glue, so that a
 // whole run — the ensemble's draws included — is enqueued without a host read:
 //
-//   wf_scenplan_paths_kernel    once per chunk, ONE WORKGROUP PER SLOT.  The M member paths of the slot's farm, two [M][Hs]
-//     arrays of doubles in LDS, Hs = H | 1, in ONE tile: K >= 3 and K M H <= 4096 leave M H <= 1365 (the scenario lay-out's
-//     several-tiles branch, M H > 2048, cannot be reached here).  Every thread draws the deviates of its (member, tick) pairs,
-//     streams 17 and 18; thread m < M draws its ramp rate, stream 16, and walks member m's recursion in place; after the
-//     barrier the threads fill every row's evaluator wind, thread r on row r, and wind_paths, consecutive lanes on consecutive
-//     (speed, direction) pairs.  The rows' wind is the same in every iteration: it is written here and nowhere else.
+//   wf_scenplan_paths_kernel    once per chunk, ONE WORKGROUP PER SLOT.  The M member paths of the slot's farm, every row's
+//     evaluator wind and wind_paths: the ensemble's tiled body (ensemble/wf_ensemble.h: wf_ensemble_tiles) with ONE tile of
+//     H ticks, Hs = H | 1 — K >= 3 and K M H <= 4096 leave M H <= 1365, and the launcher refuses M H > 2048.  The rows' wind
+//     is the same in every iteration: it is written here and nowhere else.
 //   wf_scenplan_advance_kernel  I + 1 launches per chunk, ONE WORKGROUP PER SLOT.  Launch v
 //     REDUCES iteration v - 1 (v > 0).  The slot's R = K M H rows go by in LDS tiles (wf_staged_row_rewards,
 //       ext/wf_ext_kernels.h) and leave their rewards in LDS ([K M][Hs] doubles); thread (k, m) forms its member return in
-//       ascending h and leaves it in its row's first double.  The statistics run in PASSES of nth / M whole candidates, as
-//       wf_scenario_reduce_kernel's: thread (k, m) counts its rank over the M members of its candidate — (return, m)
-//       ascending — and scatters its return to sorted[k][rank] (a pass's [nth] doubles); thread k adds the mean in ascending m
-//       and the tail in ascending rank, forms the score, leaves it in the candidate's FIRST entry (member 0's return has been
-//       added by then: no [K] array of its own, K reaches 4096 when M = H = 1) and keeps its argmax.  A fixed-order tree over the
-//       threads follows.  Then wf_plan_advance_kernel's update over the K scores: thread k counts rank_k (a broadcast read per
+//       ascending h and leaves it in its row's first double.  The statistics and the choice are the ensemble's
+//       (wf_member_statistics over the returns at stride Hs, then wf_argmax_tree); what they emit here is (mean, tail mean) in
+//       the last launch, and the score into the candidate's FIRST entry (member 0's return has been added by then: no [K]
+//       array of its own, K reaches 4096 when M = H = 1).  Then wf_plan_advance_kernel's update over the K scores: thread k counts rank_k (a broadcast read per
 //       j) and flags the elites; thread e of the [H][N] elements adds the elites' actions in ascending k in float64, divides
 //       once by E and stores the mean, and copies the winner's action where the winner is not candidate 0.  In the LAST
 //       launch the member returns and every candidate's (mean, tail mean) also go to the slot's blocks in global memory: the
@@ -38,80 +34,19 @@
 // block-uniform control flow — the branches around them test kernel arguments only.  The library is built with
 // -ffp-contract=off: every product and sum is one rounding.
 //
-// KNOWN SECOND COPIES: the path walk and the member statistics restate scenario/wf_scenario_kernels.hip's, the
-// candidate draw and the update plan/wf_plan_kernels.hip's; those files are left as they were.
+// KNOWN SECOND COPY: the candidate draw and the update restate plan/wf_plan_kernels.hip's; that file is left as
+// it was.
 #include <hip/hip_runtime.h>
-
-#include <climits>
 
 #include "../ext/wf_deviate.h"
 #include "../wf_philox.h"
 #include "wf_scenplan.h"
 
 #define WF_SCENPLAN_WIDE 8192  // floats of power per slot (R N) from which the advance kernel runs 1024 threads
-#define WF_SCENPLAN_IN_VGPR(v) asm volatile("" : "+v"(v))  // the value is held in a vector register from here on
 
 __global__ __launch_bounds__(256) void wf_scenplan_paths_kernel(const WfScenPlanPathsArgs a, int Hs) {
   extern __shared__ double sp_tile[];
-  const int tid = threadIdx.x, nth = blockDim.x;
-  const int M = a.M, H = a.H, MH = M * H, R = a.K * MH;
-  double* sp = sp_tile;      // [M][Hs] deviates of stream 17, then the stored speeds
-  double* dr = sp + M * Hs;  // [M][Hs] ... of stream 18, then the stored directions
-  const int slot = blockIdx.x;
-  const int b = wf_slot_farm(a.sl, slot);
-  const bool writes = slot < a.sl.n_slots;
-  const size_t in = writes ? slot : 0;  // the slot's input block
-  double Sc = a.ws[(size_t)b * a.wind_stride], Dc = a.wd[(size_t)b * a.wind_stride];
-  WF_SCENPLAN_IN_VGPR(Sc); WF_SCENPLAN_IN_VGPR(Dc);
-  double Sa = a.anchor ? a.anchor[in * 2] : Sc, Da = a.anchor ? a.anchor[in * 2 + 1] : Dc;
-  // the walk's parameters live in vector registers, as wf_scenario_layout_kernel's: block-uniform values held in scalar ones
-  // across the Philox rounds of the draws would not fit
-  double ws_revert = a.ws_revert, ws_sigma = a.ws_sigma, wd_revert = a.wd_revert, wd_sigma = a.wd_sigma;
-  double ws_lo = a.ws_lo, ws_hi = a.ws_hi;
-  WF_SCENPLAN_IN_VGPR(Sa); WF_SCENPLAN_IN_VGPR(Da);
-  WF_SCENPLAN_IN_VGPR(ws_revert); WF_SCENPLAN_IN_VGPR(ws_sigma); WF_SCENPLAN_IN_VGPR(wd_revert); WF_SCENPLAN_IN_VGPR(wd_sigma);
-  WF_SCENPLAN_IN_VGPR(ws_lo); WF_SCENPLAN_IN_VGPR(ws_hi);
-  const unsigned long long hi = (unsigned long long)b << 32;
-  for (int i = tid; i < MH; i += nth) {
-    const int m = i / H, j = i - m * H;
-    const unsigned long long ctr = hi | (unsigned)(m * 64 + j);
-    sp[m * Hs + j] = wf_deviate(a.seed, ctr, 17u);
-    dr[m * Hs + j] = wf_deviate(a.seed, ctr, 18u);
-  }
-  __syncthreads();
-  for (int m = tid; m < M; m += nth) {  // the walkers: thread m keeps member m's state (M <= 64 <= nth: one trip)
-    unsigned r[4];
-    philox4x32_10(a.seed, hi | (unsigned)m, 16u, r);
-    const double rate = a.wd_ramp * (2.0 * u01(r[0], r[1]) - 1.0);
-    double x = Sc, y = Dc;
-    double* s = sp + m * Hs;
-    double* d = dr + m * Hs;
-    for (int j = 0; j < H; ++j) {
-      x = (x + ws_revert * (Sa - x)) + ws_sigma * s[j];
-      const double mu = Da + rate * (double)(j + 1);
-      y = (y + wd_revert * (mu - y)) + wd_sigma * d[j];
-      double w = fmod(y, 360.0);
-      if (w < 0.0) w += 360.0;
-      s[j] = fmin(fmax(x, ws_lo), ws_hi);
-      d[j] = w;
-    }
-  }
-  __syncthreads();
-  double* __restrict__ ews = a.ews + (size_t)slot * R;
-  double* __restrict__ ewd = a.ewd + (size_t)slot * R;
-  for (int r = tid; r < R; r += nth) {
-    const int km = r / H, h = r - km * H, m = km % M;
-    ews[r] = sp[m * Hs + h];
-    ewd[r] = dr[m * Hs + h];
-  }
-  if (writes && a.wind_paths) {
-    double* __restrict__ paths = a.wind_paths + in * MH * 2;
-    for (int i = tid; i < MH; i += nth) {
-      const int m = i / H, j = i - m * H;
-      paths[2 * i] = sp[m * Hs + j];
-      paths[2 * i + 1] = dr[m * Hs + j];
-    }
-  }
+  wf_ensemble_tiles(a.ens, a.sl, a.K, a.ens.H, Hs, sp_tile, a.ews, a.ewd, a.wind_paths);  // (one tile: Ht = H)
 }
 
 // The phases below read the run's block (WfScenPlanRun, device memory) and name the slot's blocks themselves, where they use
@@ -136,7 +71,7 @@ __device__ __forceinline__ void wf_scenplan_reduce(const WfScenPlanRun& a, const
   }
   {
     double gamma = a.gamma;
-    WF_SCENPLAN_IN_VGPR(gamma);
+    WF_IN_VGPR(gamma);
     double* const mret = last ? a.mret + (size_t)slot * KM : nullptr;
     for (int km = tid; km < KM; km += nth) {
       double* r = rw + km * Hs;
@@ -151,56 +86,12 @@ __device__ __forceinline__ void wf_scenplan_reduce(const WfScenPlanRun& a, const
   }
   __syncthreads();
   const int Ks = M * Hs;  // doubles from a candidate's first entry to the next candidate's
-  {
-    const int spp = nth / M;  // whole candidates per pass (M <= 64 <= nth)
-    const int kk = tid / M, m = tid - kk * M;
-    const int q = a.q;
-    double lam = a.lam;
-    WF_SCENPLAN_IN_VGPR(lam);
-    double* const stat = last ? a.stat + (size_t)slot * K * 2 : nullptr;
-    double best_v = -HUGE_VAL;
-    int best_k = INT_MAX;
-    for (int k0 = 0; k0 < K; k0 += spp) {  // (block-uniform)
-      const bool member = kk < spp && k0 + kk < K;
-      double rv = 0.0;
-      int rank = 0;
-      if (member) {
-        const double* s = rw + (size_t)(k0 + kk) * Ks;
-        rv = s[m * Hs];
-        for (int j = 0; j < M; ++j) {
-          const double vj = s[j * Hs];
-          rank += (vj < rv) || (vj == rv && j < m);
-        }
-      }
-      __syncthreads();  // (the previous pass's tails have been added)
-      if (member) bv[kk * M + rank] = rv;
-      __syncthreads();
-      if (tid < spp && k0 + tid < K) {
-        const int k = k0 + tid;
-        double* s = rw + (size_t)k * Ks;
-        double sum = 0.0, tail = 0.0;
-        for (int j = 0; j < M; ++j) sum += s[j * Hs];
-        for (int j = 0; j < q; ++j) tail += bv[tid * M + j];
-        const double mean = sum / (double)M, cvar = tail / (double)q;
-        const double score = ((1.0 - lam) * mean) + (lam * cvar);
-        if (stat) { stat[2 * k] = mean; stat[2 * k + 1] = cvar; }
-        s[0] = score;  // (member 0's return has been added, and ranked before the barriers: the entry is the candidate's score from here on)
-        if (score > best_v || (score == best_v && k < best_k)) { best_v = score; best_k = k; }
-      }
-    }
-    __syncthreads();  // (the last pass's tails have been added: bv becomes the tree)
-    bv[tid] = best_v;
-    bi[tid] = best_k;
-  }
-  __syncthreads();
-  for (int s = nth >> 1; s > 0; s >>= 1) {  // (block-uniform)
-    if (tid < s) {
-      const double x = bv[tid + s];
-      const int k = bi[tid + s];
-      if (x > bv[tid] || (x == bv[tid] && k < bi[tid])) { bv[tid] = x; bi[tid] = k; }
-    }
-    __syncthreads();
-  }
+  double* const stat = last ? a.stat + (size_t)slot * K * 2 : nullptr;
+  const WfBest top = wf_member_statistics(rw, Hs, K, M, a.q, a.lam, bv, [rw, Ks, stat](int k, double mean, double cvar, double score) {
+    if (stat) { stat[2 * k] = mean; stat[2 * k + 1] = cvar; }
+    rw[(size_t)k * Ks] = score;  // (the candidate's first entry is its score from here on)
+  });
+  wf_argmax_tree(top, bv, bi);
   const int E = a.E;
   for (int k = tid; k < K; k += nth) {
     const double rk = rw[(size_t)k * Ks];
@@ -212,7 +103,7 @@ __device__ __forceinline__ void wf_scenplan_reduce(const WfScenPlanRun& a, const
     el[k] = rank < E;
   }
   __syncthreads();
-  const int w = bi[0] == INT_MAX ? 0 : bi[0];
+  const int w = wf_argmax_winner(bi);
   const int HN = H * N;
   const float* cand = a.cand + (size_t)slot * K * HN;
   float* const best = a.best + (size_t)slot * HN;
@@ -343,8 +234,8 @@ __global__ __launch_bounds__(1024) void wf_scenplan_advance_kernel(const WfScenP
   // does not fit (a spilled scalar register; tests/test_scenplan.py reads the metadata).  Block-uniform all the same
   int vv = v, Iv = I, o_bv = L.bv, o_bi = L.bi, o_el = L.el;
   double sg = sigma;
-  WF_SCENPLAN_IN_VGPR(vv); WF_SCENPLAN_IN_VGPR(Iv); WF_SCENPLAN_IN_VGPR(sg);
-  WF_SCENPLAN_IN_VGPR(o_bv); WF_SCENPLAN_IN_VGPR(o_bi); WF_SCENPLAN_IN_VGPR(o_el);
+  WF_IN_VGPR(vv); WF_IN_VGPR(Iv); WF_IN_VGPR(sg);
+  WF_IN_VGPR(o_bv); WF_IN_VGPR(o_bi); WF_IN_VGPR(o_el);
   double* const bv = reinterpret_cast<double*>(lds + o_bv);
   int* const bi = reinterpret_cast<int*>(lds + o_bi);
   if (v > 0)  // (block-uniform)
@@ -354,15 +245,15 @@ __global__ __launch_bounds__(1024) void wf_scenplan_advance_kernel(const WfScenP
     wf_scenplan_seed(*run, sl_);
   __syncthreads();  // (mean and best sequence in global memory: other threads of the block read them below)
   if (vv < Iv) wf_scenplan_layout(*run, sl_, vv, sg);  // (no barrier below this line)
-  else wf_scenplan_outputs(*run, sl_, bv[0], bi[0] == INT_MAX ? 0 : bi[0]);
+  else wf_scenplan_outputs(*run, sl_, bv[0], wf_argmax_winner(bi));
 }
 
 extern "C" hipError_t wfk_launch_scenplan_paths(const WfScenPlanPathsArgs* a, hipStream_t s) {
-  const int MH = a->M * a->H;
-  if (MH > 2048) return hipErrorInvalidValue;  // (one tile: K >= 3 keeps M H <= 1365)
+  const int MH = a->ens.M * a->ens.H;
+  if (MH > WF_ENSEMBLE_TILE) return hipErrorInvalidValue;  // (one tile: K >= 3 keeps M H <= 1365)
   const int threads = a->K * MH <= 128 ? 64 : 256;
-  const int Hs = a->H | 1;
-  hipLaunchKernelGGL(wf_scenplan_paths_kernel, dim3(a->sl.C), dim3(threads), sizeof(double) * 2 * (size_t)a->M * Hs, s, *a, Hs);
+  const int Hs = a->ens.H | 1;
+  hipLaunchKernelGGL(wf_scenplan_paths_kernel, dim3(a->sl.C), dim3(threads), sizeof(double) * 2 * (size_t)a->ens.M * Hs, s, *a, Hs);
   return hipGetLastError();
 }
 extern "C" hipError_t wfk_launch_scenplan_advance(const WfScenPlanRun* host, const WfScenPlanRun* dev, const WfSlots* sl, int v, double sigma,

@@ -37,9 +37,6 @@ struct call_buf {
   ~call_buf() { hipFree(p); }
 };
 
-bool in_unit(double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; }
-bool non_negative(double v) { return std::isfinite(v) && v >= 0.0; }
-
 // the parent still holds a wind per farm and is not in wf_wind_series mode (the cheap check of include/wfwindgen.h)
 bool parent_plays(const wf_windgen* g) {
   const wf_handle* h = g->h;
