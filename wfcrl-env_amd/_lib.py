@@ -418,15 +418,28 @@ POLSCEN_ABI = {
     "wf_polscen_last_error": (C.c_char_p, [_P]),
 }
 
+# every symbol include/wfpolsearch.h declares (policy search: CEM over MLP weights): its own table
+POLSEARCH_ABI = {
+    "wf_polsearch_create": (C.c_int, [_P, _P, _P, C.POINTER(_P)]),
+    "wf_polsearch_destroy": (C.c_int, [_P]),
+    "wf_polsearch_run": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_ulonglong, C.c_int, C.c_double, _P,
+                                   C.c_int, C.POINTER(WindProcess), C.c_double, C.c_double, C.c_ulonglong, C.c_int, C.c_double, _P,
+                                   C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int]),
+    "wf_polsearch_set_timing": (C.c_int, [_P, C.c_int]),
+    "wf_polsearch_last_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "wf_polsearch_kernel_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "wf_polsearch_last_error": (C.c_char_p, [_P]),
+}
+
 _lib = None
 
 
 def build(force: bool = False) -> Path:
     """Compile csrc/ into libwfstep.so with hipcc for gfx950 (cross-compiles without a GPU)."""
     srcs = []
-    for d in ("", "ext", "modelset", "probe", "yawopt", "rose", "robust", "grad", "credit", "lookahead", "plan", "series", "rollout", "retgrad", "windgen", "scenario", "scenplan", "calib", "policy", "polscen", "rollscen"):  # csrc/ itself, the extensions' shared layer, the extensions
+    for d in ("", "ext", "modelset", "probe", "yawopt", "rose", "robust", "grad", "credit", "lookahead", "plan", "series", "rollout", "retgrad", "windgen", "scenario", "scenplan", "calib", "policy", "polscen", "polsearch", "rollscen"):  # csrc/ itself, the extensions' shared layer, the extensions
         srcs += sorted((PKG_DIR / "csrc" / d).glob("*.hip")) + sorted((PKG_DIR / "csrc" / d).glob("*.h"))
-    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfmodelset.h", "wfprobe.h", "wfyawopt.h", "wfrose.h", "wfrobust.h", "wfgrad.h", "wfcredit.h", "wflookahead.h", "wfplan.h", "wfseries.h", "wfrollout.h", "wfretgrad.h", "wfwindgen.h", "wfscenario.h", "wfscenplan.h", "wfcalib.h", "wfpolicy.h", "wfpolscen.h", "wfrollscen.h")]
+    srcs += [PKG_DIR.parent / "include" / h for h in ("wfstep.h", "wfmodelset.h", "wfprobe.h", "wfyawopt.h", "wfrose.h", "wfrobust.h", "wfgrad.h", "wfcredit.h", "wflookahead.h", "wfplan.h", "wfseries.h", "wfrollout.h", "wfretgrad.h", "wfwindgen.h", "wfscenario.h", "wfscenplan.h", "wfcalib.h", "wfpolicy.h", "wfpolscen.h", "wfpolsearch.h", "wfrollscen.h")]
     stale = (not LIB_PATH.exists()) or any(s.stat().st_mtime > LIB_PATH.stat().st_mtime for s in srcs)
     if force or stale:
         subprocess.run(["make", "-j4", "-C", str(PKG_DIR / "csrc")] + (["-B"] if force else []), check=True)
@@ -457,7 +470,7 @@ def load() -> C.CDLL:
             build()
         _share_hip_runtime_with_torch()
         lib = C.CDLL(str(LIB_PATH))
-        for table in (ABI, MODELSET_ABI, PROBE_ABI, YAWOPT_ABI, ROSE_ABI, ROBUST_ABI, GRAD_ABI, CREDIT_ABI, LOOKAHEAD_ABI, PLAN_ABI, SERIES_ABI, ROLLOUT_ABI, RETGRAD_ABI, WINDGEN_ABI, SCENARIO_ABI, SCENPLAN_ABI, CALIB_ABI, POLICY_ABI, POLSCEN_ABI, ROLLSCEN_ABI):
+        for table in (ABI, MODELSET_ABI, PROBE_ABI, YAWOPT_ABI, ROSE_ABI, ROBUST_ABI, GRAD_ABI, CREDIT_ABI, LOOKAHEAD_ABI, PLAN_ABI, SERIES_ABI, ROLLOUT_ABI, RETGRAD_ABI, WINDGEN_ABI, SCENARIO_ABI, SCENPLAN_ABI, CALIB_ABI, POLICY_ABI, POLSCEN_ABI, POLSEARCH_ABI, ROLLSCEN_ABI):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
                 fn.restype, fn.argtypes = res, args

@@ -938,6 +938,54 @@ class WfStep:
         """vgprs / static LDS bytes / private-segment bytes of the kernels a policy_scenarios run launches."""
         return self._polscen().kernel_info()
 
+    # -- policy search: CEM over MLP weights (include/wfpolsearch.h) --------------------------------------
+    def _polsearch(self) -> "_PolSearch":
+        """The handle's policy-search object, created on its policy and polscen objects on first use; destroyed in close()
+        before them."""
+        po = getattr(self, "_polsearch_obj", None)
+        if po is None:
+            po = self._polsearch_obj = _PolSearch(self)
+        return po
+
+    def search_policy(self, mean, spec, horizon, sigma=0.5, candidates=32, elites=8, iterations=4, sigma_min=0.0, seed=0, gamma=1.0,
+                      wind=None, members=None, process=None, scenario_seed=0, tail=None, risk_weight=0.0, anchor=None,
+                      bounds=(3.0, 28.0), farms=None, strict=False, max_eval_farms=65536,
+                      want=("best_params", "best_fitness", "init_fitness", "mean", "sigma"), out=None) -> dict:
+        """A cross-entropy search over the weights of one small MLP policy, in one call and on the device: per iteration K
+        candidates — the incumbent, the mean, K - 2 Philox draws mean + sigma z per weight —, their fitness = the mean over the
+        listed farms of policy_returns' return (or, with `members`, of policy_scenarios' score), the `elites` best refit mean
+        and width per weight (include/wfpolsearch.h; the project's own definition, PARITY UNPINNED beyond the oracle:
+        tests/search_ref.py).  The env state and the wind are read and never changed.  The rollouts run on the policy (or
+        policy-scenario) object of this handle: policy_returns(candidates[i]) afterwards returns farm_scores[i] bit for bit.
+
+          mean        (P,) float32 the start vector (policy.policy_from_torch gives one) — torch CUDA tensor or NumPy
+          spec        policy.mlp_spec(...)
+          horizon     H, the scorer's
+          sigma       (P,) float32 widths >= 0, or a scalar for all weights
+          candidates  K in 3..64;  elites E in 1..K;  iterations I in 1..16
+          sigma_min   added to every refitted width (>= 0): the only schedule
+          seed        of the draws: a draw depends on (seed, k, p, i) only
+          gamma, wind, farms, strict, max_eval_farms   as policy_returns takes them
+          members     None: policy_returns scores; M: policy_scenarios scores over M members with `process`, `scenario_seed`
+                      (the same in every iteration), `tail`, `risk_weight`, `anchor`, `bounds`
+          want        of "best_params" (P,) float32, "best_fitness", "init_fitness" () float64, "mean", "sigma" (P,) float32 —
+                      the next call's warm start —, "fitness" (I, K) float64, "winner" (I,) int32, "candidates" (I, K, P)
+                      float32, "sigma_history" (I, P) float32, "farm_scores" (I, n, K) float64
+          out         dict of tensors / arrays of those names to write into
+        Deterministic: fixed summation orders, no atomics; fitness[i][0] has the bits of max fitness[i - 1].  With torch
+        tensors the call only enqueues work on torch's current stream and returns torch CUDA tensors."""
+        return self._polsearch().run(mean, spec, horizon, sigma, candidates, elites, iterations, sigma_min, seed, gamma, wind, members,
+                                     process, scenario_seed, tail, risk_weight, anchor, bounds, farms, strict, max_eval_farms, want, out)
+
+    def search_policy_timing(self, detail=None) -> dict:
+        """As yawopt_timing, for the last search_policy {"total_ms", "step_ms", "glue_ms"}: step_ms is the scorer's runs,
+        glue_ms this extension's own kernels."""
+        return self._polsearch().timing(detail)
+
+    def search_policy_kernel_info(self) -> dict:
+        """vgprs / static LDS bytes / private-segment bytes of the policy-search kernels as the runtime reports them."""
+        return self._polsearch().kernel_info()
+
     # -- scenario look-ahead: returns of action sequences over a wind ensemble (include/wfscenario.h) ------
     def _scenario(self) -> "_Scenario":
         """The handle's scenario object; created on first use, destroyed in close() before the handle."""
@@ -1605,9 +1653,9 @@ class WfStep:
         if getattr(self, "_h", None) is not None and self._h.value:
             # an extension object goes before its handle (include/wfprobe.h, wfyawopt.h, wfrose.h, wfrobust.h, wfgrad.h,
             # wfcredit.h, wflookahead.h, wfpolicy.h, wfplan.h, wfretgrad.h, wfrollout.h, wfrollscen.h, wfcalib.h — the rollout and the scenario-rollout
-            # object, created on the rose object, before it)
+            # object, created on the rose object, before it; the policy-search object before the policy and polscen objects)
             for name in ("_probe_points", "_probe_plane", "_yawopt_obj", "_rollout_obj", "_rollscen_obj", "_rose_obj", "_robust_obj", "_grad_obj", "_credit_obj",
-                         "_lookahead_obj", "_policy_obj", "_polscen_obj", "_scenario_obj", "_plan_obj", "_scenplan_obj", "_retgrad_obj", "_calib_obj", "_windgen_obj"):
+                         "_lookahead_obj", "_polsearch_obj", "_policy_obj", "_polscen_obj", "_scenario_obj", "_plan_obj", "_scenplan_obj", "_retgrad_obj", "_calib_obj", "_windgen_obj"):
                 ext = getattr(self, name, None)
                 if ext is not None:
                     ext.close()
@@ -2287,6 +2335,88 @@ class _PolScen(_Policy):
         self._call("run", params.data_ptr() if on_device else params.ctypes.data, K, P, H, M, C.byref(p), ws_lo, ws_hi,
                    C.c_ulonglong(int(seed) & (2**64 - 1)), float(gamma), q, float(risk_weight), aptr, n, fptr,
                    *[ptr.get(k) for k in self.OUTPUTS], int(on_device))
+        return {k: out[k] for k in spec_out}
+
+
+class _PolSearch(_Ext):
+    """The `wf_polsearch` object of a WfStep handle (include/wfpolsearch.h), created on the handle's policy and polscen objects:
+    it owns no evaluator, the rollouts run on theirs."""
+
+    NAME = "polsearch"
+    KERNELS = ("tiles", "advance")
+    OUTPUTS = ("best_params", "best_fitness", "init_fitness", "mean", "sigma", "fitness", "winner", "candidates", "sigma_history",
+               "farm_scores")
+
+    def __init__(self, owner: WfStep):
+        self._w, self._lib = owner, owner._lib
+        self._r = C.c_void_p()
+        check(self._fn("create")(owner._h, owner._policy()._r, owner._polscen()._r, C.byref(self._r)), owner._h)
+
+    def _vector(self, a, on_device, like, name):
+        """(the float32 vector kept alive, its pointer): a torch CUDA tensor on the device path, a NumPy array else."""
+        if on_device:
+            import torch
+
+            if not _is_torch(a):
+                a = torch.as_tensor(np.array(a, np.float32), device=like.device)
+            assert a.is_cuda and a.dtype == torch.float32, name
+            a = a.contiguous().reshape(-1)
+            return a, a.data_ptr()
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        return a, a.ctypes.data
+
+    def run(self, mean, spec, horizon, sigma, candidates, elites, iterations, sigma_min, seed, gamma, wind, members, process,
+            scenario_seed, tail, risk_weight, anchor, bounds, farms, strict, max_eval_farms, want, out):
+        w = self._w
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.OUTPUTS for k in want):
+            raise ValueError("want must name " + ", ".join(self.OUTPUTS[:-1]) + " and / or " + self.OUTPUTS[-1])
+        H, K, E, I = int(horizon), int(candidates), int(elites), int(iterations)
+        M, q, ws_lo, ws_hi = 0, 0, 0.0, 0.0
+        proc = None
+        # network, strict and max_eval_farms are the scorer's settings: the scorer object takes them as its own wrapper does
+        scorer = w._policy()
+        if members is not None:
+            scorer = w._polscen()
+            proc = _wind_process(process, "search_policy")
+            M, q, ws_lo, ws_hi = self._members_tail_bounds(members, tail, bounds)
+            if M < 1:
+                raise ValueError("members must be >= 1 (None: policy_returns scores, under the wind held or a wind per step)")
+            if wind is not None:
+                raise ValueError("wind and members exclude each other: the members' paths are the wind")
+        scorer._set_network(spec)
+        scorer._call("config", int(bool(strict)), int(max_eval_farms or 0))
+        fa, n, fptr = self._farms(farms)
+        ins = [mean, sigma, wind, anchor] + list((out or {}).values())
+        on_device = any(_is_torch(v) for v in ins)
+        like = next((v for v in ins if _is_torch(v)), None)
+        if on_device:
+            w._follow_torch_stream()
+        mean, mptr = self._vector(mean, on_device, like, "mean")
+        P = int(mean.shape[0])
+        if not _is_torch(sigma) and np.ndim(sigma) == 0:
+            sigma = np.full(P, float(sigma), np.float32)
+        sigma, sptr = self._vector(sigma, on_device, like, "sigma")
+        if int(sigma.shape[0]) != P:
+            raise ValueError("sigma must be a scalar or (P,): a width per weight")
+        wind, wptr = self._f64(wind, (n, H, 2), "wind", "(n_farms, H, 2): the (speed, direction) every step of the horizon is solved under",
+                               on_device, like)
+        aptr = None
+        if members is not None:
+            anchor, aptr = self._anchor(anchor, n, on_device, like)
+        f8, f4, i4 = np.float64, np.float32, np.int32
+        shapes = {"best_params": ((P,), f4), "best_fitness": ((), f8), "init_fitness": ((), f8), "mean": ((P,), f4), "sigma": ((P,), f4),
+                  "fitness": ((I, K), f8), "winner": ((I,), i4), "candidates": ((I, K, P), f4), "sigma_history": ((I, P), f4),
+                  "farm_scores": ((I, n, K), f8)}
+        if not (3 <= K <= 64 and 1 <= I <= 16):  # (the library names the limit; no output is sized from a refused shape)
+            shapes = {k: ((0,), d) for k, (_, d) in shapes.items()}
+            out = None
+        spec_out = {k: shapes[k] for k in self.OUTPUTS if k in want}
+        out, ptrs = self._outputs(out, spec_out, on_device, like)
+        ptr = dict(zip(spec_out, ptrs))
+        self._call("run", mptr, sptr, P, K, E, I, float(sigma_min), C.c_ulonglong(int(seed) & (2**64 - 1)), H, float(gamma), wptr, M,
+                   None if proc is None else C.byref(proc), ws_lo, ws_hi, C.c_ulonglong(int(scenario_seed) & (2**64 - 1)), q,
+                   float(risk_weight), aptr, n, fptr, *[ptr.get(k) for k in self.OUTPUTS], int(on_device))
         return {k: out[k] for k in spec_out}
 
 

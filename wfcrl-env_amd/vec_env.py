@@ -884,6 +884,68 @@ class VecWindFarmEnv:
                                         risk_weight=risk_weight, anchor=anchor, bounds=bounds, farms=farms, strict=strict,
                                         max_eval_farms=max_eval_farms, want=want)
 
+    def search_policy(self, policy, horizon, sigma=0.5, candidates=32, elites=8, iterations=4, sigma_min=0.0, seed=0, gamma=1.0,
+                      wind=None, members=None, process=None, scenario_seed=0, tail=None, risk_weight=0.0, anchor=None, bounds=None,
+                      farms=None, strict=False, max_eval_farms=65536,
+                      want=("best_params", "best_fitness", "init_fitness", "mean", "sigma"), kind=None, out_scale=1.0, shift=None,
+                      scale=None, use_freewind=False):
+        """A cross-entropy search over the weights of one MLP policy from the state the env is in, in one call and on the
+        device — call it BEFORE `step`; the env state is read and never changed (include/wfpolsearch.h;
+        backend.WfStep.search_policy has the arguments; the project's own definition).  `policy` is taken as policy_returns
+        takes it — (params, spec) with ONE parameter vector, the start, or an nn.Sequential converted with `kind`, out_scale,
+        shift, scale and use_freewind (policy.policy_from_torch).  The fitness of a candidate is the mean over the listed farms
+        of policy_returns' return — wind as policy_returns takes it, "series" included —, or with `members` of
+        policy_scenarios' score under the env's wind_process and speed bounds (or `process`, `bounds`).  Returns the outputs
+        `want` names, torch CUDA tensors when the env returns torch; "mean" and "sigma" fed back as policy=(mean, spec) and
+        sigma= warm-start the next call."""
+        from . import policy as P
+
+        if type(self.reward_shaper).__name__ != "DoNothingReward":
+            raise ValueError("search_policy needs the plain reward (DoNothingReward): the return of a shaped reward is "
+                             "not defined here")
+        series = isinstance(wind, str) and wind == "series"
+        if members is None:
+            if series and not self._playing:
+                raise ValueError('wind="series" needs a time-series episode: this env has no wind_time_series')
+            if self._playing and wind is None:
+                raise NotImplementedError("search_policy on a time-series episode needs wind=(n_farms, horizon, 2): the series "
+                                          "tick precedes the step, so the wind of the coming steps is not the one the env holds "
+                                          '(or wind="series": the series\' coming rows), or members= for a wind ensemble')
+        else:
+            if process is None:
+                if self._wind_process is None:
+                    raise ValueError("search_policy with members needs a wind process: this env was built without wind_process, "
+                                     "so pass process=dict(ws_revert=, ws_sigma=, wd_revert=, wd_sigma=, wd_ramp=)")
+                process = self._wind_process
+                if bounds is None and self._wind_dist is not None:
+                    bounds = (float(self._wind_dist.get("ws_lo", 3.0)), float(self._wind_dist.get("ws_hi", 28.0)))
+        if bounds is None:
+            bounds = (3.0, 28.0)
+        if isinstance(policy, tuple) and len(policy) == 2 and isinstance(policy[1], dict):
+            params, spec = policy
+        else:
+            if kind is None:
+                raise ValueError('a torch module needs kind="central" or kind="shared"')
+            params, spec = P.policy_from_torch(policy, kind, out_scale=out_scale, shift=shift, scale=scale, use_freewind=use_freewind)
+        if len(tuple(params.shape)) == 2 and int(params.shape[0]) == 1:
+            params = params[0]
+        if len(tuple(params.shape)) != 1:
+            raise ValueError("search_policy starts from ONE parameter vector (P,): pass one policy")
+        if series and members is None:
+            wind = self.fi.wind_preview(int(horizon), first=1, farms=farms, as_torch=self.return_torch)[0]
+        if self.return_torch:
+            import torch
+
+            dev = f"cuda:{self.fi.device_id}"
+            params = self._to_device(params)
+            anchor = None if anchor is None else self._to_device(anchor).double()
+            if wind is not None:  # (float64 all the way: the rows' wind is not rounded to float32)
+                wind = wind.to(device=dev, dtype=torch.float64) if isinstance(wind, torch.Tensor) else torch.as_tensor(np.asarray(wind, np.float64), device=dev)
+        return self.fi.search_policy(params, spec, horizon, sigma=sigma, candidates=candidates, elites=elites, iterations=iterations,
+                                     sigma_min=sigma_min, seed=seed, gamma=gamma, wind=wind, members=members, process=process,
+                                     scenario_seed=scenario_seed, tail=tail, risk_weight=risk_weight, anchor=anchor, bounds=bounds,
+                                     farms=farms, strict=strict, max_eval_farms=max_eval_farms, want=want)
+
     def _series_keyword(self, name, wind, steps):
         """The wind keyword of counterfactual_rewards / lookahead_returns: None or "series"; a time-series episode needs
         "series", any other episode None."""
